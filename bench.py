@@ -1,13 +1,23 @@
 #!/usr/bin/env python3
 """Benchmark of the Lippmann-Schwinger basic-scheme pass on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--n 256] [--mixing voigt|laminate]
+    python bench.py --gpus N --steps K --warmup W [--n 256] [--mixing voigt|laminate] [--dump-outputs DIR] [--full]
 
 A "step" is one LS iteration (one basicScheme pass, F:20558-20578) on a synthetic fibre RVE resident in HBM
 (non-overlapping capsules from the build's seeded placer).
 
-  N = 1   the single-GPU displacement loop.  The K-step region is timed `--repeats` times, `ms_per_step` is the
-          median; `sustained_it_s` is a >= 2 s run; `run_load_case_it_s` times fg_run_load_case (stop rule included);
+A plain run does what its headline figure needs and nothing else: set-up, W warm-up steps, ONE region of exactly K timed
+steps (`ms_per_step` = its time / K), the outputs if --dump-outputs is given, the JSON line.  Everything else below (the
+repeated regions, sustained and stop-rule rates, per-kernel HIP events, roofline and counter passes, the other grids, the
+slab driver, CG, the CPU baseline, the load-case replicas of N > 1) runs with --full only; there the K-step region is timed
+`--repeats` times (default 7) and `ms_per_step` is the median.
+
+--dump-outputs DIR: after the timed steps, what a caller of the timed path receives -- the strain and stress fields
+(fg_get_field) and their means -- as DIR/<name>.npy, float64; grids above 2^18 voxels as a fixed, seeded sample of voxels.
+The inputs are seeded: the same arguments give the same inputs in every run.
+
+  N = 1   the single-GPU displacement loop.  --full: `sustained_it_s` is a >= 2 s run; `run_load_case_it_s` times
+          fg_run_load_case (stop rule included);
           `also` carries the other BASELINE sizes (128^3 Voigt, 512^3 laminate = the north-star target config);
           `slab_forced` the same problem through the slab driver as ONE slab; `cpu_baseline` the reference's loop in
           C/OpenMP on the host cores (thread sweep + the reference's default of one thread).
@@ -18,7 +28,7 @@ A "step" is one LS iteration (one basicScheme pass, F:20558-20578) on a syntheti
           has touched the GPU -- relays rank 0's line and exits with the ranks' code.  The line names the ranks' devices
           (PCI bus ids), the transport and the time the exchanges take (`alltoall_ms`).
 
-Rank 0 prints one JSON line (metric of BASELINE.json: LS iterations/s, plus the HBM roofline of the dominant kernel).
+Rank 0 prints one JSON line (metric of BASELINE.json: LS iterations/s; with --full also the HBM roofline of the dominant kernel).
 """
 import argparse
 import json
@@ -87,6 +97,46 @@ def timed_regions(iterate, sync, steps, warmup, repeats):
         sync()
         out.append(time.perf_counter() - t0)
     return out
+
+
+DUMP_SAMPLE = 1 << 18   # --dump-outputs: voxels per field written; larger grids are sampled (seeded, the same in every run)
+DUMP_FIELDS = ("epsilon", "sigma")
+
+
+def dump_sample_index(n):
+    """flat C-order voxel indices of the --dump-outputs sample of an n-grid (sorted; None = every voxel)"""
+    N = n[0] * n[1] * n[2]
+    if N <= DUMP_SAMPLE:
+        return None
+    return np.sort(np.random.default_rng(0).choice(N, DUMP_SAMPLE, replace=False))
+
+
+def dump_outputs(directory, s, n, gather=None, rank=0):
+    """What a caller of the timed path receives after its last step: the strain and stress fields and their means, as
+    <directory>/<name>.npy (float64).  Slab solvers (N > 1): each rank samples its own x-slab, `gather` collects the pieces
+    on rank 0 in rank order, which is the order of the global indices."""
+    idx = dump_sample_index(n)
+    out = {}
+    for name in DUMP_FIELDS:
+        f = s.get_field(name)
+        nc = f.shape[0]
+        f = f.reshape(nc, -1)
+        if gather is None:
+            out[name] = f if idx is None else f[:, idx]
+            continue
+        lo = s.rank * f.shape[1]
+        sel = np.arange(lo, lo + f.shape[1]) if idx is None else idx[(idx >= lo) & (idx < lo + f.shape[1])]
+        pieces = gather(np.ascontiguousarray(f[:, sel - lo]))
+        if rank == 0:
+            out[name] = np.concatenate(pieces, axis=1)
+        del f
+    out["mean_stress"] = np.asarray(s.mean_stress(), dtype=np.float64)
+    out["mean_strain"] = np.asarray(s.mean_strain(), dtype=np.float64)
+    if rank != 0:
+        return
+    os.makedirs(directory, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def kernel_table(s, E, n, steps, scalar, stokes=False):
@@ -457,8 +507,9 @@ def cache_stream(device):
         return None
 
 
-def measure_single(args, n_edge, mixing, mode, device, E, detail):
-    """One single-GPU workload: median-of-repeats it/s (+ kernels, sustained, run_load_case when detail)."""
+def measure_single(args, n_edge, mixing, mode, device, E, detail, kernels=True, dump_dir=None):
+    """One single-GPU workload: median-of-repeats it/s (+ kernels, sustained, run_load_case when detail); the outputs of the
+    timed steps go to dump_dir (before anything else runs on the solver)."""
     from fibergen_amd import LSSolver
     from fibergen_amd.rve import bench_rve
     n = (n_edge,) * 3
@@ -475,6 +526,10 @@ def measure_single(args, n_edge, mixing, mode, device, E, detail):
            "ms_per_step_min": 1e3 * min(dts) / args.steps, "ms_per_step_max": 1e3 * max(dts) / args.steps,
            "repeats": len(dts), "rve": {"K": par["K"], "R": float(par["R"]), "L": float(par["L"]), "vf": float(phi.mean()),
                                         "interface_voxel_fraction": float(((phi > 0) & (phi < 1)).mean())}}
+    if dump_dir:
+        dump_outputs(dump_dir, s, n)
+    if not kernels:
+        return s, res, phi, normals
     kern, times, cnt = kernel_table(s, E, n, min(args.steps, 20), scalar, mode == "viscosity")
     dom = max(kern, key=lambda k: kern[k]["avg_ms"])
     res["dominant_kernel"] = {"kernel": dom, **kern[dom], "frac_of_hbm_peak": kern[dom]["GBps"] / HBM_PEAK_GBS}
@@ -542,7 +597,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=7, help="the K-step region is timed this many times; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the K-step region is timed this many times; the median is reported (default: 1, with --full 7)")
     ap.add_argument("--sustain-s", type=float, default=10.0)
     ap.add_argument("--n", "--size", dest="n", type=int, default=256, help="grid size per axis (128, 256, 512 are the BASELINE sizes; any size runs)")
     ap.add_argument("--mixing", default="voigt", choices=["voigt", "laminate"])
@@ -561,6 +617,13 @@ def main():
                     help="N = 1: do not run the two rocprofv3 counter passes that measure roofline.traffic on this box (the figure "
                          "is then read from the newest committed PMC summary and flagged as such)")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the fields and means the timed path computed as DIR/<name>.npy (float64; "
+                         "a fixed, seeded sample of voxels on grids above 2^18 voxels)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: repeated regions, sustained / stop-rule / PCIe-inclusive rates, per-kernel "
+                         "HIP events, roofline and counter passes, the `also` grids, the slab driver, CG, the CPU baseline "
+                         "(N > 1: load-case replicas, kernels and exchange times, `also_slab`, CPU baseline)")
     ap.add_argument("--cpu-budget", type=float, default=25.0)
     ap.add_argument("--slab-members", type=int, default=1,
                     help="N = 1: also run the slab driver with this many slabs on the one GPU (0 = skip)")
@@ -582,6 +645,8 @@ def main():
     launched = ("FG_BENCH_ARGV" in os.environ and "WORLD_SIZE" in os.environ and
                 os.environ.get("FG_BENCH_LAUNCHED", "") == os.environ.get("TORCHELASTIC_RUN_ID", "?"))
     args = ap.parse_args(json.loads(os.environ["FG_BENCH_ARGV"]) if launched else None)
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
 
     if args.traffic_child:
         traffic_child(args)
@@ -632,7 +697,30 @@ def main():
         E[0] = 1.0
         if stokes:
             E = np.array([1.0, -1, 0, 0, 0, 0])   # traceless prescribed stress (F:26257-26261)
-        s, res, phi, normals = measure_single(args, args.n, args.mixing, args.mode, local_rank, E, detail=True)
+        # (--method cg: `value` is the CG leg's, whose outputs are written after it)
+        dump_dir = args.dump_outputs if args.method != "cg" else None
+        s, res, phi, normals = measure_single(args, args.n, args.mixing, args.mode, local_rank, E, detail=args.full,
+                                              kernels=args.full, dump_dir=dump_dir)
+        if not args.full:
+            out = {"metric": metric, "value": res["it_s"], "unit": "it/s", "n_gpus": 1, "steps": args.steps,
+                   "warmup": args.warmup, "ms_per_step": res["ms_per_step"], "higher_is_better": True, "scaling": None,
+                   "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+                   "config": {"workload": "%d^3 two-phase fibre RVE (K=%d non-overlapping capsules, R=%.4f, L=%.3f, vf=%.3f), "
+                                          "contrast 10, mixing=%s" % (args.n, res["rve"]["K"], res["rve"]["R"], res["rve"]["L"],
+                                                                      res["rve"]["vf"], args.mixing),
+                              "grid": list(n), "mixing_rule": args.mixing, "mode": args.mode, "parallelism": "1 GPU",
+                              "timed_call": "fg_iterate (no stop-rule hand-over to the host inside the timed region)"},
+                   "ms_per_step_min": res["ms_per_step_min"], "ms_per_step_max": res["ms_per_step_max"],
+                   "repeats": res["repeats"], "rve": res["rve"]}
+            if args.method == "cg":
+                cg = cg_leg(args, s, E)
+                out.update({"metric": metric.replace("LS iterations/sec (basic scheme", "CG iterations/sec (runCGElasticity"),
+                            "value": cg["it_s"], "ms_per_step": 1e3 / cg["it_s"], "cg": cg, "basic_scheme_it_s": res["it_s"]})
+                if args.dump_outputs:
+                    dump_outputs(args.dump_outputs, s, n)
+            s.close()
+            print(json.dumps(out), flush=True)
+            return
         kern = res["kernels"]
         dom = res["dominant_kernel"]["kernel"]
         traffic, traffic_src = committed_traffic(args.n, args.mixing, dom, default_options)
@@ -696,6 +784,8 @@ def main():
         except Exception as e:  # noqa: BLE001
             out["hbm_stream"] = {"error": "%s: %s" % (type(e).__name__, e)}
         res["cg"] = cg_leg(args, s, E)   # last use of the solver
+        if args.method == "cg" and args.dump_outputs:
+            dump_outputs(args.dump_outputs, s, n)
         if args.method == "cg":
             out.update({"value": res["cg"]["it_s"], "ms_per_step": 1e3 / res["cg"]["it_s"], "cg": res["cg"],
                         "basic_scheme_it_s": it_s})
@@ -861,6 +951,12 @@ def main():
     devices = [None] * world
     dist.all_gather_object(devices, "%s rank %d: %s" % (socket.gethostname(), rank, pci_bus_id(local_rank)))
 
+    def gather_to_rank0(a):
+        """--dump-outputs: every rank's piece, in rank order, on rank 0 (host arrays through the object collective)"""
+        pieces = [None] * world if rank == 0 else None
+        dist.gather_object(a, pieces, dst=0)
+        return pieces
+
     def tune_exchange_mode(solver, E):
         """Which exchange mode the links of THIS node like better is a measurement, not a guess: a few passes with the three
         components in one all-to-all (one message per peer; latency-friendly) and with one all-to-all per component
@@ -880,7 +976,7 @@ def main():
         return best, {"one_exchange_for_three_components_ms": 1e3 * trials[0], "exchange_per_component_ms": 1e3 * trials[1]}
 
     replicas = None
-    if not args.no_replicas:
+    if args.full and not args.no_replicas:
         # every rank its own load case (calc_effective_properties' unit strains): no data-path collective
         s = LSSolver(*n, device=local_rank)
         configure(s, phi, normals, args.mixing, args.mode)
@@ -933,29 +1029,34 @@ def main():
         med = max_over_ranks(statistics.median(dts))
         lo, hi = max_over_ranks(min(dts)), max_over_ranks(max(dts))
         it_s = args.steps / med
-        local_n = (args.n // world, args.n, args.n)
-        kern, _, cnt = kernel_table(d, E, local_n, min(args.steps, 10), scalar, stokes)   # this rank's slab, HIP events
-        xt = exchange_times(d, cnt)
-        dom = max(kern, key=lambda k: kern[k]["avg_ms"])
+        if args.dump_outputs and args.method != "cg":
+            dump_outputs(args.dump_outputs, d, n, gather=gather_to_rank0, rank=rank)
         line.update({
             "value": it_s, "ms_per_step": 1e3 * med / args.steps, "scaling": "strong",
             "ms_per_step_min": 1e3 * lo / args.steps, "ms_per_step_max": 1e3 * hi / args.steps, "repeats": args.repeats,
-            "roofline": {"kernel": dom + " (rank 0's slab)", "bound": "hbm", "achieved": kern[dom]["GBps"], "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": kern[dom]["GBps"] / HBM_PEAK_GBS, "traffic": None,
-                         "alg_bytes_per_launch": int(kern[dom]["alg_GB"] * 1e9), "avg_launch_ms": kern[dom]["avg_ms"]},
             "loop_GBps_Amin": ((24 + 7 * 16) if scalar else A_MIN_BYTES_PER_VOXEL) * N * it_s / 1e9,
-            "kernels": kern, "kernel_sum_ms": kernel_table.last_sum_ms,
-            "kernel_sum_note": "rank 0's slab; sum of per-kernel HIP-event brackets (event-pair bias subtracted), exchanges excluded",
-            "replicas": replicas,
-            # the same problem on ONE GPU of this very node (rank 0's replica above): the line states its own speed-up
-            "single_gpu_it_s": replicas["rank0_single_gpu_it_s"] if replicas else None,
-            "speedup_over_single_gpu": it_s / replicas["rank0_single_gpu_it_s"] if replicas else None,
             "transport": d.transport, "rccl_ranks": world if d.transport == "rccl" else 0,
             "slab_split": split, "slab_split_trials": split_trials,
             "devices": devices, "distinct_devices": len({x.split(": ")[1] for x in devices}),
-            "alltoall_ms": xt["alltoall_fwd"] + xt["alltoall_bwd"], "exchange_ms_per_pass": xt,
             "alltoall_MB_per_gpu_per_pass": 2 * (1 if scalar else 3) * (world - 1) / world * (args.n // world) * args.n * (args.n // 2 + 1) * 16 / 1e6,
         })
+        if args.full:
+            local_n = (args.n // world, args.n, args.n)
+            kern, _, cnt = kernel_table(d, E, local_n, min(args.steps, 10), scalar, stokes)   # this rank's slab, HIP events
+            xt = exchange_times(d, cnt)
+            dom = max(kern, key=lambda k: kern[k]["avg_ms"])
+            line.update({
+                "roofline": {"kernel": dom + " (rank 0's slab)", "bound": "hbm", "achieved": kern[dom]["GBps"], "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": kern[dom]["GBps"] / HBM_PEAK_GBS, "traffic": None,
+                             "alg_bytes_per_launch": int(kern[dom]["alg_GB"] * 1e9), "avg_launch_ms": kern[dom]["avg_ms"]},
+                "kernels": kern, "kernel_sum_ms": kernel_table.last_sum_ms,
+                "kernel_sum_note": "rank 0's slab; sum of per-kernel HIP-event brackets (event-pair bias subtracted), exchanges excluded",
+                "replicas": replicas,
+                # the same problem on ONE GPU of this very node (rank 0's replica above): the line states its own speed-up
+                "single_gpu_it_s": replicas["rank0_single_gpu_it_s"] if replicas else None,
+                "speedup_over_single_gpu": it_s / replicas["rank0_single_gpu_it_s"] if replicas else None,
+                "alltoall_ms": xt["alltoall_fwd"] + xt["alltoall_bwd"], "exchange_ms_per_pass": xt,
+            })
         line["config"]["parallelism"] = ("x-slabs x%d: ONE problem, displacement loop per slab, per component one RCCL all-to-all "
                                          "each way between the FFT axes, +-1 halo planes of u, norms all-reduced" % world)
         if dry:
@@ -967,9 +1068,11 @@ def main():
             med_cg = 1.0 / max_over_ranks(1.0 / med_cg)
             line.update({"metric": metric.replace("LS iterations/sec (basic scheme", "CG iterations/sec (runCGElasticity"),
                          "basic_scheme_it_s": it_s, "value": med_cg, "ms_per_step": 1e3 / med_cg})
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, d, n, gather=gather_to_rank0, rank=rank)
         d.close()
         timer.cancel()
-        if args.also_slab and not scalar and not stokes:
+        if args.full and args.also_slab and not scalar and not stokes:
             # the other BASELINE grids (128^3; 512^3 laminate = the north-star target configuration) through the same driver, one
             # after the other; whatever happens here, the headline line stands
             line["also_slab"] = {}
@@ -1020,7 +1123,7 @@ def main():
         torch.cuda.synchronize(local_rank)
     except Exception:  # noqa: BLE001
         pass
-    if rank == 0 and not args.no_cpu_baseline and not scalar and not stokes:
+    if rank == 0 and args.full and not args.no_cpu_baseline and not scalar and not stokes:
         # north_star's table for N > 1: the CPU path timed in this same run (rank 0, every solver closed; the other ranks wait
         # at the barrier below) and it/s per grid beside it
         try:

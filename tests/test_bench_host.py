@@ -50,3 +50,14 @@ def test_cpu_loop_child_run(tmp_path):
         assert p.returncode == 0, p.stderr[-2000:]
         out[loops] = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
         assert out[loops]["fft"] == "own" and out[loops]["loops"] == loops and out[loops]["passes"] == 2 and out[loops]["it_s"] > 0
+
+
+def test_dump_sample_is_fixed():
+    """--dump-outputs: small grids are written whole, larger ones as the same sorted, distinct, in-range voxel sample in every
+    run (two builds compare output for output)."""
+    assert bench.dump_sample_index((64, 64, 64)) is None
+    a, b = bench.dump_sample_index((256, 256, 256)), bench.dump_sample_index((256, 256, 256))
+    assert np.array_equal(a, b) and a.size == bench.DUMP_SAMPLE
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 256 ** 3
+    # the 64 MB ceiling of a dump: two six-component float64 fields and two means
+    assert 2 * 6 * 8 * bench.DUMP_SAMPLE + 2 * 6 * 8 < 64e6

@@ -293,15 +293,15 @@ def test_porous_mode_on_slabs_one_rank_per_process(tmp_path, transport, nproc, g
 
 @pytest.mark.parametrize("backend,launcher", [("nccl-one-gpu", "self"), ("gloo", "self"), ("nccl-one-gpu", "torchrun")])
 def test_bench_line_for_two_ranks(backend, launcher):
-    """`bench.py --gpus 2` (what the driver starts per N -- self-launched and under torch.distributed.run, both ranks on the one GPU of the box): the slab
+    """`bench.py --full --gpus 2` (what the driver starts per N -- self-launched and under torch.distributed.run, both ranks on the one GPU of the box): the slab
     section runs, the line carries the fields the contract and north_star's table ask for -- value over ALL ranks,
     the same node's single-GPU rate, the kernels of rank 0's slab, the exchange times, the other grid through the same driver."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", backend, "--size", "128", "--steps", "4",
-           "--warmup", "2", "--repeats", "3", "--no-cpu-baseline", "--also-slab", "64:laminate", "--slab-timeout", "120"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--dist-backend", backend, "--size", "128",
+           "--steps", "4", "--warmup", "2", "--repeats", "3", "--no-cpu-baseline", "--also-slab", "64:laminate", "--slab-timeout", "120"]
     if launcher == "torchrun":   # the driver's command line for N > 1
         import socket
         with socket.socket() as sk:

@@ -135,7 +135,8 @@ def test_runs_are_reproducible_bit_for_bit():
 
 
 def test_bench_line_of_the_default_command_on_a_small_grid():
-    """`python bench.py` (the driver's N = 1 command) on 64^3 with short budgets: the one JSON line keeps the contract's keys --
+    """`python bench.py --full` (the driver's N = 1 command with every leg) on 64^3 with short budgets: the one JSON line keeps the
+    contract's keys --
     metric / value / unit / steps / warmup / ms_per_step, `roofline` with the traffic measured in the run by the two counter
     passes, `cpu_baseline` from the C loop nests on this host, the per-kernel table, one `also` leg."""
     import json
@@ -143,8 +144,8 @@ def test_bench_line_of_the_default_command_on_a_small_grid():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--size", "64", "--steps", "6", "--warmup", "2", "--repeats", "3",
-           "--sustain-s", "0.3", "--cpu-budget", "3", "--also", "32:laminate"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--size", "64", "--steps", "6", "--warmup", "2", "--repeats",
+           "3", "--sustain-s", "0.3", "--cpu-budget", "3", "--also", "32:laminate"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -170,6 +171,38 @@ def test_bench_line_of_the_default_command_on_a_small_grid():
     assert line["gamma0_apply_standalone"]["cache_assisted"] is True
     pc = line["pcie_inclusive"]
     assert pc["upload_ms"] > 0 and pc["download_ms"] > 0 and pc["it_s_inclusive"] > 0
+
+
+def test_plain_bench_run_and_its_outputs(tmp_path):
+    """`python bench.py` without --full: the headline only -- ONE region of exactly --steps timed steps, none of the --full
+    legs -- and --dump-outputs writes what the timed path computed: the strain and stress fields (64^3 = 2^18 voxels: all of
+    them) and their means, float64, consistent with each other."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--size", "64", "--steps", "7", "--warmup", "2",
+           "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert key in line, key
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["repeats"] == 1 and line["unit"] == "it/s" and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True and abs(line["ms_per_step"] * line["value"] - 1e3) < 1e-3
+    assert "fg_iterate" in line["metric"] and line["config"]["grid"] == [64, 64, 64]
+    for key in ("kernels", "roofline", "cpu_baseline", "also", "sustained_it_s", "cg_method", "slab_forced"):
+        assert key not in line, key
+    d = {name: np.load(tmp_path / "out" / (name + ".npy")) for name in ("epsilon", "sigma", "mean_stress", "mean_strain")}
+    assert d["epsilon"].shape == d["sigma"].shape == (6, 64 ** 3) and d["mean_stress"].shape == d["mean_strain"].shape == (6,)
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in d.values())
+    assert np.abs(d["epsilon"].mean(axis=1) - d["mean_strain"]).max() < 1e-10
+    assert np.abs(d["sigma"].mean(axis=1) - d["mean_stress"]).max() < 1e-9 * np.abs(d["mean_stress"]).max()
+    assert np.abs(d["epsilon"][0].mean() - 1.0) < 1e-10   # the prescribed mean strain E = e_xx
 
 
 def test_driver_smoke_entry(capsys):
