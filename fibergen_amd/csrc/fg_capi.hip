@@ -201,6 +201,13 @@ int fg_set_phase(fg_solver* s, int p, double mu, double lambda, const double* ph
   });
 }
 
+int fg_set_phase_field_fine(fg_solver* s, int p, const double* phi) {
+  return guarded(s, [&](fg::Solver& v) {
+    if (!phi) throw std::runtime_error("phi pointer is NULL");
+    v.set_phase_field_fine(p, phi);
+  });
+}
+
 int fg_set_normals(fg_solver* s, const double* normals) {
   return guarded(s, [&](fg::Solver& v) {
     if (!normals) throw std::runtime_error("normals pointer is NULL");
@@ -240,7 +247,9 @@ int fg_set_option_i(fg_solver* s, const char* key, long value) {
       v.invalidate_moduli();   // the precomputed effective moduli depend on the mode's phase table
     }
     else if (k == "gamma_scheme") {
-      if (value != 0 && value != 1) throw std::runtime_error("gamma_scheme must be 0 (staggered) or 1 (collocated)");
+      if (value < 0 || value > 2)
+        throw std::runtime_error("gamma_scheme must be 0 (staggered), 1 (collocated) or 2 (full_staggered: doubly fine grid)");
+      if (value == 2 && v.is_slab()) throw std::runtime_error("full_staggered is not available on slab-decomposed solvers");
       o.gamma_scheme = (int)value;
     }
     else if (k == "u_tile") {

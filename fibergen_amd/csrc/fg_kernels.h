@@ -150,6 +150,35 @@ void launch_stress_div_sum_voigt(const Grid& g, const StressParams& sp, const Fi
 void launch_eps_delta_recompute(const Grid& g, const FieldPtrs<3>& u, const FieldPtrs<6>& eps_old, const StressParams& sp,
                                 const FieldPtrs<kMaxPhases>& phi, const double* tau_sum, double nvox, const Vec6& E,
                                 double coef, const FieldPtrs<6>& eps, double* partial, double* sumsq6, hipStream_t s);
+// ---- gamma_scheme full_staggered (doubly fine grid, fg_kernels_dfg.hip).  The literal chain of the reference -- strain
+// prolonged to the 2nx x 2ny x 2nz grid with a shift per component (prolongate_to_dfg F:14216-14270), Voigt PK1 per fine
+// cell, restriction with the opposite shift (restrict_from_dfg F:14273-14335) -- reads the same coarse strain values in
+// all 8 fine cells a restricted component averages, so it collapses to a point-wise coarse evaluation in which each
+// component group g (normal, 23, 13, 12) sees its own staggered phase fractions, the 8-cell means of the fine fractions
+// over the block shifted by the group's offset.  mod = {A_n, B_n, A_23, A_13, A_12}: A_g = sum_p phi_p^(g) 2 mu_p,
+// B_n = sum_p phi_p^(n) lambda_p.
+// fine: one phase's image [2nx][2ny][2nz] on the device -> phi^(n) (the coarse field, padded layout) and phi^(23, 13, 12)
+void launch_dfg_fractions_fine(const Grid& g, const double* fine, double* phi_n, const FieldPtrs<3>& phi_s, hipStream_t s);
+// a coarse field replicated piecewise-constant onto the fine grid (half_staggered, raw data: initFullStageredRawPhases
+// F:17648-17710): phi^(23) = mean of the 4 cells (i, j-1..j, k-1..k), likewise 13 and 12
+void launch_dfg_fractions_replica(const Grid& g, const double* phi, const FieldPtrs<3>& phi_s, hipStream_t s);
+// phi: [nph][n] normal-group fractions, phis: [nph][3][n] shear-group fractions -> the five moduli
+void launch_dfg_moduli(const Grid& g, const PhaseTable& pt, const double* phi, const double* phis, const FieldPtrs<5>& mod,
+                       hipStream_t s);
+// calcStress / meanPK1 / meanW on the five moduli: mode 0 tau = P(eps) + beta eps + gamma tr(eps) I (beta = -alpha 2 mu_0,
+// gamma = -alpha lambda_0); mode 1 sums of P into out6; mode 2 sum of 1/2 P:eps into out6[0]
+void launch_dfg_stress(int mode, const Grid& g, const StressParams& sp, const FieldPtrs<6>& eps, const FieldPtrs<5>& mod,
+                       const FieldPtrs<6>& tau, double* partial, double* out6, hipStream_t s);
+void launch_eps_delta_recompute(const Grid& g, const FieldPtrs<3>& u, const FieldPtrs<6>& eps_old, const StressParams& sp,
+                                const FieldPtrs<5>& mod, const double* tau_sum, double nvox, const Vec6& E, double coef,
+                                const FieldPtrs<6>& eps, double* partial, double* sumsq6, hipStream_t s);
+void launch_eps_tile(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<6>& eps, const FieldPtrs<5>& mod,
+                     const FieldPtrs<3>& f, double* partial, double* sum6, hipStream_t s);
+void launch_u_tile(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& u, const FieldPtrs<5>& mod,
+                   const FieldPtrs<3>& f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s, bool sum_tau);
+void launch_u_tile_cg(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& p_old, const FieldPtrs<3>& r,
+                      const FieldPtrs<3>& p_new, const FieldPtrs<5>& mod, const FieldPtrs<3>& f, const Vec6& E, const double* sc,
+                      int i_num, int i_den, double nvox, double small, double* partial, double* sumsq6, hipStream_t s);
 void launch_eps_delta(const Grid& g, const FieldPtrs<3>& u, const FieldPtrs<6>& tau, const double* tau_sum, double nvox,
                       const Vec6& E, double coef, const FieldPtrs<6>& eps, double* partial, double* sumsq6, hipStream_t s);
 void launch_copy(const double* src, double* dst, long ndoubles, hipStream_t s);

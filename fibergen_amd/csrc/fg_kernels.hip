@@ -1108,6 +1108,8 @@ __global__ void k_add_small(double* out, const double* in, int n) {
 // squares of eta.  Same operation order as k_eps_norm followed by xpay.
 // NPH > 0: no stored tau; `tau` holds the strain the pass started from and the polarisation is re-evaluated from it
 // (a point-wise function of that strain: same arithmetic as k_stress, so the same values).
+// NPH < 0: gamma_scheme full_staggered, phi.p[0..4] are the five moduli A_n, B_n, A_23, A_13, A_12 of the doubly fine grid
+// (fg_kernels_dfg.hip) and the polarisation is (alpha A_g + beta) eps_c (+ (alpha B_n + gamma) tr eps for the normal components).
 template <int NPH>
 __global__ __launch_bounds__(kBlock) void k_eps_delta(Grid g, FieldPtrs<3> u, FieldPtrs<6> tau, const double* tau_sum,
                                                       double nvox, Vec6 E, double coef, FieldPtrs<6> eps, double* partial,
@@ -1176,6 +1178,26 @@ __global__ __launch_bounds__(kBlock) void k_eps_delta(Grid g, FieldPtrs<3> u, Fi
       for (int c = 0; c < 3; ++c) tt[c].y = voigt_tau_normal<NPH>(o[c].y, o[0].y, o[1].y, o[2].y, ph, sp);
 #pragma unroll
       for (int c = 3; c < 6; ++c) tt[c].y = voigt_tau_shear<NPH>(o[c].y, ph, sp);
+    } else if constexpr (NPH < 0) {
+      const double beta = -sp.alpha * 2 * sp.mu_0, gamma = -sp.alpha * sp.lambda_0;
+      double2 m[5];
+#pragma unroll
+      for (int q = 0; q < 5; ++q) m[q] = ld2(phi.p[q], p.off);
+      double2 o[6];
+#pragma unroll
+      for (int c = 0; c < 6; ++c) o[c] = tt[c];
+      const double trx = o[0].x + o[1].x + o[2].x, try_ = o[0].y + o[1].y + o[2].y;
+      const double bx = sp.alpha * m[1].x + gamma, by = sp.alpha * m[1].y + gamma;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        tt[c].x = o[c].x * (sp.alpha * m[0].x + beta) + bx * trx;
+        tt[c].y = o[c].y * (sp.alpha * m[0].y + beta) + by * try_;
+      }
+#pragma unroll
+      for (int c = 3; c < 6; ++c) {
+        tt[c].x = o[c].x * (sp.alpha * m[c - 1].x + beta);
+        tt[c].y = o[c].y * (sp.alpha * m[c - 1].y + beta);
+      }
     }
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
@@ -1743,6 +1765,19 @@ void launch_eps_delta_recompute(const Grid& g, const FieldPtrs<3>& u, const Fiel
   else
     hipLaunchKernelGGL(k_eps_delta<kMaxPhases>, dim3(nb), dim3(kBlock), 0, s, g, u, eps_old, tau_sum, nvox, E, coef, eps,
                        partial, sp, phi, chunk_rows(g));
+  FG_HIP_CHECK(hipGetLastError());
+  fold_sum(partial, nb, 6, sumsq6, s);
+  FG_HIP_CHECK(hipGetLastError());
+}
+
+void launch_eps_delta_recompute(const Grid& g, const FieldPtrs<3>& u, const FieldPtrs<6>& eps_old, const StressParams& sp,
+                                const FieldPtrs<5>& mod, const double* tau_sum, double nvox, const Vec6& E, double coef,
+                                const FieldPtrs<6>& eps, double* partial, double* sumsq6, hipStream_t s) {
+  const int nb = sweep_blocks((long)g.nx * g.ny * g.nzc);
+  FieldPtrs<kMaxPhases> m = {};
+  for (int q = 0; q < 5; ++q) m.p[q] = mod.p[q];
+  hipLaunchKernelGGL(k_eps_delta<-1>, dim3(nb), dim3(kBlock), 0, s, g, u, eps_old, tau_sum, nvox, E, coef, eps, partial, sp, m,
+                     chunk_rows(g));
   FG_HIP_CHECK(hipGetLastError());
   fold_sum(partial, nb, 6, sumsq6, s);
   FG_HIP_CHECK(hipGetLastError());

@@ -218,9 +218,12 @@ struct CgDirection {
   double nvox, small;
 };
 
-template <int TYR, int ZS, bool SUMT, bool PHI2, bool CGP = false>
+// NMOD = 5: gamma_scheme full_staggered (doubly fine grid): mod = {A_n, B_n, A_23, A_13, A_12}, the moduli of the normal
+// components and of each shear component from its own staggered phase fractions (see fg_kernels_dfg.hip); 3 more 16-byte
+// loads per plane.  NMOD = 2 is the staggered sweep, unchanged.
+template <int TYR, int ZS, bool SUMT, bool PHI2, bool CGP = false, int NMOD = 2>
 __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, double beta, double gamma, FieldPtrs<3> u,
-                                                                      FieldPtrs<2> mod, FieldPtrs<3> fo, Vec6 E, double* partial,
+                                                                      FieldPtrs<NMOD> mod, FieldPtrs<3> fo, Vec6 E, double* partial,
                                                                       int nty, int ntz, int LX, int nt, PhaseLin lin,
                                                                       CgDirection cg) {
   constexpr bool FULLROW = ZS > 0;
@@ -326,6 +329,11 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, dou
     const double2 Ac = ld2(mod.p[0], oq);
     double2 Bc = Ac;
     if (!PHI2) Bc = ld2(mod.p[1], oq);
+    [[maybe_unused]] double2 Sc[3];
+    if constexpr (NMOD == 5) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) Sc[c] = ld2(mod.p[2 + c], oq);
+    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) u2[c] = load_u(c, o2, st + 2 >= 0 && st + 2 < nsteps);
     // ---- y neighbours of u through LDS
@@ -365,9 +373,15 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, dou
     t0.x = e0.x * ax + bx * trx; t0.y = e0.y * ay + by * try_;
     t1.x = e1.x * ax + bx * trx; t1.y = e1.y * ay + by * try_;
     t2.x = e2.x * ax + bx * trx; t2.y = e2.y * ay + by * try_;
-    t3.x = e3.x * ax; t3.y = e3.y * ay;
-    t4.x = e4.x * ax; t4.y = e4.y * ay;
-    t5.x = e5.x * ax; t5.y = e5.y * ay;
+    if constexpr (NMOD == 5) {
+      t3.x = e3.x * (Sc[0].x + beta); t3.y = e3.y * (Sc[0].y + beta);
+      t4.x = e4.x * (Sc[1].x + beta); t4.y = e4.y * (Sc[1].y + beta);
+      t5.x = e5.x * (Sc[2].x + beta); t5.y = e5.y * (Sc[2].y + beta);
+    } else {
+      t3.x = e3.x * ax; t3.y = e3.y * ay;
+      t4.x = e4.x * ax; t4.y = e4.y * ay;
+      t5.x = e5.x * ax; t5.y = e5.y * ay;
+    }
     const bool inside = st >= 0 && st < nsteps;
     if (own && inside) {
       acc[0] += e0.x * e0.x + e0.y * e0.y; acc[1] += e1.x * e1.x + e1.y * e1.y; acc[2] += e2.x * e2.x + e2.y * e2.y;
@@ -649,9 +663,10 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_cgu_tile(Grid g, F
 // conditions): eps -> f = div((C - C0) : eps) and the six sums of the polarisation, Voigt mixing with the precomputed
 // effective moduli.  Same tiling (rows = waves, lanes = z pairs, march along x, y neighbours of tau through LDS -- two
 // images, one barrier per plane --, z neighbours by DPP); the strain of the next plane is requested one step ahead.
-template <int TYR, int ZS>
+// NMOD = 5: the doubly fine grid's five moduli (see k_u_tile)
+template <int TYR, int ZS, int NMOD = 2>
 __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_eps_tile(Grid g, double beta, double gamma, FieldPtrs<6> eps,
-                                                                        FieldPtrs<2> mod, FieldPtrs<3> fo, double* partial,
+                                                                        FieldPtrs<NMOD> mod, FieldPtrs<3> fo, double* partial,
                                                                         int nty, int ntz, int LX, int nt) {
   constexpr bool FULLROW = ZS > 0;
   constexpr int NZS = ZS ? ZS : 1;
@@ -708,12 +723,17 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_eps_tile(Grid g, d
   auto next_x = [&](double v) { return dpp_move<0x130>(v); };
 
   double2 en[6], An, Bn;   // inputs of the coming step
+  [[maybe_unused]] double2 Sn[3];
   {
     const long o = plane(x0 - 1);
 #pragma unroll
     for (int c = 0; c < 6; ++c) en[c] = ld2(eps.p[c], o);
     An = ld2(mod.p[0], o);
     Bn = ld2(mod.p[1], o);
+    if constexpr (NMOD == 5) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) Sn[c] = ld2(mod.p[2 + c], o);
+    }
   }
   double2 zero = make_double2(0.0, 0.0);
   double2 t0m = zero, t5m = zero, t4m = zero, part1 = zero, part2 = zero;
@@ -724,12 +744,21 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_eps_tile(Grid g, d
     const long oq = plane(q);
     double2 e0 = en[0], e1 = en[1], e2 = en[2], e3 = en[3], e4 = en[4], e5 = en[5];
     const double2 Ac = An, Bc = Bn;
+    [[maybe_unused]] double2 Sc[3];
+    if constexpr (NMOD == 5) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) Sc[c] = Sn[c];
+    }
     if (st < nsteps) {
       const long on = plane(q + 1);
 #pragma unroll
       for (int c = 0; c < 6; ++c) en[c] = ld2(eps.p[c], on);
       An = ld2(mod.p[0], on);
       Bn = ld2(mod.p[1], on);
+      if constexpr (NMOD == 5) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Sn[c] = ld2(mod.p[2 + c], on);
+      }
     }
     // ---- polarisation  tau = (A - 2 mu0) eps + (B - lambda0) tr(eps) I
     const double ax = Ac.x + beta, ay = Ac.y + beta, bx = Bc.x + gamma, by = Bc.y + gamma;
@@ -738,9 +767,15 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_eps_tile(Grid g, d
     t0.x = e0.x * ax + bx * trx; t0.y = e0.y * ay + by * try_;
     t1.x = e1.x * ax + bx * trx; t1.y = e1.y * ay + by * try_;
     t2.x = e2.x * ax + bx * trx; t2.y = e2.y * ay + by * try_;
-    t3.x = e3.x * ax; t3.y = e3.y * ay;
-    t4.x = e4.x * ax; t4.y = e4.y * ay;
-    t5.x = e5.x * ax; t5.y = e5.y * ay;
+    if constexpr (NMOD == 5) {
+      t3.x = e3.x * (Sc[0].x + beta); t3.y = e3.y * (Sc[0].y + beta);
+      t4.x = e4.x * (Sc[1].x + beta); t4.y = e4.y * (Sc[1].y + beta);
+      t5.x = e5.x * (Sc[2].x + beta); t5.y = e5.y * (Sc[2].y + beta);
+    } else {
+      t3.x = e3.x * ax; t3.y = e3.y * ay;
+      t4.x = e4.x * ax; t4.y = e4.y * ay;
+      t5.x = e5.x * ax; t5.y = e5.y * ay;
+    }
     const bool inside = st >= 0 && st < nsteps;
     if (own && inside) {
       acc[0] += t0.x + t0.y; acc[1] += t1.x + t1.y; acc[2] += t2.x + t2.y;
@@ -949,8 +984,8 @@ inline int march_length(int nx, long tiles, int cus) {
   return best;
 }
 
-template <int TYR, int ZS, bool SUMT, bool PHI2 = false, bool CGP = false>
-void launch_u_tile_t(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& u, const FieldPtrs<2>& mod,
+template <int TYR, int ZS, bool SUMT, bool PHI2 = false, bool CGP = false, int NMOD = 2>
+void launch_u_tile_t(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& u, const FieldPtrs<NMOD>& mod,
                      const FieldPtrs<3>& f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s,
                      const PhaseLin& lin = PhaseLin{0, 0, 0, 0}, const CgDirection& cg = CgDirection{}) {
   constexpr int NZS = ZS ? ZS : 1;
@@ -966,11 +1001,11 @@ void launch_u_tile_t(const Grid& g, double mu_0, double lambda_0, const FieldPtr
   const size_t lds = 6 * TYR * NZS * 64 * sizeof(double2);
   static PerDeviceOnce configured;
   if (auto once = configured.first_use()) {
-    FG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_u_tile<TYR, ZS, SUMT, PHI2, CGP>),
+    FG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_u_tile<TYR, ZS, SUMT, PHI2, CGP, NMOD>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
   const int nt = 3.0 * (double)g.n * sizeof(double) > 256.0 * 1024 * 1024 ? 1 : 0;
-  hipLaunchKernelGGL((k_u_tile<TYR, ZS, SUMT, PHI2, CGP>), dim3(nb), dim3(TYR * NZS * 64), lds, s, g, -2 * mu_0, -lambda_0, u, mod, f,
+  hipLaunchKernelGGL((k_u_tile<TYR, ZS, SUMT, PHI2, CGP, NMOD>), dim3(nb), dim3(TYR * NZS * 64), lds, s, g, -2 * mu_0, -lambda_0, u, mod, f,
                      E, partial, nty, ntz, LX, nt, lin, cg);
   FG_HIP_CHECK(hipGetLastError());
   fold_sum(partial, nb, SUMT ? 12 : 6, sumsq6, s);
@@ -1039,6 +1074,38 @@ void launch_u_tile_cg(const Grid& g, double mu_0, double lambda_0, const FieldPt
   else if (nzh == 128) FG_CGK(6, 2);
   else FG_CGK(8, 0);
 #undef FG_CGK
+}
+
+// gamma_scheme full_staggered: the same sweeps on the five moduli of the doubly fine grid (default tile shapes)
+void launch_u_tile(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& u, const FieldPtrs<5>& mod,
+                   const FieldPtrs<3>& f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s, bool sum_tau) {
+  const int nzh = g.nz / 2;
+#define FG_DFG(R, Z)                                                                                                    \
+  do {                                                                                                                  \
+    if (sum_tau) launch_u_tile_t<R, Z, true, false, false, 5>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s);    \
+    else launch_u_tile_t<R, Z, false, false, false, 5>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s);           \
+  } while (0)
+  if (nzh == 64) FG_DFG(8, 1);
+  else if (nzh == 128) FG_DFG(6, 2);
+  else FG_DFG(8, 0);
+#undef FG_DFG
+}
+
+void launch_u_tile_cg(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& p_old, const FieldPtrs<3>& r,
+                      const FieldPtrs<3>& p_new, const FieldPtrs<5>& mod, const FieldPtrs<3>& f, const Vec6& E, const double* sc,
+                      int i_num, int i_den, double nvox, double small, double* partial, double* sumsq6, hipStream_t s) {
+  CgDirection cg;
+  for (int c = 0; c < 3; ++c) cg.r[c] = r.p[c], cg.po[c] = p_new.p[c];
+  cg.sc = sc;
+  cg.i_num = i_num;
+  cg.i_den = i_den;
+  cg.nvox = nvox;
+  cg.small = small;
+  const int nzh = g.nz / 2;
+  const PhaseLin lin = {0, 0, 0, 0};
+  if (nzh == 64) launch_u_tile_t<8, 1, false, false, true, 5>(g, mu_0, lambda_0, p_old, mod, f, E, partial, sumsq6, s, lin, cg);
+  else if (nzh == 128) launch_u_tile_t<6, 2, false, false, true, 5>(g, mu_0, lambda_0, p_old, mod, f, E, partial, sumsq6, s, lin, cg);
+  else launch_u_tile_t<8, 0, false, false, true, 5>(g, mu_0, lambda_0, p_old, mod, f, E, partial, sumsq6, s, lin, cg);
 }
 
 // *flag := 0 unless phi0 == 1 - phi1 bit for bit at every voxel (what normalizePhi F:17613-17626 produces for two phases);
@@ -1459,8 +1526,8 @@ bool launch_sc_sweep_fast(const Grid& g, double mu_0, const double* T, const dou
   return false;   // the untiled sweep carries no sums of tau
 }
 
-template <int TYR, int ZS>
-void launch_eps_tile_t(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<6>& eps, const FieldPtrs<2>& mod,
+template <int TYR, int ZS, int NMOD = 2>
+void launch_eps_tile_t(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<6>& eps, const FieldPtrs<NMOD>& mod,
                        const FieldPtrs<3>& f, double* partial, double* sum6, hipStream_t s) {
   constexpr int NZS = ZS ? ZS : 1;
   constexpr int TYU = TYR - 2, TZU = ZS ? 64 * ZS : 62;
@@ -1476,11 +1543,11 @@ void launch_eps_tile_t(const Grid& g, double mu_0, double lambda_0, const FieldP
   const size_t lds = 6 * TYR * NZS * 64 * sizeof(double2);
   static PerDeviceOnce configured;
   if (auto once = configured.first_use()) {
-    FG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_eps_tile<TYR, ZS>),
+    FG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_eps_tile<TYR, ZS, NMOD>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
   const int nt = 3.0 * (double)g.n * sizeof(double) > 256.0 * 1024 * 1024 ? 1 : 0;
-  hipLaunchKernelGGL((k_eps_tile<TYR, ZS>), dim3(nb), dim3(TYR * NZS * 64), lds, s, g, -2 * mu_0, -lambda_0, eps, mod, f,
+  hipLaunchKernelGGL((k_eps_tile<TYR, ZS, NMOD>), dim3(nb), dim3(TYR * NZS * 64), lds, s, g, -2 * mu_0, -lambda_0, eps, mod, f,
                      partial, nty, ntz, LX, nt);
   FG_HIP_CHECK(hipGetLastError());
   fold_sum(partial, nb, 6, sum6, s);
@@ -1493,6 +1560,14 @@ void launch_eps_tile(const Grid& g, double mu_0, double lambda_0, const FieldPtr
   if (nzh == 64) launch_eps_tile_t<8, 1>(g, mu_0, lambda_0, eps, mod, f, partial, sum6, s);
   else if (nzh == 128) launch_eps_tile_t<6, 2>(g, mu_0, lambda_0, eps, mod, f, partial, sum6, s);
   else launch_eps_tile_t<8, 0>(g, mu_0, lambda_0, eps, mod, f, partial, sum6, s);
+}
+
+void launch_eps_tile(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<6>& eps, const FieldPtrs<5>& mod,
+                     const FieldPtrs<3>& f, double* partial, double* sum6, hipStream_t s) {
+  const int nzh = g.nz / 2;
+  if (nzh == 64) launch_eps_tile_t<8, 1, 5>(g, mu_0, lambda_0, eps, mod, f, partial, sum6, s);
+  else if (nzh == 128) launch_eps_tile_t<6, 2, 5>(g, mu_0, lambda_0, eps, mod, f, partial, sum6, s);
+  else launch_eps_tile_t<8, 0, 5>(g, mu_0, lambda_0, eps, mod, f, partial, sum6, s);
 }
 
 template <int TYR, int ZS, int MODE>

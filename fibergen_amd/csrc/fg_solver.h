@@ -58,7 +58,9 @@ struct SolverOptions {
   double eps_a = 3.666852862501036e-11;          // eps^(2/3)
   int mode = 0;                 // 0 = elasticity, 1 = scalar (heat / porous: 3-component gradient, 1-component potential),
                                 // 2 = viscosity (dual Stokes scheme: DeltaOperatorStaggered F:20422-20460, 6 components)
-  int gamma_scheme = 0;         // 0 = staggered (GammaOperatorStaggered F:20288), 1 = collocated (GammaOperatorCollocated F:20302)
+  int gamma_scheme = 0;         // 0 = staggered (GammaOperatorStaggered F:20288), 1 = collocated (GammaOperatorCollocated F:20302),
+                                // 2 = full_staggered / half_staggered: the staggered operator with the material evaluated on
+                                // the doubly fine grid (use_dfg F:14894-14897), in coarse form (fg_kernels.h)
   int loadstep_extrapolation_order = 0;   // 0 = none, 1 = linear, ... (F:14696; method "polynomial" F:21468-21514)
   int slab_interleave = -1;     // -1: where available; 0: one message per peer and component
   int error_estimator = 0;      // 0 = epsilon (EpsilonErrorEstimator F:14591-14637), 1 = residual (ResidualErrorEstimator
@@ -156,7 +158,7 @@ class Solver {
 
   const Grid& grid() const { return g_; }
   SolverOptions& options() { return opt_; }
-  void invalidate_moduli() { mod_dirty_ = smod_dirty_ = complement_dirty_ = true; }
+  void invalidate_moduli() { mod_dirty_ = mod5_dirty_ = smod_dirty_ = complement_dirty_ = true; }
   void invalidate_interface_lists() { mixed_dirty_ = true; }   // which lists exist depends on u_tile
   void reference_material_changed() { recompute_bc(); }   // (mu_0, lambda_0) set from outside: M, MQ depend on C0
   hipStream_t stream() const { return stream_; }
@@ -166,6 +168,9 @@ class Solver {
   int num_phases() const { return pt_.n; }
   void set_phase_material(int p, double mu, double lambda);
   void set_phase_field(int p, const double* phi_host);  // [nx][ny][nz], copied
+  // gamma_scheme 2: phase p's image on the doubly fine grid [2nx][2ny][2nz] (initPhi under select_dfg F:17152-17230), reduced on
+  // the device to its coarse field and its three shear-group fractions; the image is not kept
+  void set_phase_field_fine(int p, const double* fine_host);
   void set_normals(const double* n_host);                // [3][nx][ny][nz]
   void set_bc_projector(const double* P36);              // row-major 6x6
   void set_callback(ConvergenceCallback cb, void* user) { cb_ = cb; cb_user_ = user; }
@@ -242,6 +247,11 @@ class Solver {
   bool u_loop_eligible(bool allow_mixed_bc = false) const;
   bool two_phase_complementary();       // phi_0 == 1 - phi_1 everywhere (checked once per geometry)
   FieldPtrs<2> effective_moduli();      // per-voxel sums of the phase moduli for the fast kernels (allocated on first use)
+  bool dfg() const { return opt_.gamma_scheme == 2; }
+  void dfg_check() const;               // throws for the combinations full_staggered does not cover
+  FieldPtrs<5> dfg_moduli();            // gamma_scheme 2: A_n, B_n, A_23, A_13, A_12 (once per geometry)
+  // calcStress into tau_: the phase fractions, or under gamma_scheme 2 the five moduli
+  void stress_to_tau(const StressParams& sp, double* src, const FieldPtrs<kMaxPhases>& phi, const FieldPtrs<3>& nrm);
   void build_laminate_lists();          // interface / affected voxel lists of the laminate correction (once per geometry)
   void u_pass_front(const double* E6);  // u_k (fu_) -> sums of squares of eps_k, f_{k+1} (fu_alt_)
   void u_pass_back();                   // f_{k+1} -> u_{k+1}, buffers swapped
@@ -367,6 +377,10 @@ class Solver {
   double *lam_phic_ = nullptr, *lam_nrmc_ = nullptr, *lam_epsc_ = nullptr;
   double* mod_ = nullptr;      // 2: per-voxel effective moduli (sum phi 2 mu, sum phi lambda) of the fast sweep
   bool mod_dirty_ = true;
+  double* phis_ = nullptr;     // gamma_scheme 2: [nphase][3] shear-group fractions phi^(23), phi^(13), phi^(12)
+  unsigned fine_set_ = 0;      // phases whose phis_ came from a fine image (the others are built from phi_ as replicas)
+  double* mod5_ = nullptr;     // gamma_scheme 2: the five moduli
+  bool mod5_dirty_ = true;
   bool complement_dirty_ = true, complementary_ = false;
   double* fu_alt_ = nullptr;   // 3: second f/u buffer of the displacement-based loop (swapped with fu_)
   double* phi_ = nullptr;      // nphase

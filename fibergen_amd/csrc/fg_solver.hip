@@ -194,7 +194,7 @@ void Solver::release() {
   if (aff_list_) (void)hipFree(aff_list_);
   if (aff_slots_) (void)hipFree(aff_slots_);
   if (dtau_) (void)hipFree(dtau_);
-  double* bufs[] = {eps_, tau_, fu_, fu_alt_, phi_, normals_, partial_, dscal_, cg_r_, cg_p_, cg_w_, mod_, fu_cg_};
+  double* bufs[] = {eps_, tau_, fu_, fu_alt_, phi_, normals_, partial_, dscal_, cg_r_, cg_p_, cg_w_, mod_, fu_cg_, phis_, mod5_};
   for (double* b : bufs)
     if (b) (void)hipFree(b);
   if (hscal_) (void)hipHostFree(hscal_);
@@ -236,17 +236,20 @@ void Solver::set_num_phases(int n) {
   phi_ = nullptr;
   FG_HIP_CHECK(hipMalloc(&phi_, (size_t)n * g_.n * sizeof(double)));
   FG_HIP_CHECK(hipMemsetAsync(phi_, 0, (size_t)n * g_.n * sizeof(double), stream_));
+  if (phis_) FG_HIP_CHECK(hipFree(phis_));
+  phis_ = nullptr;
+  fine_set_ = 0;
   pt_.n = n;
-  mod_dirty_ = true;
-  smod_dirty_ = true;
+  mod_dirty_ = mod5_dirty_ = true;
+  smod_dirty_ = mod5_dirty_ = true;
   complement_dirty_ = true;
   mixed_dirty_ = true;
 }
 
 void Solver::set_phase_material(int p, double mu, double lambda) {
   if (p < 0 || p >= pt_.n) throw std::runtime_error("phase index out of range");
-  mod_dirty_ = true;
-  smod_dirty_ = true;
+  mod_dirty_ = mod5_dirty_ = true;
+  smod_dirty_ = mod5_dirty_ = true;
   complement_dirty_ = true;
   mixed_dirty_ = true;
   pt_.mu[p] = mu;
@@ -255,11 +258,35 @@ void Solver::set_phase_material(int p, double mu, double lambda) {
 
 void Solver::set_phase_field(int p, const double* phi_host) {
   if (p < 0 || p >= pt_.n) throw std::runtime_error("phase index out of range");
-  mod_dirty_ = true;
-  smod_dirty_ = true;
+  mod_dirty_ = mod5_dirty_ = true;
+  smod_dirty_ = mod5_dirty_ = true;
   complement_dirty_ = true;
   mixed_dirty_ = true;
+  fine_set_ &= ~(1u << p);
   upload_padded(phi_ + (long)p * g_.n, phi_host);
+}
+
+void Solver::set_phase_field_fine(int p, const double* fine_host) {
+  if (p < 0 || p >= pt_.n) throw std::runtime_error("phase index out of range");
+  if (!dfg()) throw std::runtime_error("a phase field on the doubly fine grid needs gamma_scheme full_staggered (2)");
+  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("full_staggered is not available on slab-decomposed solvers");
+  FG_HIP_CHECK(hipSetDevice(device_));
+  const size_t nfine = 8 * (size_t)g_.nxyz;
+  if (!phis_) {
+    FG_HIP_CHECK(hipMalloc(&phis_, 3 * (size_t)pt_.n * g_.n * sizeof(double)));
+    FG_HIP_CHECK(hipMemsetAsync(phis_, 0, 3 * (size_t)pt_.n * g_.n * sizeof(double), stream_));
+  }
+  double* fine = nullptr;
+  FG_HIP_CHECK(hipMalloc(&fine, nfine * sizeof(double)));
+  FG_HIP_CHECK(hipMemcpyAsync(fine, fine_host, nfine * sizeof(double), hipMemcpyHostToDevice, stream_));
+  FieldPtrs<3> s;
+  for (int c = 0; c < 3; ++c) s.p[c] = phis_ + (3L * p + c) * g_.n;
+  launch_dfg_fractions_fine(g_, fine, phi_ + (long)p * g_.n, s, stream_);
+  FG_HIP_CHECK(hipStreamSynchronize(stream_));   // the caller's image may go once this returns; ours goes now
+  FG_HIP_CHECK(hipFree(fine));
+  mod_dirty_ = mod5_dirty_ = true;
+  smod_dirty_ = complement_dirty_ = mixed_dirty_ = true;
+  fine_set_ |= 1u << p;
 }
 
 void Solver::set_normals(const double* n_host) {
@@ -521,6 +548,7 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
   if (nranks_ != 1) throw std::runtime_error("basic_scheme: slab solvers run under the slab driver (fg_slab.hip)");
   if (pt_.n < 1) throw std::runtime_error("No materials specified");
   if (opt_.mixing == kMixLaminate && !normals_) throw std::runtime_error("laminate mixing needs interface normals");
+  if (dfg()) dfg_check();
   FieldPtrs<kMaxPhases> phi;
   for (int q = 0; q < kMaxPhases; ++q) phi.p[q] = q < pt_.n ? phi_ + (long)q * g_.n : nullptr;
   FieldPtrs<3> nrm;
@@ -539,17 +567,21 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
     // DeltaOperatorStaggered  F:20422-20460 (dual Stokes scheme), called with alpha = -1 by basicScheme:
     //   m = 1/(4 mu0);  adj = E - 2 alpha m <tau>;  eta = GammaStaggered(adj; mu = -1/(4 m), lambda = inf)(tau)
     //   + 2 alpha m tau.   lambda0 = inf makes c20 = c10 in G0OperatorFourierStaggered (F:19749-19755).
-    if (opt_.gamma_scheme != 0) throw std::runtime_error("viscosity mode supports gamma_scheme=staggered only");
+    if (opt_.gamma_scheme == 1) throw std::runtime_error("viscosity mode supports gamma_scheme staggered and full_staggered only");
     if (opt_.mixing != kMixVoigt) throw std::runtime_error("viscosity mode supports Voigt mixing only");
     if (opt_.bc_relax != 1.0) throw std::runtime_error("viscosity mode supports bc_relax = 1 only");
     const bool mixed_bc = !(frobenius(BC_MQ_) < kEps);   // initBCProjector / applyBCProjector inside GammaOperatorStaggered
     const double m = 1 / (4 * opt_.mu_0);
-    const bool fused = opt_.fuse_stress_div != 0;
+    // full_staggered: the fused form exists as the tiled sweep only (other grids store the polarisation)
+    const bool fused = opt_.fuse_stress_div != 0 && (!dfg() || (opt_.u_loop >= 2 && u_tile_supported(g_)));
     if (fused) {
       // the polarisation is a point-wise function of the strain: it is evaluated inside the divergence sweep (with its
       // six sums) and again in the tail sweep, and never stored
       time_begin(0);
-      if (opt_.u_loop >= 2 && u_tile_supported(g_))   // fast kernels allowed: the LDS-tiled marching form
+      if (dfg())
+        launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), dfg_moduli(), ptrs3(fu_), partial_, dscal_ + kSlotMean,
+                        stream_);
+      else if (opt_.u_loop >= 2 && u_tile_supported(g_))   // fast kernels allowed: the LDS-tiled marching form
         launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), effective_moduli(), ptrs3(fu_), partial_,
                         dscal_ + kSlotMean, stream_);
       else
@@ -558,7 +590,7 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
       time_end(0);
     } else {
       time_begin(0);
-      launch_stress(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs6(src), phi, nrm, ptrs6(tau_), derr_, stream_);
+      stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), src, phi, nrm);
       time_end(0);
       launch_sum6(g_, ptrs6(tau_), false, partial_, dscal_ + kSlotMean, stream_);   // tau_copy->average(), stays on the device
       time_begin(1);
@@ -583,7 +615,11 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
     Vec6 Ev;
     for (int c = 0; c < 6; ++c) Ev.v[c] = E6[c];
     time_begin(9);
-    if (fused)
+    if (fused && dfg())
+      launch_eps_delta_recompute(g_, ptrs3(fu_), ptrs6(src), stress_params(opt_.mu_0, opt_.lambda_0, 1.0), dfg_moduli(),
+                                 dscal_ + kSlotMean, (double)nglobal_, Ev, 2 * alpha * m, ptrs6(dst), partial_,
+                                 dscal_ + kSlotSumSq, stream_);
+    else if (fused)
       launch_eps_delta_recompute(g_, ptrs3(fu_), ptrs6(src), stress_params(opt_.mu_0, opt_.lambda_0, 1.0), phi,
                                  dscal_ + kSlotMean, (double)nglobal_, Ev, 2 * alpha * m, ptrs6(dst), partial_,
                                  dscal_ + kSlotSumSq, stream_);
@@ -601,7 +637,7 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
     // GammaOperatorCollocated  F:20302-20310: fftTensor, initBCProjector, Gamma0_hat, applyBCProjector, fftInvTensor on the
     // six components
     time_begin(0);
-    launch_stress(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs6(src), phi, nrm, ptrs6(tau_), derr_, stream_);
+    stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), src, phi, nrm);
     time_end(0);
     time_begin(2);
     fft_->forward(tau_, 6, g_.n, 1 / (double)nglobal_);   // fftTensor: 1/N on the forward transform  F:18531-18560
@@ -648,14 +684,17 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
   const bool mq_zero = frobenius(BC_MQ_) < kEps;
   // Voigt mixing: polarisation and divergence in one sweep (tau never stored); the laminate rule keeps the
   // two-kernel form (its per-voxel Newton solve is too costly to repeat at the six neighbours)
-  const bool fuse_sd = opt_.fuse_stress_div && opt_.mixing == kMixVoigt && mq_zero;
+  const bool fuse_sd = opt_.fuse_stress_div && opt_.mixing == kMixVoigt && mq_zero && !dfg();
   // with the fast kernels allowed (u_loop = 2) the LDS-tiled form takes over where the grid fits; it also delivers
   // the sums of tau, so mixed boundary conditions keep the fused sweep
   const bool tile_sd = opt_.fuse_stress_div && opt_.mixing == kMixVoigt && opt_.u_loop >= 2 && u_tile_supported(g_);
   if (tile_sd) {
     time_begin(0);
-    launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), effective_moduli(), ptrs3(fu_), partial_, dscal_ + kSlotMean,
-                    stream_);
+    if (dfg())
+      launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), dfg_moduli(), ptrs3(fu_), partial_, dscal_ + kSlotMean, stream_);
+    else
+      launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), effective_moduli(), ptrs3(fu_), partial_, dscal_ + kSlotMean,
+                      stream_);
     time_end(0);
     if (!mq_zero) {
       FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean, dscal_ + kSlotMean, 6 * sizeof(double), hipMemcpyDeviceToHost, stream_));
@@ -668,7 +707,7 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
     time_end(0);
   } else {
     time_begin(0);
-    launch_stress(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs6(src), phi, nrm, ptrs6(tau_), derr_, stream_);
+    stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), src, phi, nrm);
     time_end(0);
     if (!mq_zero) {
       launch_sum6(g_, ptrs6(tau_), false, partial_, dscal_ + kSlotMean, stream_);
@@ -956,7 +995,10 @@ bool Solver::u_loop_eligible(bool allow_mixed_bc) const {
       throw std::runtime_error("heat / porous mode: mixed boundary conditions run with method=basic (fg_run_load_case) only");
     return pt_.n >= 1;
   }
-  if (!(opt_.u_loop && opt_.mode == 0 && opt_.gamma_scheme == 0 && nranks_ == 1 && pt_.n >= 1 &&
+  // full_staggered: the displacement loop runs the tiled Voigt sweep only (the untiled sweep has no five-moduli form)
+  const bool scheme_ok = opt_.gamma_scheme == 0 ||
+                         (dfg() && opt_.mixing == kMixVoigt && opt_.u_loop >= 2 && opt_.u_tile && u_tile_supported(g_));
+  if (!(opt_.u_loop && opt_.mode == 0 && scheme_ok && nranks_ == 1 && pt_.n >= 1 &&
         (opt_.mixing == kMixVoigt || (opt_.mixing == kMixLaminate && normals_)) && opt_.bc_relax == 1.0))
     return false;
   if (frobenius(BC_MQ_) < kEps) return true;
@@ -986,7 +1028,7 @@ bool Solver::two_phase_complementary() {
 FieldPtrs<2> Solver::effective_moduli() {
   if (!mod_) {
     FG_HIP_CHECK(hipMalloc(&mod_, 2 * (size_t)g_.n * sizeof(double)));
-    mod_dirty_ = true;
+    mod_dirty_ = mod5_dirty_ = true;
   }
   FieldPtrs<2> mod;
   mod.p[0] = mod_;
@@ -999,6 +1041,46 @@ FieldPtrs<2> Solver::effective_moduli() {
     mod_dirty_ = false;
   }
   return mod;
+}
+
+void Solver::dfg_check() const {
+  if (opt_.mode == 1)
+    throw std::runtime_error("gamma_scheme full_staggered is not available in heat / porous mode (the reference's 3-component "
+                             "prolongation uses another grid convention)");
+  if (opt_.mixing != kMixVoigt)
+    throw std::runtime_error("gamma_scheme full_staggered supports Voigt mixing only (the laminate split is not linear in phi and "
+                             "needs normals on the fine grid)");
+  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("full_staggered is not available on slab-decomposed solvers");
+}
+
+FieldPtrs<5> Solver::dfg_moduli() {
+  dfg_check();
+  if (!mod5_) {
+    FG_HIP_CHECK(hipMalloc(&mod5_, 5 * (size_t)g_.n * sizeof(double)));
+    mod5_dirty_ = true;
+  }
+  FieldPtrs<5> mod;
+  for (int q = 0; q < 5; ++q) mod.p[q] = mod5_ + (long)q * g_.n;
+  if (mod5_dirty_) {
+    if (!phis_) {
+      FG_HIP_CHECK(hipMalloc(&phis_, 3 * (size_t)pt_.n * g_.n * sizeof(double)));
+      FG_HIP_CHECK(hipMemsetAsync(phis_, 0, 3 * (size_t)pt_.n * g_.n * sizeof(double), stream_));
+    }
+    for (int p = 0; p < pt_.n; ++p) {   // coarse input: the fine field is its piecewise-constant replica
+      if (fine_set_ & (1u << p)) continue;
+      FieldPtrs<3> s;
+      for (int c = 0; c < 3; ++c) s.p[c] = phis_ + (3L * p + c) * g_.n;
+      launch_dfg_fractions_replica(g_, phi_ + (long)p * g_.n, s, stream_);
+    }
+    launch_dfg_moduli(g_, phase_table(), phi_, phis_, mod, stream_);
+    mod5_dirty_ = false;
+  }
+  return mod;
+}
+
+void Solver::stress_to_tau(const StressParams& sp, double* src, const FieldPtrs<kMaxPhases>& phi, const FieldPtrs<3>& nrm) {
+  if (dfg()) launch_dfg_stress(0, g_, sp, ptrs6(src), dfg_moduli(), ptrs6(tau_), nullptr, nullptr, stream_);
+  else launch_stress(g_, sp, ptrs6(src), phi, nrm, ptrs6(tau_), derr_, stream_);
 }
 
 void Solver::build_laminate_lists() {
@@ -1083,7 +1165,10 @@ void Solver::u_pass_front(const double* E6) {
     }
     if (opt_.u_tile && u_tile_supported(g_)) {
       const bool sum_tau = !(frobenius(BC_MQ_) < kEps);   // mixed BC: sums of tau land in kSlotMean
-      if (two_phase_complementary()) {
+      if (dfg()) {   // full_staggered: the five moduli, also for two complementary phases
+        launch_u_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), dfg_moduli(), ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq,
+                      stream_, sum_tau);
+      } else if (two_phase_complementary()) {
         // two phases with phi_0 = 1 - phi_1: the sweep reads phi_1 and forms the moduli itself (8 B per voxel less)
         FieldPtrs<2> ph;
         ph.p[0] = phi_ + g_.n;
@@ -1095,6 +1180,8 @@ void Solver::u_pass_front(const double* E6) {
         launch_u_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), effective_moduli(), ptrs3(fu_alt_), E, partial_,
                       dscal_ + kSlotSumSq, stream_, sum_tau);
       }
+    } else if (dfg()) {   // u_loop_eligible admits full_staggered on tiled grids only
+      throw std::logic_error("full_staggered: the untiled displacement sweep has no five-moduli form");
     } else   // grids the tiles do not fit (odd nz, short rows): the untiled sweep
       launch_u_fast(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), effective_moduli(), ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq,
                     stream_);
@@ -1150,6 +1237,7 @@ void Solver::ensure_eps() {
 
 void Solver::iterate(const double* E6, int n) {
   FG_HIP_CHECK(hipSetDevice(device_));
+  if (dfg()) dfg_check();
   int i = 0;
   if (u_loop_eligible()) {
     if (!u_valid_ && n > 0 && opt_.mode == 1) {
@@ -1191,8 +1279,12 @@ void Solver::mean_stress(double* out6) {
   FieldPtrs<3> nrm;
   for (int c = 0; c < 3; ++c) nrm.p[c] = normals_ ? normals_ + (long)c * g_.n : nullptr;
   // meanPK1: alpha /= nxyz, accumulate  F:12318-12340
-  launch_stress_mean(g_, stress_params(0.0, 0.0, 1.0 / (double)nglobal_), ptrs6(eps_), phi, nrm, partial_,
-                     dscal_ + kSlotMean, derr_, stream_);
+  if (dfg())
+    launch_dfg_stress(1, g_, stress_params(0.0, 0.0, 1.0 / (double)nglobal_), ptrs6(eps_), dfg_moduli(), FieldPtrs<6>{}, partial_,
+                      dscal_ + kSlotMean, stream_);
+  else
+    launch_stress_mean(g_, stress_params(0.0, 0.0, 1.0 / (double)nglobal_), ptrs6(eps_), phi, nrm, partial_,
+                       dscal_ + kSlotMean, derr_, stream_);
   FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean, dscal_ + kSlotMean, 6 * sizeof(double), hipMemcpyDeviceToHost, stream_));
   FG_HIP_CHECK(hipStreamSynchronize(stream_));
   for (int c = 0; c < 6; ++c) out6[c] = hscal_[kSlotMean + c];
@@ -1205,7 +1297,12 @@ double Solver::mean_energy() {
   if (opt_.mode == 1) throw std::runtime_error("the energy error estimator is not available in heat / porous mode");
   FieldPtrs<3> nrm;
   for (int c = 0; c < 3; ++c) nrm.p[c] = normals_ ? normals_ + (long)c * g_.n : nullptr;
-  launch_energy_mean(g_, stress_params(0.0, 0.0, 1.0), ptrs6(eps_), phase_ptrs(), nrm, partial_, dscal_ + kSlotMean, derr_, stream_);
+  if (dfg())
+    launch_dfg_stress(2, g_, stress_params(0.0, 0.0, 1.0), ptrs6(eps_), dfg_moduli(), FieldPtrs<6>{}, partial_, dscal_ + kSlotMean,
+                      stream_);
+  else
+    launch_energy_mean(g_, stress_params(0.0, 0.0, 1.0), ptrs6(eps_), phase_ptrs(), nrm, partial_, dscal_ + kSlotMean, derr_,
+                       stream_);
   FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean, dscal_ + kSlotMean, sizeof(double), hipMemcpyDeviceToHost, stream_));
   FG_HIP_CHECK(hipStreamSynchronize(stream_));
   return hscal_[kSlotMean] / (double)nglobal_;
@@ -1415,6 +1512,7 @@ bool Solver::run_load_steps(const double* E6, const double* S6, const double* pa
 
 // runSolver  F:21400-21433 for one load step
 bool Solver::run_one_step(const double* E0, const double* S0) {
+  if (dfg()) dfg_check();
   // EpsilonErrorEstimator  F:14591-14637: constructed on the field the step starts from (zero for the first step)
   const double prev0 = fresh_step_ ? 0.0 : current_norm9();
   if (opt_.error_estimator >= 2) {
@@ -1613,6 +1711,15 @@ bool Solver::run_cg_u(const double* E0, double prev0) {
   };
   // fused form: u_p := u_r + beta u_p (beta from the sums at dscal_[i_num] / dscal_[i_den]) inside the sweep of the operator
   auto apply_dir = [&](int i_num, int i_den) {
+    if (dfg()) {
+      time_begin(0);
+      launch_u_tile_cg(g_, opt_.mu_0, opt_.lambda_0, ptrs3(u_p), ptrs3(u_r), ptrs3(p_alt), dfg_moduli(), ptrs3(fu_alt_), Z, dscal_,
+                       i_num, i_den, (double)nglobal_, std::numeric_limits<double>::min(), partial_, dscal_ + kSlotSumSq, stream_);
+      time_end(0);
+      fft_g0_chain(fu_alt_, -1.0, nullptr, tau_);
+      std::swap(u_p, p_alt);
+      return;
+    }
     FieldPtrs<2> m;
     const PhaseTable t = phase_table();
     const bool two = two_phase_complementary();
@@ -2113,7 +2220,7 @@ void Solver::run_stage(int stage, const double* E6) {
   switch (stage) {
     case kStageStress:
       if (pt_.n < 1) throw std::runtime_error("No materials specified");
-      launch_stress(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs6(eps_), phi, nrm, ptrs6(tau_), derr_, stream_);
+      stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), eps_, phi, nrm);
       check_device_error("stress");
       break;
     case kStageStressConst:
@@ -2226,7 +2333,7 @@ void Solver::get_field(const std::string& name, double* out) {
     for (int q = 0; q < kMaxPhases; ++q) phi.p[q] = q < pt_.n ? phi_ + (long)q * g_.n : nullptr;
     FieldPtrs<3> nrm;
     for (int c = 0; c < 3; ++c) nrm.p[c] = normals_ ? normals_ + (long)c * g_.n : nullptr;
-    launch_stress(g_, stress_params(0.0, 0.0, 1.0), ptrs6(eps_), phi, nrm, ptrs6(tau_), derr_, stream_);
+    stress_to_tau(stress_params(0.0, 0.0, 1.0), eps_, phi, nrm);
     check_device_error("sigma");
     download_unpadded(tau_, out, 6, g_.n);
     return;
@@ -2236,7 +2343,7 @@ void Solver::get_field(const std::string& name, double* out) {
     FieldPtrs<kMaxPhases> phi = phase_ptrs();
     FieldPtrs<3> nrm;
     for (int c = 0; c < 3; ++c) nrm.p[c] = normals_ ? normals_ + (long)c * g_.n : nullptr;
-    launch_stress(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs6(eps_), phi, nrm, ptrs6(tau_), derr_, stream_);
+    stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), eps_, phi, nrm);
     check_device_error("u");
     launch_div(g_, ptrs6(tau_), ptrs3(fu_), XHalo{{nullptr, nullptr}, {nullptr, nullptr}}, stream_);
     const double a = 1 / (2 * opt_.mu_0), mu_g = 1 / (4 * opt_.mu_0);

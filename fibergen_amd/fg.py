@@ -276,10 +276,15 @@ class FG:
         scheme = self._child_value(solver, "gamma_scheme", "auto", str)
         if scheme == "auto":
             scheme = "staggered"
-        if scheme not in ("staggered", "collocated") or (scheme == "collocated" and scalar):  # scalar: any non-elastic mode
-            raise RuntimeError("gamma scheme '%s' is not built on the MI355X path (staggered; collocated for elasticity): set "
-                               "<gamma_scheme>staggered</gamma_scheme> -- the schemes differ by their discretisation error, "
-                               "nothing is substituted silently" % scheme)
+        dfg = scheme in _DFG_SCHEMES   # the doubly fine grid  use_dfg F:14894-14897
+        if (scheme not in ("staggered", "collocated") and not dfg) or (scheme == "collocated" and scalar):  # scalar: any non-elastic mode
+            raise RuntimeError("gamma scheme '%s' is not built on the MI355X path (staggered, full_staggered, half_staggered; "
+                               "collocated for elasticity): set <gamma_scheme>staggered</gamma_scheme> -- the schemes differ by "
+                               "their discretisation error, nothing is substituted silently" % scheme)
+        if dfg and mode in ("heat", "porous"):
+            raise RuntimeError("gamma scheme '%s' is not available in %s mode on the MI355X path (elasticity and viscosity only)"
+                               % (scheme, mode))
+        self._scheme = scheme
         est = self._child_value(solver, "error_estimator", "epsilon", str)
         if est not in ("epsilon", "residual", "sigma", "energy", "none"):   # create_error_estimator  F:14940-14972
             if est == "div_sigma":   # DivSigmaErrorEstimator F:14473-14510 is a stub in the reference (abs = rel = 0: one iteration)
@@ -290,6 +295,9 @@ class FG:
             raise RuntimeError("Unknown mixing rule '%s'" % mixing)
         if scalar and mixing != "voigt":
             raise RuntimeError("mixing rule '%s' is not available in %s mode (voigt only)" % (mixing, mode))
+        if dfg and mixing != "voigt":
+            raise RuntimeError("gamma scheme '%s' is not available with mixing rule '%s' on the MI355X path (voigt only: the "
+                               "laminate split is not linear in phi)" % (scheme, mixing))
 
         if getattr(self, "_slabs", False):
             from .distributed import GlobalViewSolver
@@ -410,7 +418,26 @@ class FG:
         elif self._raw_phase and getattr(self, "_raw_normals", None) is not None and \
                 (self._want_normals or self._mixing == "laminate"):
             self._normals = self._raw_normals   # initMultiphase centroid normals  F:16861-16907
-        if self._raw_phase:
+        # full_staggered: <place_fiber> geometry is voxelised on the doubly fine grid and normalised there (initPhi under
+        # select_dfg(true) F:17152-17230); the solver keeps the coarse 8-cell means and the staggered fractions of the image
+        fine = getattr(self, "_scheme", "staggered") in ("full_staggered", "full-staggered") and not self._raw_phase
+        if fine:
+            from . import geometry
+            fshape = tuple(2 * n for n in shape)
+            phif, _n, real_vf = geometry.voxelize(self._fibers, fshape, self._dims, self._x0, nph, self._matrix_mat,
+                                                  want_normals=False, smooth_levels=self._solver_int("smooth_levels", -1),
+                                                  smooth_tol=self._solver_float("smooth_tol", 0.001), device=self._device)
+            phif = _normalize_phi(phif)
+            self._real_vf = real_vf
+            if self._want_normals:
+                _p, normals, _v = geometry.voxelize(self._fibers, shape, self._dims, self._x0, nph, self._matrix_mat,
+                                                    want_normals=True, device=self._device)
+                self._normals = normals
+            for p in range(nph):
+                lss.set_phase(p, self._phase_materials[p]["mu"], self._phase_materials[p]["lambda"])
+                lss.set_phase_fine(p, phif[p])
+            self._phi = lss.get_field("phi")   # the coarse field F:17180-17228
+        elif self._raw_phase:
             phi = self._phi
         else:
             from . import geometry
@@ -422,10 +449,11 @@ class FG:
             if normals is not None:
                 self._normals = normals
             self._real_vf = real_vf
-        phi = _normalize_phi(phi)  # normalizePhi  F:17588-17646 (last material wins)
-        self._phi = phi
-        for p in range(nph):
-            lss.set_phase(p, self._phase_materials[p]["mu"], self._phase_materials[p]["lambda"], phi[p])
+        if not fine:
+            phi = _normalize_phi(phi)  # normalizePhi  F:17588-17646 (last material wins)
+            self._phi = phi
+            for p in range(nph):
+                lss.set_phase(p, self._phase_materials[p]["mu"], self._phase_materials[p]["lambda"], phi[p])
         if self._normals is not None:
             lss.set_normals(self._normals)
         elif self._mixing == "laminate":
@@ -1080,6 +1108,9 @@ class FG:
             self._raw_normals = nrm / mag
         self._phase_valid = False
         return None
+
+
+_DFG_SCHEMES = ("full_staggered", "full-staggered", "half_staggered")   # F:15068
 
 
 def _normalize_phi(phi):

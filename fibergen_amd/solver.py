@@ -14,6 +14,11 @@ from . import _lib
 
 MIXING = {"voigt": 0, "laminate": 1}
 
+# gamma_scheme option values; full_staggered and half_staggered are the staggered operator with the material evaluated on
+# the doubly fine grid (use_dfg F:14894-14897, alias "full-staggered" F:15068): they differ only in how the fine phase
+# fields are made (voxelised on the fine grid, or replicated from the coarse one)
+GAMMA_SCHEMES = {"staggered": 0, "collocated": 1, "full_staggered": 2, "full-staggered": 2, "half_staggered": 2}
+
 STAGES = {"stress": 0, "div": 1, "fft_forward": 2, "g0": 3, "fft_inverse": 4, "eps": 5, "iteration": 6,
           "stress_const": 7}
 
@@ -72,6 +77,14 @@ class LSSolver:
             ptr = _dp(phi)
         self._check(self._lib.fg_set_phase(self._h, int(p), float(mu), float(lam), ptr))
 
+    def set_phase_fine(self, p, phi):
+        """gamma_scheme full_staggered: phase p's fractions on the doubly fine grid, shape (2nx, 2ny, 2nz)."""
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        fine = tuple(2 * n for n in self.shape)
+        if phi.shape != fine:
+            raise ValueError("the fine phase field must have shape %r" % (fine,))
+        self._check(self._lib.fg_set_phase_field_fine(self._h, int(p), _dp(phi)))
+
     def set_normals(self, normals):
         normals = np.ascontiguousarray(normals, dtype=np.float64)
         if normals.shape != (3,) + self.shape:
@@ -89,9 +102,9 @@ class LSSolver:
                     raise RuntimeError("Unknown solver method '%s'" % v)
                 self._check(self._lib.fg_set_option_i(self._h, b"method", 1 if v == "cg" else 0))
             elif k == "gamma_scheme":
-                if v not in ("staggered", "collocated"):
+                if v not in GAMMA_SCHEMES:
                     raise RuntimeError("Unknown gamma scheme '%s'" % v)
-                self._check(self._lib.fg_set_option_i(self._h, b"gamma_scheme", 1 if v == "collocated" else 0))
+                self._check(self._lib.fg_set_option_i(self._h, b"gamma_scheme", GAMMA_SCHEMES[v]))
             elif k == "mode":
                 if v not in ("elasticity", "heat", "porous", "viscosity"):
                     raise RuntimeError("mode '%s' is not available on the MI355X path" % v)

@@ -65,6 +65,12 @@ void fg_destroy(fg_solver* s);
  * (F:7333-7454).  Phase order = materials order.  phi may be NULL to keep the current field. */
 int fg_set_num_phases(fg_solver* s, int nphases);
 int fg_set_phase(fg_solver* s, int p, double mu, double lambda, const double* phi /* [nx][ny][nz] */);
+/* gamma_scheme 2: phase p's fractions on the doubly fine grid, [2nx][2ny][2nz] over the same box (initPhi after
+ * select_dfg(true) F:17152-17230, normalised there).  The image is reduced on the device to the coarse field (the 8-cell
+ * means of F:17180-17228, what "phi" returns) and to the three shear-group fractions, and is not kept.  A phase given through
+ * fg_set_phase instead is taken as replicated piecewise-constant onto the fine grid (initFullStageredRawPhases
+ * F:17136-17149, F:17648-17710: half_staggered and raw voxel data). */
+int fg_set_phase_field_fine(fg_solver* s, int p, const double* phi /* [2nx][2ny][2nz] */);
 /* interface normals for laminate mixing (LSSolver::_normals, F:14717) */
 int fg_set_normals(fg_solver* s, const double* normals /* [3][nx][ny][nz] */);
 
@@ -75,7 +81,14 @@ int fg_set_normals(fg_solver* s, const double* normals /* [3][nx][ny][nz] */);
  * fg_set_phase is the conductivity; E6 / S6 / out6 arrays carry 3 values followed by zeros; Voigt mixing, basic scheme;
  * 2 = viscosity F:15234-15239: dual Stokes scheme DeltaOperatorStaggered F:20422-20460, mu of fg_set_phase is the
  * fluidity constant of the XML, "epsilon" holds the fluid stress, "sigma" the shear rate; Voigt mixing, basic scheme),
- * gamma_scheme (0 = staggered, 1 = collocated: GammaOperatorCollocated F:20302-20310, Fourier-space 6x6 Gamma0),
+ * gamma_scheme (0 = staggered, 1 = collocated: GammaOperatorCollocated F:20302-20310, Fourier-space 6x6 Gamma0; 2 =
+ * full_staggered / half_staggered: the staggered operator (GammaOperator F:20480-20530) with every material evaluation on the
+ * doubly fine grid, use_dfg F:14894-14897 -- calcStress F:18134-18348, calcMeanStress / calcMeanEnergy F:17765-17811 and the
+ * sigma / energy estimators F:14410-14587 prolong the strain (prolongate_to_dfg F:14216-14270), evaluate PK1 per fine cell
+ * and restrict (restrict_from_dfg F:14273-14335); for Voigt mixing of linear laws this equals a coarse evaluation in which
+ * each component group reads its own staggered phase fractions, which is how it runs here.  The reference medium
+ * (calcRefMaterial F:22283-22313), "phi" and fg_volume_fraction stay on the coarse field.  Elasticity and viscosity with
+ * Voigt mixing, basic scheme and CG; laminate mixing, mode heat / porous and slab-decomposed solvers are refused),
  * method (0 = basic scheme, runBasic F:21716-21805; 1 = conjugate gradients, runCGElasticity
  * F:23153-23247, the reference's default), error_estimator (0 = epsilon F:14591-14637; 1 = residual F:14382-14405, method
  * cg only; 2 = sigma F:14514-14587; 3 = energy F:14410-14468; 4 = none F:14370-14378 -- 2 and 3 re-measure <sigma> / <W> of
