@@ -127,3 +127,86 @@ class DfgViscosityOracle(DfgMixin, ViscosityOracle):
     def __post_init__(self):
         super().__post_init__()
         self._dfg_setup()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Shared problem builders of the dfg test files (CPU only)
+
+def tile_shape(grid):
+    """Which instantiation of the five-moduli tiled sweeps (k_u_tile / k_eps_tile, NMOD = 5) a grid takes, restated from
+    u_tile_supported and launch_u_tile / launch_eps_tile in fg_kernels_fast.hip: "<8,1>" (nz = 128, one wave per row),
+    "<6,2>" (nz = 256, two waves per row), "<8,0>" with halo lanes for the rest -- "short" (40 <= nz/2 < 62: one tile whose
+    surplus lanes hold wrapped copies), "exact" (nz/2 = 62) or "two" (nz/2 > 62: several z tiles, the last one clamped) --
+    and "untiled" where the tiles do not fit (odd nz, nz/2 < 40, ny < 14, nx < 4)."""
+    nx, ny, nz = grid
+    nzh = nz // 2
+    if nz % 2 or nzh < 40 or ny < 14 or nx < 4:
+        return "untiled"
+    if nzh == 64:
+        return "<8,1>"
+    if nzh == 128:
+        return "<6,2>"
+    return "<8,0> short" if nzh < 62 else ("<8,0> exact" if nzh == 62 else "<8,0> two")
+
+
+def smooth_field(rng, shape):
+    """test_gpu_fuzz.smooth_field: a smooth periodic field in [0, 1] with flat parts at both ends (on the fine shape: pure
+    fine cells at 0 and 1 next to mixtures)"""
+    from test_gpu_fuzz import smooth_field as f
+    return f(rng, shape)
+
+
+def fine_images(rng, grid, nph, sharp=False):
+    """nph fine phase images (shape 2 grid) that sum to one: smooth fields with pure cells, or a sharp 0/1 image"""
+    fshape = tuple(2 * n for n in grid)
+    if nph == 1:
+        return [np.ones(fshape)]
+    cut = (lambda f: (f > 0.5).astype(np.float64)) if sharp else (lambda f: f)
+    p1 = cut(smooth_field(rng, fshape))
+    if nph == 2:
+        return [1.0 - p1, p1]
+    p2 = np.minimum(cut(smooth_field(rng, fshape)), 1.0 - p1)
+    out = [1.0 - p1 - p2, p1, p2]
+    for _ in range(nph - 3):
+        out.append(np.zeros(fshape))
+    return out
+
+
+def split_input(images, kinds):
+    """(fine, coarse, oracle_fine) for per-phase input kinds "fine" / "coarse": a coarse phase is handed over as the
+    8-cell mean of its image and is, for the reference, the piecewise-constant replica of that mean
+    (initFullStageredRawPhases F:17648-17710)."""
+    fine, coarse, ofine = [], [], []
+    for img, kind in zip(images, kinds):
+        if kind == "fine":
+            fine.append(img)
+            coarse.append(None)
+            ofine.append(img)
+        else:
+            c = restrict_component(img, (0, 0, 0))
+            fine.append(None)
+            coarse.append(c)
+            ofine.append(replicate(c))
+    return fine, coarse, ofine
+
+
+def input_kinds(kind, nph):
+    """"fine" / "coarse": all phases alike; "mixed": alternating, phase 0 coarse (needs two phases)"""
+    if kind == "mixed":
+        assert nph >= 2
+        return ["coarse" if p % 2 == 0 else "fine" for p in range(nph)]
+    return [kind] * nph
+
+
+def calc_stress_fractions(eps, phis_fine, mats, mu_0, lambda_0, viscosity=False):
+    """calcStress F:18134-18184 on the coarse form: pk1_fractions with C0 subtracted the way LSOracle.calc_stress does"""
+    if viscosity:   # ScalarLinearIsotropic(6) with mu / 2 (F:15237): the Hooke law with (mu / 4, 0)
+        mats = [(m / 4, 0.0) for m, _ in mats]
+    P = pk1_fractions(eps, phis_fine, mats)
+    if mu_0 != 0:
+        P = P + (-2.0 * mu_0) * eps
+    if lambda_0 != 0:
+        tr = eps[0] + eps[1] + eps[2]
+        for c in range(3):
+            P[c] = P[c] + (-lambda_0) * tr
+    return P

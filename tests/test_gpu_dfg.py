@@ -3,7 +3,8 @@ fine-grid restatement of tests/dfg_reference.py, and the reference's viscosity d
 import numpy as np
 import pytest
 
-from dfg_reference import DfgLSOracle, DfgViscosityOracle, replicate, restrict_component
+from dfg_reference import (DfgLSOracle, DfgViscosityOracle, fine_images, input_kinds, replicate, restrict_component, split_input,
+                           tile_shape)
 from helpers import INCLUSION, MATRIX, lame, rel_err, sphere_phi
 
 pytestmark = pytest.mark.gpu
@@ -218,3 +219,41 @@ def test_fg_viscosity_demo_full_staggered():
     assert o.run_cg(E) is False
     assert lss.iterations == o.iterations
     assert rel_err(lss.mean_stress(), o.mean_stress()) < 1e-8
+
+
+TILED_GRIDS = [((6, 14, 128), (2.0, 1.0, 0.5)), ((16, 16, 128), (1, 1, 1)), ((4, 14, 256), (1.0, 1.5, 0.8)), ((5, 20, 256), (1, 1, 1)),
+               ((5, 14, 100), (0.7, 1.3, 2.1)), ((4, 16, 80), (1, 1, 1)), ((4, 14, 200), (2.0, 1.0, 0.5)), ((6, 15, 130), (1, 1, 1)),
+               ((8, 14, 124), (1.0, 2.0, 0.5))]
+
+
+@pytest.mark.parametrize("variant", ["basic_mixed_bc", "cg", "cg_mixed_bc", "viscosity_mixed_bc"])
+@pytest.mark.parametrize("grid,dims", TILED_GRIDS, ids=["%dx%dx%d-%s" % (g + (tile_shape(g).replace(" ", "-"),)) for g, _ in TILED_GRIDS])
+def test_every_tile_shape_converged_runs(grid, dims, variant):
+    """Converged runs on every shape of the five-moduli tiled sweeps, three phases (coarse, fine, coarse input) with pure cells:
+    basic_mixed_bc -- the displacement loop with the sums of tau (k_u_tile<..., SUMT, 5>); cg -- the displacement-space CG
+    (launch_u_tile_cg: k_u_tile<..., CGP, 5>); cg_mixed_bc -- a projector sends CG to strain space (u_loop_eligible() is false
+    with a projector unless mixed BC are allowed, i.e. in run() of the basic scheme): k_eps_tile<..., 5> per operator
+    application; viscosity_mixed_bc -- k_eps_tile<..., 5> with the recomputing tail and the adjusted sums"""
+    rng = np.random.default_rng(15)
+    viscosity = variant.startswith("viscosity")
+    mats = [(1.0, 0.0), (0.05, 0.0), (3.0, 0.0)] if viscosity else [lame(**MATRIX), lame(**INCLUSION), (0.9, 1.7)]
+    fine, coarse, ofine = split_input(fine_images(rng, grid, 3), input_kinds("mixed", 3))
+    cg = variant.startswith("cg")
+    kw = dict(tol=1e-6, bc_tol=1e-8) if variant.endswith("mixed_bc") else dict(tol=1e-6)
+    from fibergen_amd import LSSolver
+    s = LSSolver(*grid, *dims)
+    s.set_options(mode="viscosity" if viscosity else "elasticity", gamma_scheme="full_staggered")
+    s.set_num_phases(3)
+    for p, (mu, lam) in enumerate(mats):
+        s.set_phase(p, mu, lam, coarse[p])
+        if fine[p] is not None:
+            s.set_phase_fine(p, fine[p])
+    s.set_options(method="cg" if cg else "basic", **kw)
+    o = (DfgViscosityOracle if viscosity else DfgLSOracle)(*grid, *dims, mats=mats, phis=[np.zeros(grid)] * 3, phis_fine=ofine, **kw)
+    if variant == "viscosity_mixed_bc":
+        _check(s, o, np.array([0, 0, 0, 0.3, -0.2, 1.0]), np.zeros(6), P=np.diag([0.0, 0, 0, 0.5, 0.5, 0.5]))
+    elif variant.endswith("mixed_bc"):
+        _check(s, o, np.array([1.0, 0, 0, 0, 0, 0.3]), np.zeros(6), cg=cg, P=np.diag([1.0, 0, 0, 0, 0, 0.5]))
+    else:
+        _check(s, o, np.array([1.0, 0, 0, 0, 0, 0.5]), cg=cg)
+    s.close()
