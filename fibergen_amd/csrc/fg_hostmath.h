@@ -51,6 +51,15 @@ inline void voigt_mv(const Mat6& M, const double* v, double* out) {
   }
 }
 
+// calcBCMean  F:20242-20245: E = E0 + bc_relax M:(S0 - QC0:E0)
+inline void bc_mean(const Mat6& QC0, const Mat6& M, double bc_relax, const double* E0, const double* S0, double* E) {
+  double t1[6], t2[6], t3[6];
+  voigt_mv(QC0, E0, t1);
+  for (int i = 0; i < 6; ++i) t2[i] = S0[i] - t1[i];
+  voigt_mv(M, t2, t3);
+  for (int i = 0; i < 6; ++i) E[i] = E0[i] + bc_relax * t3[i];
+}
+
 // Voigt::dyad4(A, B) column by column  F:582-597
 inline Mat6 voigt_mm(const Mat6& A, const Mat6& B) {
   Mat6 C;

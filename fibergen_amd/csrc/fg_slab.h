@@ -55,6 +55,11 @@ class SlabGroup {
   bool run_cg_scalar(const double* E0, double prev0);
   bool agree_on_voting();                                              // does any rank carry a convergence callback?
   bool stop_requested() const;                                         // reduced flag word: some rank was cancelled
+  // _converged on the rule's measurement with the group's hooks (fg_stop_rule.h); true: the loop ends, *failed says how
+  template <class BcOk>
+  bool converged(const StopRule& rule, long iter, bool voting, BcOk bc_ok, bool* failed, bool callbacks = true);
+  void set_sumsq(int slot, int ncomp);
+  void finish_cg_u(long iter, const double* E, double t_start);
   void vote(double* v2);                                               // sums of two host values over the ranks
   void pass_exact(const double* E6, bool mixed_bc);                    // strain-state pipeline, adopts
   void wait_norms();

@@ -2,7 +2,6 @@
 // See fg_slab.h, fg_slab_plan.h (layouts, exchange plan) and fg_comm.h (transports).
 #include "fg_slab.h"
 
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -21,11 +20,6 @@ namespace {
 constexpr double kEps = 2.220446049250313e-16;
 // comm -> compute event slots
 constexpr int kXA2AFwd = 0, kXA2ABwd = 3, kXHaloU = 6, kXHaloTau = 7, kXModuli = 8, kXSums = 9;
-
-double now_seconds() {
-  using clk = std::chrono::steady_clock;
-  return std::chrono::duration<double>(clk::now().time_since_epoch()).count();
-}
 
 // y lengths the blocked FFT pass does not cover: plain [nxl][ny][nzc] <-> blocked [q][nxl][nyl][nzc] copy of one component
 __global__ void k_block_remap(const cplx* in, cplx* out, int nxl, int ny, int nyl, int nzc, int to_blocked) {
@@ -680,6 +674,50 @@ void SlabGroup::wait_norms() {
 
 bool SlabGroup::stop_requested() const { return m_[0]->hscal_[kSlotFlag + 1] != 0.0; }
 
+// The group's side of the stop rule (fg_stop_rule.h).  rel_err comes from all-reduced sums and is the same on every rank; so
+// is the stop word, and the callbacks' answers are voted on: every rank takes the same decision.  callbacks = false: the fused
+// scalar loops, which are chosen when no rank votes and have never called a callback (on a lone slab one may be installed).
+template <class BcOk>
+bool SlabGroup::converged(const StopRule& rule, long iter, bool voting, BcOk bc_ok, bool* failed, bool callbacks) {
+  auto record = [&](double rel_err) {
+    for (Solver* s : m_) s->residuals_.push_back(rel_err);
+  };
+  auto poll = [&] {
+    StopPoll p;
+    for (Solver* s : m_) {
+      if (callbacks && s->cb_ && s->cb_(s->cb_user_)) p.stop = true;
+      if (s->cancel_) p.cancelled = true;   // cancelled from inside the callback
+    }
+    return agree_poll(p, m_[0]->nranks_, voting, [&](double* v2) { vote(v2); });
+  };
+  const StopDecision d = rule.decide(iter, stop_hooks([&] { return stop_requested(); }, record, poll, bc_ok));
+  *failed = d == StopDecision::kFail;
+  return d != StopDecision::kContinue;
+}
+
+// the reduced sums of squares hscal_[slot .. slot + ncomp) as every member's sumsq_ (zero beyond ncomp)
+void SlabGroup::set_sumsq(int slot, int ncomp) {
+  for (int c = 0; c < 6; ++c) {
+    const double ss = c < ncomp ? m_[0]->hscal_[slot + c] : 0.0;
+    for (Solver* s : m_) s->sumsq_[c] = ss;
+  }
+}
+
+// end of a CG run in displacement / potential space: the state is (E, u_e), the strain field is materialised from it
+void SlabGroup::finish_cg_u(long iter, const double* E, double t_start) {
+  for (Solver* s : m_) {
+    s->in_run_ = false;
+    s->iterations_ = iter;
+    s->su_valid_ = true;
+    s->eps_stale_ = true;
+    for (int c = 0; c < 6; ++c) s->E_cur_[c] = E[c];
+    s->slab_materialise_eps();
+  }
+  synchronize();
+  const double dt = now_seconds() - t_start;
+  for (Solver* s : m_) s->solve_time_ += dt;
+}
+
 // all members have left their local contribution in dscal_[slot..slot+n): reduce over ranks, bring to every host
 void SlabGroup::reduce_and_fetch(int slot, int n, bool min_op) {
   for (Solver* s : m_) s->slab_reduce(slot, n, min_op);
@@ -1012,7 +1050,7 @@ bool SlabGroup::run_step(const double* E0, const double* S0, bool fresh) {
   require_scalar_fast(true);
   const bool fast_allowed = fast_ok(true);
   bool fast = fast_allowed;
-  double prev = 0.0;   // EpsilonErrorEstimator  F:14591-14637: norms of the field the step starts from
+  double prev0 = 0.0;   // EpsilonErrorEstimator  F:14591-14637: norms of the field the step starts from
   if (fresh) {
     for (Solver* s : m_) {
       FG_HIP_CHECK(hipMemsetAsync(s->eps_, 0, 6 * (size_t)s->g_.n * sizeof(double), s->stream_));   // F:21379
@@ -1023,8 +1061,9 @@ bool SlabGroup::run_step(const double* E0, const double* S0, bool fresh) {
       for (int i = 0; i < 6; ++i) s->E_cur_[i] = E0[i];
     }
   } else {
-    prev = current_norm9();
+    prev0 = current_norm9();
   }
+  StopRule rule = a.stop_rule(prev0);
   estimator_begin(fresh);
   for (Solver* s : m_) s->in_run_ = true;
   // a continuing step in the displacement loop: the state is u of the previous load (eps = E_old + sym grad u); one
@@ -1045,17 +1084,12 @@ bool SlabGroup::run_step(const double* E0, const double* S0, bool fresh) {
   double E[6], E_next[6];
   for (int i = 0; i < 6; ++i) E[i] = E0[i];
   bool failed = false;
-  const double small = std::numeric_limits<double>::min();
   const double nglobal = (double)a.nglobal_;
 
   for (;;) {
     if (update_ref) {
       calc_ref_material();
-      double t1[6], t2[6], t3[6];   // calcBCMean  F:20242-20245
-      voigt_mv(a.BC_QC0_, E0, t1);
-      for (int i = 0; i < 6; ++i) t2[i] = S0[i] - t1[i];
-      voigt_mv(a.BC_M_, t2, t3);
-      for (int i = 0; i < 6; ++i) E[i] = E0[i] + a.opt_.bc_relax * t3[i];
+      bc_mean(a.BC_QC0_, a.BC_M_, a.opt_.bc_relax, E0, S0, E);
       update_ref = false;
       if (fast) prepare();   // effective moduli are independent of the reference material, but may not exist yet
     }
@@ -1100,48 +1134,10 @@ bool SlabGroup::run_step(const double* E0, const double* S0, bool fresh) {
       for (int c = 0; c < 6; ++c) E_next[c] = E[c] - t1[c];   // alpha = -1  (F:20575)
     }
 
-    // component_norm + fix_dim + norm_2 over 9 mirrored entries  F:10127-10138, F:14600-14609, F:14627
-    double mm[6], s9 = 0.0;
-    for (int c = 0; c < 6; ++c) {
-      const double ss = a.hscal_[kSlotSumSq + c];
-      for (Solver* s : m_) s->sumsq_[c] = ss;
-      mm[c] = std::sqrt(ss / nglobal);
-    }
-    for (int c = 0; c < 6; ++c) s9 += mm[c] * mm[c];
-    for (int c = 3; c < 6; ++c) s9 += mm[c] * mm[c];
-    const double cur = std::sqrt(s9);
-    double abs_err = std::fabs(prev - cur);
-    double rel_err = abs_err / (small + cur);
-    prev = cur;
-    if (a.opt_.error_estimator >= 2) estimator_update(&abs_err, &rel_err);   // sigma / energy / none: F:14410-14587
-
-    // _converged  F:21177-21244.  rel_err comes from all-reduced sums and is the same on every rank; so is the stop word.
-    if (std::isnan(rel_err) || stop_requested()) {
-      failed = true;
-      break;
-    }
-    for (Solver* s : m_) s->residuals_.push_back(rel_err);
-    bool stop = false, cancelled = false;
-    for (Solver* s : m_) {
-      if (s->cb_ && s->cb_(s->cb_user_)) stop = true;
-      if (s->cancel_) cancelled = true;   // cancelled from inside the callback
-    }
-    if (voting) {
-      double v[2] = {stop ? 1.0 : 0.0, cancelled ? 1.0 : 0.0};
-      vote(v);
-      stop = v[0] != 0.0;
-      cancelled = v[1] != 0.0;
-    }
-    if (a.nranks_ > 1 && !voting) cancelled = false;   // an asynchronous fg_cancel: acted upon through the next flag word
-    if (stop) break;
-    if (cancelled) {
-      failed = true;
-      break;
-    }
-    if (iter >= a.opt_.maxiter) break;
-    if (rel_err <= a.opt_.tol || abs_err <= a.opt_.abs_tol) {
-      if (bc_error(E0, S0) <= a.opt_.bc_tol) break;
-    }
+    set_sumsq(kSlotSumSq, 6);
+    rule.measure(norm9_of_sums(a.sumsq_, nglobal));
+    if (a.opt_.error_estimator >= 2) estimator_update(&rule.abs_err, &rule.rel_err);   // sigma / energy / none: F:14410-14587
+    if (converged(rule, iter, voting, [&] { return bc_error(E0, S0) <= a.opt_.bc_tol; }, &failed)) break;
     if (pending) {
       if (voting) pass_fast_chain();
       for (Solver* s : m_) {
@@ -1197,7 +1193,6 @@ bool SlabGroup::run_cg(const double* E6, const double* S6, bool fresh) {
     prepare();
   }
   const bool voting = agree_on_voting();
-  const bool residual_est = a.opt_.error_estimator == 1;
   const double small = std::numeric_limits<double>::min();
   const double nglobal = (double)a.nglobal_;
   const int blk[2] = {kSlotCg, kSlotCg + 8}, s0 = kSlotCg + 16;
@@ -1280,13 +1275,13 @@ bool SlabGroup::run_cg(const double* E6, const double* S6, bool fresh) {
     launch_cgu_dot(1, s->gu_, strided3(u_e(s), s->ucs_), strided3(u_r(s), s->ucs_), E, s->partial_, s->dscal_ + blk[0], s->stream_);
     s->slab_reduce(blk[0], 7, false);   // gamma_0 = r:r / N + tiny
   }
-  double gamma_cur = 0.0, gamma_0 = 0.0;
-  if (residual_est) {
+  double gamma_0 = 0.0;   // only the residual estimator reads it
+  if (a.opt_.error_estimator == 1) {
     fetch7(blk[0]);
     wait_norms();
-    gamma_cur = gamma_0 = a.hscal_[kSlotCg + 6] / nglobal + small;
+    gamma_0 = a.hscal_[kSlotCg + 6] / nglobal + small;
   }
-  double prev = prev0;   // estimator constructed on the field the step starts from
+  StopRule rule = a.stop_rule(prev0, gamma_0);
   long iter = 0;
   bool failed = false, applied = false;
   int dir_cur = 0, dir_nxt = 1;   // fused: slots of the pending direction update
@@ -1343,66 +1338,16 @@ bool SlabGroup::run_cg(const double* E6, const double* S6, bool fresh) {
       s->eps_stale_ = true;
       for (int c = 0; c < 6; ++c) s->E_cur_[c] = E.v[c];
     }
-    double m[6], s9 = 0.0;
-    for (int c = 0; c < 6; ++c) {
-      const double ss = a.hscal_[kSlotCg + c];
-      for (Solver* s : m_) s->sumsq_[c] = ss;
-      m[c] = std::sqrt(ss / nglobal);
-    }
-    for (int c = 0; c < 6; ++c) s9 += m[c] * m[c];
-    for (int c = 3; c < 6; ++c) s9 += m[c] * m[c];
-    const double curn = std::sqrt(s9);
-    double abs_err = std::fabs(prev - curn);
-    double rel_err = abs_err / (small + curn);
-    prev = curn;
-    if (residual_est) {   // update_cg(gamma, gamma0)  F:14397-14401 with the gamma this iteration started from
-      abs_err = std::sqrt(gamma_cur);
-      rel_err = std::sqrt(gamma_cur / gamma_0);
-      gamma_cur = a.hscal_[kSlotCg + 6] / nglobal + small;
-    }
-    if (std::isnan(rel_err) || stop_requested()) {   // _converged  F:21177-21244, decisions on reduced values only
-      failed = true;
-      break;
-    }
-    for (Solver* s : m_) s->residuals_.push_back(rel_err);
-    bool stop = false, cancelled = false;
-    for (Solver* s : m_) {
-      if (s->cb_ && s->cb_(s->cb_user_)) stop = true;
-      if (s->cancel_) cancelled = true;
-    }
-    if (voting) {
-      double v[2] = {stop ? 1.0 : 0.0, cancelled ? 1.0 : 0.0};
-      vote(v);
-      stop = v[0] != 0.0;
-      cancelled = v[1] != 0.0;
-    }
-    if (a.nranks_ > 1 && !voting) cancelled = false;
-    if (stop) break;
-    if (cancelled) {
-      failed = true;
-      break;
-    }
-    if (iter >= a.opt_.maxiter) break;
-    if (rel_err <= a.opt_.tol || abs_err <= a.opt_.abs_tol) {
-      if (bc_error(E0, S0) <= a.opt_.bc_tol) break;
-    }
+    set_sumsq(kSlotCg, 6);
+    rule.measure(norm9_of_sums(a.sumsq_, nglobal), a.hscal_[kSlotCg + 6] / nglobal + small);   // r:r after the update: the next gamma
+    if (converged(rule, iter, voting, [&] { return bc_error(E0, S0) <= a.opt_.bc_tol; }, &failed)) break;
     iter++;
     if (!applied) {
       if (fused_dir) dir_cur = cur, dir_nxt = nxt;   // formed inside the next operator application
       else direction_update(cur, nxt);
     }
   }
-  for (Solver* s : m_) {
-    s->in_run_ = false;
-    s->iterations_ = iter;
-    s->su_valid_ = true;
-    s->eps_stale_ = true;
-    for (int c = 0; c < 6; ++c) s->E_cur_[c] = E.v[c];
-    s->slab_materialise_eps();
-  }
-  synchronize();
-  const double dt = now_seconds() - t_start;
-  for (Solver* s : m_) s->solve_time_ += dt;
+  finish_cg_u(iter, E.v, t_start);
   return failed;
 }
 
@@ -1413,7 +1358,6 @@ bool SlabGroup::run_cg(const double* E6, const double* S6, bool fresh) {
 bool SlabGroup::run_cg_scalar(const double* E0, double prev0) {
   Solver& a = *m_[0];
   const double t_start = now_seconds();
-  const bool residual_est = a.opt_.error_estimator == 1;
   const double small = std::numeric_limits<double>::min();
   const double nglobal = (double)a.nglobal_;
   if (a.opt_.update_ref) {
@@ -1423,6 +1367,15 @@ bool SlabGroup::run_cg_scalar(const double* E0, double prev0) {
   const bool voting = agree_on_voting();
   Vec6 E, Z;
   for (int i = 0; i < 6; ++i) E.v[i] = i < 3 ? E0[i] : 0.0, Z.v[i] = 0.0;
+  const double S_zero[6] = {0, 0, 0, 0, 0, 0};
+  // The norm of the gradient in this file's scalar loops is sqrt(sum_c ss_c / N); the single-GPU loops take the square root
+  // of every component first and square it again (norm3_of_sums).  The two round differently, and a rounding is a value:
+  // each keeps its own.
+  auto norm_of_sums = [&](const double* sumsq) {
+    double s3 = 0.0;
+    for (int c = 0; c < 3; ++c) s3 += sumsq[c] / nglobal;
+    return std::sqrt(s3);
+  };
   auto T_e = [](Solver* s) { return s->su_[s->su_cur_]; };
   auto T_w = [](Solver* s) { return s->su_[s->su_cur_ ^ 1]; };
   auto T_r = [](Solver* s) { return s->scg_; };
@@ -1502,9 +1455,7 @@ bool SlabGroup::run_cg_scalar(const double* E0, double prev0) {
     }
     fetch7(blk[0]);
     wait_norms();
-    double gamma_cur = a.hscal_[kSlotCg + 6] / nglobal + small;
-    const double gamma_0 = gamma_cur;
-    double prev = prev0;
+    StopRule rule = a.stop_rule(prev0, a.hscal_[kSlotCg + 6] / nglobal + small);
     long iter = 0;
     bool failed = false, applied = false;
     for (;;) {
@@ -1539,28 +1490,9 @@ bool SlabGroup::run_cg_scalar(const double* E0, double prev0) {
         applied = true;
       }
       wait_norms();
-      double s3 = 0.0;
-      for (int c = 0; c < 6; ++c) {
-        const double ss = c < 3 ? a.hscal_[kSlotCg + c] : 0.0;
-        for (Solver* s : m_) s->sumsq_[c] = ss;
-        s3 += ss / nglobal;
-      }
-      const double curn = std::sqrt(s3);
-      double abs_err = std::fabs(prev - curn);
-      double rel_err = abs_err / (small + curn);
-      prev = curn;
-      if (residual_est) {   // update_cg(gamma, gamma0)  F:14397-14401 with the gamma this iteration started from
-        abs_err = std::sqrt(gamma_cur);
-        rel_err = std::sqrt(gamma_cur / gamma_0);
-      }
-      gamma_cur = a.hscal_[kSlotCg + 6] / nglobal + small;
-      if (std::isnan(rel_err) || stop_requested()) {
-        failed = true;
-        break;
-      }
-      for (Solver* s : m_) s->residuals_.push_back(rel_err);
-      if (iter >= a.opt_.maxiter) break;
-      if (rel_err <= a.opt_.tol || abs_err <= a.opt_.abs_tol) {
+      set_sumsq(kSlotCg, 3);
+      rule.measure(norm_of_sums(a.sumsq_), a.hscal_[kSlotCg + 6] / nglobal + small);   // r.r after the update: the next gamma
+      auto bc_ok = [&] {
         // bc_error reads the gradient of the current iterate: component 0 of the state buffer must be it
         for (size_t i = 0; i < m_.size(); ++i) {
           Solver* s = m_[i];
@@ -1572,31 +1504,22 @@ bool SlabGroup::run_cg_scalar(const double* E0, double prev0) {
           s->eps_stale_ = true;
           for (int c = 0; c < 6; ++c) s->E_cur_[c] = E.v[c];
         }
-        double S0[6] = {0, 0, 0, 0, 0, 0};
-        if (bc_error(E.v, S0) <= a.opt_.bc_tol) break;
-      }
+        return bc_error(E.v, S_zero) <= a.opt_.bc_tol;
+      };
+      if (converged(rule, iter, voting, bc_ok, &failed, false)) break;
       iter++;
     }
     for (size_t i = 0; i < m_.size(); ++i) {
       Solver* s = m_[i];
       if (e_cur[i] != T_e(s))
         FG_HIP_CHECK(hipMemcpyAsync(T_e(s), e_cur[i], (size_t)s->ucs_ * sizeof(double), hipMemcpyDeviceToDevice, s->stream_));
-      s->in_run_ = false;
-      s->iterations_ = iter;
-      s->su_valid_ = true;
-      s->eps_stale_ = true;
-      for (int c = 0; c < 6; ++c) s->E_cur_[c] = E.v[c];
-      s->slab_materialise_eps();
     }
-    synchronize();
-    const double dt = now_seconds() - t_start;
-    for (Solver* s : m_) s->solve_time_ += dt;
+    finish_cg_u(iter, E.v, t_start);
     return failed;
   }
   dot(1, false, false, kSlotCg, 7);
-  double gamma = a.hscal_[kSlotCg + 6] / nglobal + small;
-  const double gamma_0 = gamma;
-  double prev = prev0;
+  StopRule rule = a.stop_rule(prev0, a.hscal_[kSlotCg + 6] / nglobal + small);
+  double& gamma = rule.gamma_cur;
   long iter = 0;
   bool failed = false;
   for (;;) {
@@ -1612,64 +1535,16 @@ bool SlabGroup::run_cg_scalar(const double* E0, double prev0) {
       s->eps_stale_ = true;
       for (int c = 0; c < 6; ++c) s->E_cur_[c] = E.v[c];
     }
-    double s3 = 0.0;
-    for (int c = 0; c < 6; ++c) {
-      const double ss = c < 3 ? a.hscal_[kSlotCg + c] : 0.0;
-      for (Solver* s : m_) s->sumsq_[c] = ss;
-      s3 += ss / nglobal;
-    }
-    const double cur = std::sqrt(s3);
-    double abs_err = std::fabs(prev - cur);
-    double rel_err = abs_err / (small + cur);
-    prev = cur;
-    if (residual_est) {   // update_cg(gamma, gamma0)  F:14397-14401
-      abs_err = std::sqrt(gamma);
-      rel_err = std::sqrt(gamma / gamma_0);
-    }
-    if (std::isnan(rel_err) || stop_requested()) {
-      failed = true;
-      break;
-    }
-    for (Solver* s : m_) s->residuals_.push_back(rel_err);
-    bool stop = false, cancelled = false;
-    for (Solver* s : m_) {
-      if (s->cb_ && s->cb_(s->cb_user_)) stop = true;
-      if (s->cancel_) cancelled = true;
-    }
-    if (voting) {
-      double v[2] = {stop ? 1.0 : 0.0, cancelled ? 1.0 : 0.0};
-      vote(v);
-      stop = v[0] != 0.0;
-      cancelled = v[1] != 0.0;
-    }
-    if (a.nranks_ > 1 && !voting) cancelled = false;
-    if (stop) break;
-    if (cancelled) {
-      failed = true;
-      break;
-    }
-    if (iter >= a.opt_.maxiter) break;
-    if (rel_err <= a.opt_.tol || abs_err <= a.opt_.abs_tol) {
-      double S0[6] = {0, 0, 0, 0, 0, 0};
-      if (bc_error(E.v, S0) <= a.opt_.bc_tol) break;
-    }
+    set_sumsq(kSlotCg, 3);
+    rule.measure(norm_of_sums(a.sumsq_));
+    if (converged(rule, iter, voting, [&] { return bc_error(E.v, S_zero) <= a.opt_.bc_tol; }, &failed)) break;
     iter++;
     const double delta = rr / nglobal + small;
     const double beta = delta / gamma;
     gamma = delta;
     for (Solver* s : m_) launch_sc_cg_axpy(1, s->gu_, T_e(s), T_p(s), T_r(s), T_w(s), beta, s->stream_, s->ucs_);   // p = r + beta p
   }
-  for (Solver* s : m_) {
-    s->in_run_ = false;
-    s->iterations_ = iter;
-    s->su_valid_ = true;
-    s->eps_stale_ = true;
-    for (int c = 0; c < 6; ++c) s->E_cur_[c] = E.v[c];
-    s->slab_materialise_eps();
-  }
-  synchronize();
-  const double dt = now_seconds() - t_start;
-  for (Solver* s : m_) s->solve_time_ += dt;
+  finish_cg_u(iter, E.v, t_start);
   return failed;
 }
 
@@ -1680,7 +1555,6 @@ bool SlabGroup::run_cg_scalar(const double* E0, double prev0) {
 bool SlabGroup::run_cg_strain(const double* E0, const double* S0, double prev0) {
   Solver& a = *m_[0];
   const double t_start = now_seconds();
-  const bool residual_est = a.opt_.error_estimator == 1;
   const double small = std::numeric_limits<double>::min();
   const double nglobal = (double)a.nglobal_;
   for (Solver* s : m_) {
@@ -1694,13 +1568,8 @@ bool SlabGroup::run_cg_strain(const double* E0, const double* S0, double prev0) 
   const bool voting = agree_on_voting();
   const bool mixed_bc = !(frobenius(a.BC_MQ_) < kEps);
   Vec6 E, Z;
-  {
-    double t1[6], t2[6], t3[6];   // calcBCMean  F:20242-20245
-    voigt_mv(a.BC_QC0_, E0, t1);
-    for (int i = 0; i < 6; ++i) t2[i] = S0[i] - t1[i];
-    voigt_mv(a.BC_M_, t2, t3);
-    for (int i = 0; i < 6; ++i) E.v[i] = E0[i] + a.opt_.bc_relax * t3[i], Z.v[i] = 0.0;
-  }
+  bc_mean(a.BC_QC0_, a.BC_M_, a.opt_.bc_relax, E0, S0, E.v);
+  for (int i = 0; i < 6; ++i) Z.v[i] = 0.0;
   // dst = operator(src): the pass works in place on eps_, so the field is copied into dst and dst takes eps_'s place
   auto apply = [&](double* Solver::*src, double* Solver::*dst) {
     for (Solver* s : m_) {
@@ -1736,11 +1605,10 @@ bool SlabGroup::run_cg_strain(const double* E0, const double* S0, double prev0) 
   }
   apply(&Solver::eps_, &Solver::cg_r_);                                          // r = -Gamma0 (C - C0) eps
   dot(0, &Solver::cg_r_, &Solver::eps_, &Solver::eps_, 0.0, kSlotMean, 1);       // r += E - eps ; r:r
-  double gamma = a.hscal_[kSlotMean] / nglobal + small;
-  const double gamma_0 = gamma;
+  StopRule rule = a.stop_rule(prev0, a.hscal_[kSlotMean] / nglobal + small);   // gamma_0 = r:r / N + tiny
+  double& gamma = rule.gamma_cur;
   for (Solver* s : m_)
     FG_HIP_CHECK(hipMemcpyAsync(s->cg_p_, s->cg_r_, 6 * (size_t)s->g_.n * sizeof(double), hipMemcpyDeviceToDevice, s->stream_));
-  double prev = prev0;
   long iter = 0;
   bool failed = false;
   for (;;) {
@@ -1748,49 +1616,10 @@ bool SlabGroup::run_cg_strain(const double* E0, const double* S0, double prev0) 
     dot(1, &Solver::cg_p_, &Solver::cg_w_, &Solver::cg_w_, 0.0, kSlotMean, 1);   // p:(p - w)
     const double alpha = gamma / (a.hscal_[kSlotMean] / nglobal + small);
     dot(2, &Solver::eps_, &Solver::cg_p_, &Solver::cg_p_, alpha, kSlotSumSq, 6);  // eps += alpha p ; norms
-    double m[6], s9 = 0.0;
-    for (int c = 0; c < 6; ++c) {
-      const double ss = a.hscal_[kSlotSumSq + c];
-      for (Solver* s : m_) s->sumsq_[c] = ss;
-      m[c] = std::sqrt(ss / nglobal);
-    }
-    for (int c = 0; c < 6; ++c) s9 += m[c] * m[c];
-    for (int c = 3; c < 6; ++c) s9 += m[c] * m[c];
-    const double cur = std::sqrt(s9);
-    double abs_err = std::fabs(prev - cur);
-    double rel_err = abs_err / (small + cur);
-    prev = cur;
-    if (residual_est) {   // update_cg(gamma, gamma0)  F:14397-14401
-      abs_err = std::sqrt(gamma);
-      rel_err = std::sqrt(gamma / gamma_0);
-    }
-    if (a.opt_.error_estimator >= 2) estimator_update(&abs_err, &rel_err);   // update_cg -> update  F:14465, F:14584
-    if (std::isnan(rel_err) || stop_requested()) {
-      failed = true;
-      break;
-    }
-    for (Solver* s : m_) s->residuals_.push_back(rel_err);
-    bool stop = false, cancelled = false;
-    for (Solver* s : m_) {
-      if (s->cb_ && s->cb_(s->cb_user_)) stop = true;
-      if (s->cancel_) cancelled = true;
-    }
-    if (voting) {
-      double v[2] = {stop ? 1.0 : 0.0, cancelled ? 1.0 : 0.0};
-      vote(v);
-      stop = v[0] != 0.0;
-      cancelled = v[1] != 0.0;
-    }
-    if (a.nranks_ > 1 && !voting) cancelled = false;
-    if (stop) break;
-    if (cancelled) {
-      failed = true;
-      break;
-    }
-    if (iter >= a.opt_.maxiter) break;
-    if (rel_err <= a.opt_.tol || abs_err <= a.opt_.abs_tol) {
-      if (bc_error(E0, S0) <= a.opt_.bc_tol) break;
-    }
+    set_sumsq(kSlotSumSq, 6);
+    rule.measure(norm9_of_sums(a.sumsq_, nglobal));
+    if (a.opt_.error_estimator >= 2) estimator_update(&rule.abs_err, &rule.rel_err);   // update_cg -> update  F:14465, F:14584
+    if (converged(rule, iter, voting, [&] { return bc_error(E0, S0) <= a.opt_.bc_tol; }, &failed)) break;
     iter++;
     dot(3, &Solver::cg_r_, &Solver::cg_p_, &Solver::cg_w_, -alpha, kSlotMean, 1);   // r -= alpha (p - w) ; r:r
     const double delta = a.hscal_[kSlotMean] / nglobal + small;

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <limits>
 #include <memory>
@@ -20,6 +21,7 @@
 #include "fg_fft.h"
 #include "fg_hostmath.h"
 #include "fg_kernels.h"
+#include "fg_stop_rule.h"
 #include "fg_transfer.h"
 
 namespace fg {
@@ -38,6 +40,11 @@ constexpr int kSlotFlag = 22;    // 2: slab driver, summed over the ranks with e
 constexpr int kSlotCg = 24;      // displacement CG: two blocks of 8 (norms of eps [6] + r:r, alternating per iteration), then p:(p-w) [8]
 constexpr int kNumSlots = 48;
 }  // namespace slots
+
+inline double now_seconds() {
+  using clk = std::chrono::steady_clock;
+  return std::chrono::duration<double>(clk::now().time_since_epoch()).count();
+}
 
 typedef int (*ConvergenceCallback)(void* user);
 typedef int (*LoadstepCallback)(void* user, int istep);
@@ -92,38 +99,6 @@ struct SolverOptions {
   int tile_plans = 1;           // tile kernels (decimal sizes): the kernels built for one plan each where the plan is in their tables
                                 // (fg_fft_smooth_plans.h) (1) or the class kernels for every plan (0); process-wide switch, same butterflies
   int stage_chunk_kb = 16384;   // pipeline stage of the staged transfers (<= 16 MB; tests shrink it)
-};
-
-// The error estimators that re-measure a mean of the strain field every iteration (create_error_estimator F:14940-14972):
-// SigmaErrorEstimator F:14514-14587 (created with _mode = 2: from its third update on, the mean of the distances to the
-// last two mean stresses), EnergyErrorEstimator F:14410-14468, NoneErrorEstimator F:14370-14378 (always 1).  The solver
-// (one GPU or the slab group) supplies the measurement; norm_2 runs over the 9 mirrored entries (fix_dim).
-struct MeanEstimator {
-  double m_prev[6] = {0, 0, 0, 0, 0, 0}, m_pp[6] = {0, 0, 0, 0, 0, 0}, w_prev = 0.0;
-  long iter = 0;
-  static double norm9_diff(const double* a, const double* b) {
-    double s = 0.0;
-    for (int c = 0; c < 6; ++c) s += (a[c] - b[c]) * (a[c] - b[c]) * (c >= 3 ? 2.0 : 1.0);
-    return std::sqrt(s);
-  }
-  void start_sigma(const double* m) {
-    for (int c = 0; c < 6; ++c) m_prev[c] = m_pp[c] = m[c];
-    iter = 0;
-  }
-  void update_sigma(const double* m, double* abs_err, double* rel_err) {
-    const double zero[6] = {0, 0, 0, 0, 0, 0};
-    *abs_err = iter > 1 ? 0.5 * (norm9_diff(m_pp, m) + norm9_diff(m_prev, m)) : norm9_diff(m_prev, m);
-    *rel_err = *abs_err / (std::numeric_limits<double>::min() + norm9_diff(m, zero));
-    for (int c = 0; c < 6; ++c) m_pp[c] = m_prev[c], m_prev[c] = m[c];
-    ++iter;
-  }
-  void start_energy(double w) { w_prev = w, iter = 0; }
-  void update_energy(double w, double* abs_err, double* rel_err) {
-    *abs_err = std::fabs(w_prev - w);
-    *rel_err = *abs_err / (std::numeric_limits<double>::min() + std::fabs(w));
-    w_prev = w;
-    ++iter;
-  }
 };
 
 enum Stage {
@@ -241,6 +216,12 @@ class Solver {
   void estimator_begin(bool fresh);
   void estimator_update(double* abs_err, double* rel_err);
   MeanEstimator est_;
+  StopRule stop_rule(double prev0, double gamma_0 = 0.0) const {
+    return StopRule(opt_.tol, opt_.abs_tol, opt_.maxiter, opt_.error_estimator, prev0, gamma_0);
+  }
+  // _converged on the rule's measurement with this solver's hooks (fg_stop_rule.h); true: the loop ends, *failed says how
+  template <class BcOk>
+  bool converged(const StopRule& rule, long iter, BcOk bc_ok, bool* failed);
   bool run_cg(const double* E0, const double* S0, double prev0);
   bool run_cg_scalar(const double* E0, double prev0);  // heat / porous: CG in potential space
   bool run_cg_u(const double* E0, double prev0);      // the same CG carried in displacement space (Voigt, prescribed mean strains)

@@ -1,7 +1,6 @@
 #include "fg_solver.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <complex>
 #include <cstdio>
@@ -54,11 +53,6 @@ __global__ void k_bc_adjust_sums(double* sums, Mat36 B, double factor) {
     o[c] = s[c] - factor * t;
   }
   for (int c = 0; c < 6; ++c) sums[c] = o[c];
-}
-
-double now_seconds() {
-  using clk = std::chrono::steady_clock;
-  return std::chrono::duration<double>(clk::now().time_since_epoch()).count();
 }
 }  // namespace
 
@@ -1388,6 +1382,21 @@ double Solver::bc_error(const double* E_cur, const double* S_cur) {
 }
 
 // ------------------------------------------------------------------ the solver loop
+// The lone solver's side of the stop rule (fg_stop_rule.h): a stop request is fg_cancel, the callback is its own.
+template <class BcOk>
+bool Solver::converged(const StopRule& rule, long iter, BcOk bc_ok, bool* failed) {
+  auto record = [&](double rel_err) { residuals_.push_back(rel_err); };
+  auto poll = [&] {
+    StopPoll p;
+    p.stop = cb_ && cb_(cb_user_);
+    p.cancelled = cancel_;   // cancelled from inside the callback
+    return p;
+  };
+  const StopDecision d = rule.decide(iter, stop_hooks([&] { return cancel_.load(); }, record, poll, bc_ok));
+  *failed = d == StopDecision::kFail;
+  return d != StopDecision::kContinue;
+}
+
 // run F:21247-21398 -> runLoadsteppingSolver (single load step, t = 1) F:21584-21685
 // -> runSolver -> runBasic F:21716-21805 with the stop rule of _converged F:21177-21244.
 bool Solver::run(const double* E6, const double* S6) {
@@ -1540,7 +1549,7 @@ bool Solver::run_one_step(const double* E0, const double* S0) {
   }
   in_run_ = true;
 
-  double prev = prev0;
+  StopRule rule = stop_rule(prev0);
   long iter = 1;
   // a continuing load step in the displacement loop: the state is u of the previous step (eps = E_old + sym grad u); one
   // unrecorded pass turns it into u' with eps' = E_new + sym grad u' -- the field the reference's first iteration of the
@@ -1550,17 +1559,11 @@ bool Solver::run_one_step(const double* E0, const double* S0) {
   double E[6];
   for (int i = 0; i < 6; ++i) E[i] = E0[i];
   bool failed = false;
-  const double small = std::numeric_limits<double>::min();
 
   for (;;) {
     if (update_ref) {
       calc_ref_material();
-      // calcBCMean  F:20242-20245
-      double t1[6], t2[6], t3[6];
-      voigt_mv(BC_QC0_, E0, t1);
-      for (int i = 0; i < 6; ++i) t2[i] = S0[i] - t1[i];
-      voigt_mv(BC_M_, t2, t3);
-      for (int i = 0; i < 6; ++i) E[i] = E0[i] + opt_.bc_relax * t3[i];
+      bc_mean(BC_QC0_, BC_M_, opt_.bc_relax, E0, S0, E);
       update_ref = false;
     }
     bool pending_back = false;
@@ -1611,40 +1614,10 @@ bool Solver::run_one_step(const double* E0, const double* S0) {
       for (int c = 0; c < 6; ++c) E_next_[c] = E[c] - t1[c];   // alpha = -1  (F:20575)
     }
 
-    // component_norm + fix_dim + norm_2 over 9 mirrored entries  F:10127-10138, F:14600-14609, F:14627
-    double m[6], s9 = 0.0;
-    for (int c = 0; c < 6; ++c) {
-      sumsq_[c] = hscal_[kSlotSumSq + c];
-      m[c] = std::sqrt(sumsq_[c] / (double)nglobal_);
-    }
-    for (int c = 0; c < 6; ++c) s9 += m[c] * m[c];
-    for (int c = 3; c < 6; ++c) s9 += m[c] * m[c];
-    const double cur = std::sqrt(s9);
-    double abs_err = std::fabs(prev - cur);
-    double rel_err = abs_err / (small + cur);
-    prev = cur;
-    if (opt_.error_estimator >= 2) estimator_update(&abs_err, &rel_err);   // sigma / energy / none: F:14410-14587
-
-    // _converged  F:21177-21244
-    if (std::isnan(rel_err)) {
-      failed = true;  // "NaN detected in solution. Aborting."
-      break;
-    }
-    if (cancel_) {
-      failed = true;
-      break;
-    }
-    residuals_.push_back(rel_err);
-    if (cb_ && cb_(cb_user_)) break;
-    if (cancel_) {
-      failed = true;
-      break;
-    }
-    if (iter >= opt_.maxiter) break;
-    if (rel_err <= opt_.tol || abs_err <= opt_.abs_tol) {
-      const double bc_err = bc_error(E0, S0);
-      if (bc_err <= opt_.bc_tol) break;
-    }
+    for (int c = 0; c < 6; ++c) sumsq_[c] = hscal_[kSlotSumSq + c];
+    rule.measure(norm9_of_sums(sumsq_, (double)nglobal_));
+    if (opt_.error_estimator >= 2) estimator_update(&rule.abs_err, &rule.rel_err);   // sigma / energy / none: F:14410-14587
+    if (converged(rule, iter, [&] { return bc_error(E0, S0) <= opt_.bc_tol; }, &failed)) break;
     if (pending_back) adopt_back();
     iter++;
   }
@@ -1748,14 +1721,14 @@ bool Solver::run_cg_u(const double* E0, double prev0) {
   FG_HIP_CHECK(hipMemcpyAsync(u_r, fu_alt_, f3, hipMemcpyDeviceToDevice, stream_));
   FG_HIP_CHECK(hipMemcpyAsync(u_p, fu_alt_, f3, hipMemcpyDeviceToDevice, stream_));   // p = r
   launch_cgu_dot(1, g_, ptrs3(fu_), ptrs3(u_r), E, partial_, dscal_ + blk[0], stream_);   // gamma_0 = r:r / N + tiny
-  double prev = prev0;  // estimator constructed on the field the step started from
-  const bool residual_est = opt_.error_estimator == 1;
-  double gamma_cur = 0.0, gamma_0 = 0.0;   // r:r / N + tiny of the current iteration / of the start (residual estimator)
-  if (residual_est) {
+  double gamma_0 = 0.0;   // r:r / N + tiny at the start: only the residual estimator reads it
+  if (opt_.error_estimator == 1) {
     FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotCg + 6, dscal_ + blk[0] + 6, sizeof(double), hipMemcpyDeviceToHost, stream_));
     FG_HIP_CHECK(hipStreamSynchronize(stream_));
-    gamma_cur = gamma_0 = hscal_[kSlotCg + 6] / (double)nglobal_ + small;
+    gamma_0 = hscal_[kSlotCg + 6] / (double)nglobal_ + small;
   }
+  StopRule rule = stop_rule(prev0, gamma_0);
+  const double S_zero[6] = {0, 0, 0, 0, 0, 0};
   long iter = 0;
   bool failed = false;
   bool applied = false;   // u_w = operator(u_p) of the coming iteration is already enqueued
@@ -1800,37 +1773,10 @@ bool Solver::run_cg_u(const double* E0, double prev0) {
     u_valid_ = true;
     eps_stale_ = true;
     for (int c = 0; c < 6; ++c) E_cur_[c] = E.v[c];
-    double m[6], s9 = 0.0;
-    for (int c = 0; c < 6; ++c) {
-      sumsq_[c] = hscal_[kSlotCg + c];
-      m[c] = std::sqrt(sumsq_[c] / (double)nglobal_);
-    }
-    for (int c = 0; c < 6; ++c) s9 += m[c] * m[c];
-    for (int c = 3; c < 6; ++c) s9 += m[c] * m[c];
-    const double curn = std::sqrt(s9);
-    double abs_err = std::fabs(prev - curn);
-    double rel_err = abs_err / (small + curn);
-    prev = curn;
-    if (residual_est) {   // update_cg(gamma, gamma0)  F:14397-14401 with the gamma this iteration started from
-      abs_err = std::sqrt(gamma_cur);
-      rel_err = std::sqrt(gamma_cur / gamma_0);
-      gamma_cur = hscal_[kSlotCg + 6] / (double)nglobal_ + small;   // delta = r:r after the update: the next gamma
-    }
-    if (std::isnan(rel_err) || cancel_) {  // _converged  F:21177-21244
-      failed = true;
-      break;
-    }
-    residuals_.push_back(rel_err);
-    if (cb_ && cb_(cb_user_)) break;
-    if (cancel_) {
-      failed = true;
-      break;
-    }
-    if (iter >= opt_.maxiter) break;
-    if (rel_err <= opt_.tol || abs_err <= opt_.abs_tol) {
-      double S0[6] = {0, 0, 0, 0, 0, 0};
-      if (bc_error(E0, S0) <= opt_.bc_tol) break;
-    }
+    for (int c = 0; c < 6; ++c) sumsq_[c] = hscal_[kSlotCg + c];
+    // delta = r:r after the update is the next gamma
+    rule.measure(norm9_of_sums(sumsq_, (double)nglobal_), hscal_[kSlotCg + 6] / (double)nglobal_ + small);
+    if (converged(rule, iter, [&] { return bc_error(E0, S_zero) <= opt_.bc_tol; }, &failed)) break;
     iter++;
     if (!applied) {   // p = r + beta p
       if (fused_dir) {
@@ -1868,6 +1814,21 @@ bool Solver::run_cg_scalar(const double* E0, double prev0) {
   if (opt_.update_ref) calc_ref_material();
   Vec6 E, Z;
   for (int i = 0; i < 6; ++i) E.v[i] = i < 3 ? E0[i] : 0.0, Z.v[i] = 0.0;
+  const double S_zero[6] = {0, 0, 0, 0, 0, 0};
+  auto set_state = [&] {   // for accessors called from the callback / bc_error: g = E + grad T_e, T_e = fu_'s first component
+    u_valid_ = true;
+    eps_stale_ = true;
+    for (int c = 0; c < 6; ++c) E_cur_[c] = E.v[c];
+  };
+  auto finish = [&](long iter) {
+    in_run_ = false;
+    cg_u_active_ = false;
+    iterations_ = iter;
+    set_state();
+    ensure_eps();
+    FG_HIP_CHECK(hipStreamSynchronize(stream_));
+    solve_time_ += now_seconds() - t_start;
+  };
   auto fetch = [&](int slot, int n) {
     FG_HIP_CHECK(hipMemcpyAsync(hscal_ + slot, dscal_ + slot, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
     check_device_error("cg");
@@ -1906,9 +1867,7 @@ bool Solver::run_cg_scalar(const double* E0, double prev0) {
     FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotCg + 6, dscal_ + blk[0] + 6, sizeof(double), hipMemcpyDeviceToHost, stream_));
     FG_HIP_CHECK(hipStreamSynchronize(stream_));
     check_device_error("cg");
-    double gamma_cur = hscal_[kSlotCg + 6] / nvox + small;
-    const double gamma_0 = gamma_cur;
-    double prev = prev0;
+    StopRule rule = stop_rule(prev0, hscal_[kSlotCg + 6] / nvox + small);
     long iter = 0;
     bool failed = false, applied = false;
     for (;;) {
@@ -1929,58 +1888,29 @@ bool Solver::run_cg_scalar(const double* E0, double prev0) {
       }
       FG_HIP_CHECK(hipEventSynchronize(ev_copy_));
       if (*herr_ != 0) check_device_error("cg");
-      double s3 = 0.0;
-      for (int c = 0; c < 6; ++c) {
-        sumsq_[c] = c < 3 ? hscal_[kSlotCg + c] : 0.0;
-        const double m = std::sqrt(sumsq_[c] / nvox);
-        s3 += m * m;
-      }
-      const double curn = std::sqrt(s3);
-      double abs_err = std::fabs(prev - curn);
-      double rel_err = abs_err / (small + curn);
-      prev = curn;
-      if (opt_.error_estimator == 1) {   // update_cg(gamma, gamma0)  F:14397-14401 with the gamma this iteration started from
-        abs_err = std::sqrt(gamma_cur);
-        rel_err = std::sqrt(gamma_cur / gamma_0);
-      }
-      gamma_cur = hscal_[kSlotCg + 6] / nvox + small;   // delta = r.r after the update: the next gamma
-      if (std::isnan(rel_err) || cancel_) {
-        failed = true;
-        break;
-      }
-      residuals_.push_back(rel_err);
-      if (iter >= opt_.maxiter) break;
-      if (rel_err <= opt_.tol || abs_err <= opt_.abs_tol) {
+      for (int c = 0; c < 6; ++c) sumsq_[c] = c < 3 ? hscal_[kSlotCg + c] : 0.0;
+      // delta = r.r after the update is the next gamma
+      rule.measure(norm3_of_sums(sumsq_, nvox), hscal_[kSlotCg + 6] / nvox + small);
+      auto bc_ok = [&] {
         // bc_error reads the strain of the current iterate: fu_'s first component must be it
         if (e_cur != fu_) {
           FG_HIP_CHECK(hipMemcpyAsync(fu_, e_cur, f1, hipMemcpyDeviceToDevice, stream_));
           std::swap(e_cur, e_alt);
         }
-        u_valid_ = true;
-        eps_stale_ = true;
-        for (int c = 0; c < 6; ++c) E_cur_[c] = E.v[c];
-        double S0[6] = {0, 0, 0, 0, 0, 0};
-        if (bc_error(E.v, S0) <= opt_.bc_tol) break;
-      }
+        set_state();
+        return bc_error(E.v, S_zero) <= opt_.bc_tol;
+      };
+      if (converged(rule, iter, bc_ok, &failed)) break;
       iter++;
     }
     if (e_cur != fu_) FG_HIP_CHECK(hipMemcpyAsync(fu_, e_cur, f1, hipMemcpyDeviceToDevice, stream_));
-    in_run_ = false;
-    cg_u_active_ = false;
-    iterations_ = iter;
-    u_valid_ = true;
-    eps_stale_ = true;
-    for (int c = 0; c < 6; ++c) E_cur_[c] = E.v[c];
-    ensure_eps();
-    FG_HIP_CHECK(hipStreamSynchronize(stream_));
-    solve_time_ += now_seconds() - t_start;
+    finish(iter);
     return failed;
   }
   launch_sc_cg_dot(1, g_, fu_, T_r, E, partial_, dscal_ + kSlotSumSq, stream_);
   fetch(kSlotSumSq, 7);
-  double gamma = hscal_[kSlotSumSq + 6] / (double)nglobal_ + small;
-  const double gamma_0 = gamma;
-  double prev = prev0;
+  StopRule rule = stop_rule(prev0, hscal_[kSlotSumSq + 6] / (double)nglobal_ + small);
+  double& gamma = rule.gamma_cur;
   long iter = 0;
   bool failed = false;
   for (;;) {
@@ -1993,53 +1923,17 @@ bool Solver::run_cg_scalar(const double* E0, double prev0) {
     launch_sc_cg_dot(1, g_, fu_, T_r, E, partial_, dscal_ + kSlotSumSq, stream_);
     fetch(kSlotSumSq, 7);
     const double rr = hscal_[kSlotSumSq + 6];
-    u_valid_ = true;
-    eps_stale_ = true;
-    for (int c = 0; c < 6; ++c) E_cur_[c] = E.v[c];
-    double s3 = 0.0;
-    for (int c = 0; c < 6; ++c) {
-      sumsq_[c] = c < 3 ? hscal_[kSlotSumSq + c] : 0.0;
-      const double m = std::sqrt(sumsq_[c] / (double)nglobal_);
-      s3 += m * m;
-    }
-    const double cur = std::sqrt(s3);
-    double abs_err = std::fabs(prev - cur);
-    double rel_err = abs_err / (small + cur);
-    prev = cur;
-    if (opt_.error_estimator == 1) {   // update_cg(gamma, gamma0)  F:14397-14401
-      abs_err = std::sqrt(gamma);
-      rel_err = std::sqrt(gamma / gamma_0);
-    }
-    if (std::isnan(rel_err) || cancel_) {
-      failed = true;
-      break;
-    }
-    residuals_.push_back(rel_err);
-    if (cb_ && cb_(cb_user_)) break;
-    if (cancel_) {
-      failed = true;
-      break;
-    }
-    if (iter >= opt_.maxiter) break;
-    if (rel_err <= opt_.tol || abs_err <= opt_.abs_tol) {
-      double S0[6] = {0, 0, 0, 0, 0, 0};
-      if (bc_error(E.v, S0) <= opt_.bc_tol) break;
-    }
+    set_state();
+    for (int c = 0; c < 6; ++c) sumsq_[c] = c < 3 ? hscal_[kSlotSumSq + c] : 0.0;
+    rule.measure(norm3_of_sums(sumsq_, (double)nglobal_));
+    if (converged(rule, iter, [&] { return bc_error(E.v, S_zero) <= opt_.bc_tol; }, &failed)) break;
     iter++;
     const double delta = rr / (double)nglobal_ + small;
     const double beta = delta / gamma;
     gamma = delta;
     launch_sc_cg_axpy(1, g_, fu_, T_p, T_r, fu_alt_, beta, stream_);
   }
-  in_run_ = false;
-  cg_u_active_ = false;
-  iterations_ = iter;
-  u_valid_ = true;
-  eps_stale_ = true;
-  for (int c = 0; c < 6; ++c) E_cur_[c] = E.v[c];
-  ensure_eps();
-  FG_HIP_CHECK(hipStreamSynchronize(stream_));
-  solve_time_ += now_seconds() - t_start;
+  finish(iter);
   return failed;
 }
 
@@ -2058,14 +1952,15 @@ bool Solver::run_cg(const double* E0, const double* S0, double prev0) {
   const double small = std::numeric_limits<double>::min();
   if (opt_.update_ref) calc_ref_material();
   Vec6 E, Z;
-  {
-    double t1[6], t2[6], t3[6];  // calcBCMean  F:20242-20245
-    voigt_mv(BC_QC0_, E0, t1);
-    for (int i = 0; i < 6; ++i) t2[i] = S0[i] - t1[i];
-    voigt_mv(BC_M_, t2, t3);
-    for (int i = 0; i < 6; ++i) E.v[i] = E0[i] + opt_.bc_relax * t3[i], Z.v[i] = 0.0;
-  }
-  double prev = prev0;  // estimator constructed on the field the step started from
+  bc_mean(BC_QC0_, BC_M_, opt_.bc_relax, E0, S0, E.v);
+  for (int i = 0; i < 6; ++i) Z.v[i] = 0.0;
+  auto bc_ok = [&] { return bc_error(E0, S0) <= opt_.bc_tol; };
+  auto finish = [&](long iter) {
+    in_run_ = false;
+    iterations_ = iter;
+    FG_HIP_CHECK(hipStreamSynchronize(stream_));
+    solve_time_ += now_seconds() - t_start;
+  };
   auto fetch = [&](int slot, int n) {
     FG_HIP_CHECK(hipMemcpyAsync(hscal_ + slot, dscal_ + slot, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
     check_device_error("cg");
@@ -2075,8 +1970,8 @@ bool Solver::run_cg(const double* E0, const double* S0, double prev0) {
   basic_scheme(Z.v, eps_, cg_r_);                                                  // r = -Gamma0 (C - C0) eps
   launch_cg(0, g_, r, e, e, E, 0.0, partial_, dscal_ + kSlotMean, stream_);        // r += E - eps ; r:r
   fetch(kSlotMean, 1);
-  double gamma = hscal_[kSlotMean] / (double)nglobal_ + small;
-  const double gamma_0 = gamma;
+  StopRule rule = stop_rule(prev0, hscal_[kSlotMean] / (double)nglobal_ + small);   // gamma_0 = r:r / N + tiny
+  double& gamma = rule.gamma_cur;
   FG_HIP_CHECK(hipMemcpyAsync(cg_p_, cg_r_, f6, hipMemcpyDeviceToDevice, stream_));  // p = r
   // Round 4 (option cg_fused): the CG scalars on the device, the updates of eps and r as ONE sweep with their norms, the next
   // direction and operator application enqueued before the host waits for the seven sums of the stop rule -- one host
@@ -2085,7 +1980,6 @@ bool Solver::run_cg(const double* E0, const double* S0, double prev0) {
     const int blk[2] = {kSlotCg, kSlotCg + 8}, s0 = kSlotCg + 16;
     const double nvox = (double)nglobal_;
     FG_HIP_CHECK(hipMemcpyAsync(dscal_ + blk[0] + 6, dscal_ + kSlotMean, sizeof(double), hipMemcpyDeviceToDevice, stream_));   // gamma_0
-    double gamma_cur = gamma;
     long iter = 0;
     bool failed = false, applied = false;
     for (;;) {
@@ -2105,44 +1999,14 @@ bool Solver::run_cg(const double* E0, const double* S0, double prev0) {
       }
       FG_HIP_CHECK(hipEventSynchronize(ev_copy_));
       if (*herr_ != 0) check_device_error("cg");
-      double m[6], s9 = 0.0;
-      for (int c = 0; c < 6; ++c) {
-        sumsq_[c] = hscal_[kSlotCg + c];
-        m[c] = std::sqrt(sumsq_[c] / nvox);
-      }
-      for (int c = 0; c < 6; ++c) s9 += m[c] * m[c];
-      for (int c = 3; c < 6; ++c) s9 += m[c] * m[c];
-      const double curn = std::sqrt(s9);
-      double abs_err = std::fabs(prev - curn);
-      double rel_err = abs_err / (small + curn);
-      prev = curn;
-      if (opt_.error_estimator == 1) {   // update_cg(gamma, gamma0)  F:14397-14401 with the gamma this iteration started from
-        abs_err = std::sqrt(gamma_cur);
-        rel_err = std::sqrt(gamma_cur / gamma_0);
-      }
-      gamma_cur = hscal_[kSlotCg + 6] / nvox + small;
-      if (opt_.error_estimator >= 2) estimator_update(&abs_err, &rel_err);   // update_cg -> update  F:14465, F:14584
-      if (std::isnan(rel_err) || cancel_) {  // _converged  F:21177-21244
-        failed = true;
-        break;
-      }
-      residuals_.push_back(rel_err);
-      if (cb_ && cb_(cb_user_)) break;
-      if (cancel_) {
-        failed = true;
-        break;
-      }
-      if (iter >= opt_.maxiter) break;
-      if (rel_err <= opt_.tol || abs_err <= opt_.abs_tol) {
-        if (bc_error(E0, S0) <= opt_.bc_tol) break;
-      }
+      for (int c = 0; c < 6; ++c) sumsq_[c] = hscal_[kSlotCg + c];
+      rule.measure(norm9_of_sums(sumsq_, nvox), hscal_[kSlotCg + 6] / nvox + small);   // r:r after the update: the next gamma
+      if (opt_.error_estimator >= 2) estimator_update(&rule.abs_err, &rule.rel_err);   // update_cg -> update  F:14465, F:14584
+      if (converged(rule, iter, bc_ok, &failed)) break;
       iter++;
       if (!applied) launch_cg_dev(6, g_, e, r, p, w, dscal_, blk[nxt] + 6, blk[cur] + 6, nvox, small, partial_, nullptr, stream_);
     }
-    in_run_ = false;
-    iterations_ = iter;
-    FG_HIP_CHECK(hipStreamSynchronize(stream_));
-    solve_time_ += now_seconds() - t_start;
+    finish(iter);
     return failed;
   }
   long iter = 0;
@@ -2155,36 +2019,10 @@ bool Solver::run_cg(const double* E0, const double* S0, double prev0) {
     alpha = gamma / alpha;
     launch_cg(2, g_, e, p, p, E, alpha, partial_, dscal_ + kSlotSumSq, stream_);   // eps += alpha p ; norms
     fetch(kSlotSumSq, 6);
-    double m[6], s9 = 0.0;
-    for (int c = 0; c < 6; ++c) {
-      sumsq_[c] = hscal_[kSlotSumSq + c];
-      m[c] = std::sqrt(sumsq_[c] / (double)nglobal_);
-    }
-    for (int c = 0; c < 6; ++c) s9 += m[c] * m[c];
-    for (int c = 3; c < 6; ++c) s9 += m[c] * m[c];
-    const double cur = std::sqrt(s9);
-    double abs_err = std::fabs(prev - cur);
-    double rel_err = abs_err / (small + cur);
-    prev = cur;
-    if (opt_.error_estimator == 1) {   // update_cg(gamma, gamma0)  F:14397-14401
-      abs_err = std::sqrt(gamma);
-      rel_err = std::sqrt(gamma / gamma_0);
-    }
-    if (opt_.error_estimator >= 2) estimator_update(&abs_err, &rel_err);   // update_cg -> update  F:14465, F:14584
-    if (std::isnan(rel_err) || cancel_) {  // _converged  F:21177-21244
-      failed = true;
-      break;
-    }
-    residuals_.push_back(rel_err);
-    if (cb_ && cb_(cb_user_)) break;
-    if (cancel_) {
-      failed = true;
-      break;
-    }
-    if (iter >= opt_.maxiter) break;
-    if (rel_err <= opt_.tol || abs_err <= opt_.abs_tol) {
-      if (bc_error(E0, S0) <= opt_.bc_tol) break;
-    }
+    for (int c = 0; c < 6; ++c) sumsq_[c] = hscal_[kSlotSumSq + c];
+    rule.measure(norm9_of_sums(sumsq_, (double)nglobal_));
+    if (opt_.error_estimator >= 2) estimator_update(&rule.abs_err, &rule.rel_err);   // update_cg -> update  F:14465, F:14584
+    if (converged(rule, iter, bc_ok, &failed)) break;
     iter++;
     launch_cg(3, g_, r, p, w, E, -alpha, partial_, dscal_ + kSlotMean, stream_);   // r -= alpha (p - w) ; r:r
     fetch(kSlotMean, 1);
@@ -2193,10 +2031,7 @@ bool Solver::run_cg(const double* E0, const double* S0, double prev0) {
     gamma = delta;
     launch_cg(4, g_, p, r, r, E, beta, partial_, dscal_ + kSlotMean, stream_);     // p = r + beta p
   }
-  in_run_ = false;
-  iterations_ = iter;
-  FG_HIP_CHECK(hipStreamSynchronize(stream_));
-  solve_time_ += now_seconds() - t_start;
+  finish(iter);
   return failed;
 }
 

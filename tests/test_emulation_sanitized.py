@@ -23,7 +23,8 @@ def test_emulation_suites_under_asan_ubsan():
     env = dict(os.environ, FG_EMU_SANITIZE="1", LD_PRELOAD=asan,
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     out = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-p", "no:cacheprovider",
-                          os.path.join(ROOT, "tests", "test_fft_emulation.py"), os.path.join(ROOT, "tests", "test_plane_cut.py")],
+                          os.path.join(ROOT, "tests", "test_fft_emulation.py"), os.path.join(ROOT, "tests", "test_plane_cut.py"),
+                          os.path.join(ROOT, "tests", "test_stop_rule.py")],
                          env=env, capture_output=True, text=True, cwd=ROOT)
     tail = out.stdout[-3000:] + out.stderr[-3000:]
     assert out.returncode == 0, tail
