@@ -247,9 +247,10 @@ int fg_set_option_i(fg_solver* s, const char* key, long value) {
       v.invalidate_moduli();   // the precomputed effective moduli depend on the mode's phase table
     }
     else if (k == "gamma_scheme") {
-      if (value < 0 || value > 2)
-        throw std::runtime_error("gamma_scheme must be 0 (staggered), 1 (collocated) or 2 (full_staggered: doubly fine grid)");
+      if (value < 0 || value > 3)
+        throw std::runtime_error("gamma_scheme must be 0 (staggered), 1 (collocated), 2 (full_staggered: doubly fine grid) or 3 (willot)");
       if (value == 2 && v.is_slab()) throw std::runtime_error("full_staggered is not available on slab-decomposed solvers");
+      if (value == 3 && v.is_slab()) throw std::runtime_error("gamma_scheme willot is not available on slab-decomposed solvers");
       o.gamma_scheme = (int)value;
     }
     else if (k == "u_tile") {

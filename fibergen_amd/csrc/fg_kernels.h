@@ -37,6 +37,13 @@ struct XiTables {
   const double* xi[3];
 };
 
+// willot scheme: t_a[m] = tan(q_a / 2) / (4 w_a), e_a[m] = 1 + e^{i q_a} per axis, built on the host (willot_axis_table in
+// fg_willot_math.h); the z tables hold nzc entries
+struct WillotTables {
+  const double* t[3];
+  const cplx* e[3];
+};
+
 struct G0Layout {
   int transposed;  // 0: [nx][ny][nzc]   1: y-slab [nyl][nx][nzc]
   int nyl, jj0;
@@ -139,6 +146,10 @@ void launch_g0(const Grid& g, const FieldPtrs<3>& fh, const G0Tables& tb, double
                hipStream_t s);
 void launch_gamma_collocated(const Grid& g, const FieldPtrs<6>& th, const XiTables& xt, double c10, double c20, double beta,
                              const Vec6& E, hipStream_t s);
+// gamma_scheme willot (fg_kernels_willot.hip): eta_hat = alpha Gamma_hat : tau_hat + beta tau_hat in place, lambda_0 = infinity
+// selects the Stokes form; zero frequency = E (+ mcoef * mean6[c] for a device-resident mean6, else mean6 = nullptr)
+void launch_gamma_willot(const Grid& g, const FieldPtrs<6>& th, const WillotTables& wt, double mu_0, double lambda_0,
+                         double alpha, double beta, const Vec6& E, const double* mean6, double mcoef, hipStream_t s);
 void launch_eps_norm(const Grid& g, const FieldPtrs<3>& u, const FieldPtrs<6>& eps, const Vec6& E, const Vec6& R,
                      bool add_R, double* partial, double* sumsq6, const XHalo& h, hipStream_t s);
 // viscosity: eta = (E - coef tau_sum / nvox) + sym grad u + coef tau, sums of squares (tau_sum on the device)

@@ -1373,13 +1373,6 @@ __global__ __launch_bounds__(kBlock) void k_stress_const(long n2, double two_mu,
   }
 }
 
-int grid_for(long nwork, int max_blocks) {
-  long b = (nwork + kBlock - 1) / kBlock;
-  if (b > max_blocks) b = max_blocks;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 }  // namespace
 
 namespace {

@@ -11,6 +11,14 @@ namespace {
 
 constexpr int kBlock = 256;
 
+// blocks of kBlock threads for a grid-stride loop over nwork items, at most max_blocks
+inline int grid_for(long nwork, int max_blocks) {
+  long b = (nwork + kBlock - 1) / kBlock;
+  if (b > max_blocks) b = max_blocks;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
 __device__ __forceinline__ double2 ld2(const double* p, long i) { return *reinterpret_cast<const double2*>(p + i); }
 __device__ __forceinline__ void st2(double* p, long i, double2 v) { *reinterpret_cast<double2*>(p + i) = v; }
 

@@ -67,7 +67,9 @@ struct SolverOptions {
                                 // 2 = viscosity (dual Stokes scheme: DeltaOperatorStaggered F:20422-20460, 6 components)
   int gamma_scheme = 0;         // 0 = staggered (GammaOperatorStaggered F:20288), 1 = collocated (GammaOperatorCollocated F:20302),
                                 // 2 = full_staggered / half_staggered: the staggered operator with the material evaluated on
-                                // the doubly fine grid (use_dfg F:14894-14897), in coarse form (fg_kernels.h)
+                                // the doubly fine grid (use_dfg F:14894-14897), in coarse form (fg_kernels.h),
+                                // 3 = willot: Willot's rotated scheme (GammaOperatorWillotR F:20322, DeltaOperatorWillotR F:20380;
+                                // elasticity and viscosity, whole grids; the lambda_0 rule of fg_willot_math.h)
   int loadstep_extrapolation_order = 0;   // 0 = none, 1 = linear, ... (F:14696; method "polynomial" F:21468-21514)
   int slab_interleave = -1;     // -1: where available; 0: one message per peer and component
   int error_estimator = 0;      // 0 = epsilon (EpsilonErrorEstimator F:14591-14637), 1 = residual (ResidualErrorEstimator
@@ -230,6 +232,10 @@ class Solver {
   FieldPtrs<2> effective_moduli();      // per-voxel sums of the phase moduli for the fast kernels (allocated on first use)
   bool dfg() const { return opt_.gamma_scheme == 2; }
   void dfg_check() const;               // throws for the combinations full_staggered does not cover
+  bool willot() const { return opt_.gamma_scheme == 3; }
+  void willot_check() const;            // throws for the combinations the willot scheme does not cover
+  WillotTables willot_tables();         // the per-axis tables of the scheme (built on first use)
+  void willot_scheme(const double* E6, double* src, double* dst, const FieldPtrs<kMaxPhases>& phi, const FieldPtrs<3>& nrm);
   FieldPtrs<5> dfg_moduli();            // gamma_scheme 2: A_n, B_n, A_23, A_13, A_12 (once per geometry)
   // calcStress into tau_: the phase fractions, or under gamma_scheme 2 the five moduli
   void stress_to_tau(const StressParams& sp, double* src, const FieldPtrs<kMaxPhases>& phi, const FieldPtrs<3>& nrm);
@@ -376,6 +382,8 @@ class Solver {
   double* g0_kpm_[3] = {nullptr, nullptr, nullptr};
   cplx* g0_kp_[3] = {nullptr, nullptr, nullptr};
   double* xi_[3] = {nullptr, nullptr, nullptr};  // collocated scheme: signed frequency / cell size per axis
+  double* wil_t_[3] = {nullptr, nullptr, nullptr};   // willot scheme: tan(q / 2) / (4 w) per axis (willot_axis_table)
+  cplx* wil_e_[3] = {nullptr, nullptr, nullptr};     // willot scheme: 1 + e^{iq} per axis
 
   hostmath::Mat6 BC_P_, BC_Q_, BC_M_, BC_MQ_, BC_QC0_;
   double F00_[6];

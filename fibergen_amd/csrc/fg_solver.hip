@@ -11,6 +11,7 @@
 
 #include "fg_hip_util.h"
 #include "fg_slab.h"
+#include "fg_willot_math.h"
 
 namespace fg {
 
@@ -198,6 +199,8 @@ void Solver::release() {
     if (g0_kpm_[a]) (void)hipFree(g0_kpm_[a]);
     if (g0_kp_[a]) (void)hipFree(g0_kp_[a]);
     if (xi_[a]) (void)hipFree(xi_[a]);
+    if (wil_t_[a]) (void)hipFree(wil_t_[a]);
+    if (wil_e_[a]) (void)hipFree(wil_e_[a]);
   }
   for (hipEvent_t e : {ev_[0], ev_[1], ev_copy_})
     if (e) (void)hipEventDestroy(e);
@@ -262,6 +265,7 @@ void Solver::set_phase_field(int p, const double* phi_host) {
 
 void Solver::set_phase_field_fine(int p, const double* fine_host) {
   if (p < 0 || p >= pt_.n) throw std::runtime_error("phase index out of range");
+  if (willot()) throw std::runtime_error("gamma_scheme willot takes phase fields on the solver's grid (a fine phase field needs full_staggered)");
   if (!dfg()) throw std::runtime_error("a phase field on the doubly fine grid needs gamma_scheme full_staggered (2)");
   if (nranks_ != 1 || slab_layout_) throw std::runtime_error("full_staggered is not available on slab-decomposed solvers");
   FG_HIP_CHECK(hipSetDevice(device_));
@@ -543,6 +547,7 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
   if (pt_.n < 1) throw std::runtime_error("No materials specified");
   if (opt_.mixing == kMixLaminate && !normals_) throw std::runtime_error("laminate mixing needs interface normals");
   if (dfg()) dfg_check();
+  if (willot()) willot_check();
   FieldPtrs<kMaxPhases> phi;
   for (int q = 0; q < kMaxPhases; ++q) phi.p[q] = q < pt_.n ? phi_ + (long)q * g_.n : nullptr;
   FieldPtrs<3> nrm;
@@ -561,9 +566,13 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
     // DeltaOperatorStaggered  F:20422-20460 (dual Stokes scheme), called with alpha = -1 by basicScheme:
     //   m = 1/(4 mu0);  adj = E - 2 alpha m <tau>;  eta = GammaStaggered(adj; mu = -1/(4 m), lambda = inf)(tau)
     //   + 2 alpha m tau.   lambda0 = inf makes c20 = c10 in G0OperatorFourierStaggered (F:19749-19755).
-    if (opt_.gamma_scheme == 1) throw std::runtime_error("viscosity mode supports gamma_scheme staggered and full_staggered only");
+    if (opt_.gamma_scheme == 1) throw std::runtime_error("viscosity mode supports gamma_scheme staggered, full_staggered and willot only");
     if (opt_.mixing != kMixVoigt) throw std::runtime_error("viscosity mode supports Voigt mixing only");
     if (opt_.bc_relax != 1.0) throw std::runtime_error("viscosity mode supports bc_relax = 1 only");
+    if (willot()) {
+      willot_scheme(E6, src, dst, phi, nrm);
+      return;
+    }
     const bool mixed_bc = !(frobenius(BC_MQ_) < kEps);   // initBCProjector / applyBCProjector inside GammaOperatorStaggered
     const double m = 1 / (4 * opt_.mu_0);
     // full_staggered: the fused form exists as the tiled sweep only (other grids store the polarisation)
@@ -625,6 +634,10 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
     u_valid_ = false;
     if (dst == eps_) eps_stale_ = false;
     for (int c = 0; c < 6; ++c) E_cur_[c] = E6[c];
+    return;
+  }
+  if (willot()) {
+    willot_scheme(E6, src, dst, phi, nrm);
     return;
   }
   if (opt_.gamma_scheme == 1) {
@@ -734,6 +747,100 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
   if (timing_) times_.count++;
   // fu_ now holds the displacement this strain was built from (eps = E + sym grad u when R == 0)
   u_valid_ = !add_R && dst == eps_;
+  if (dst == eps_) eps_stale_ = false;
+  for (int c = 0; c < 6; ++c) E_cur_[c] = E6[c];
+}
+
+// GammaOperatorFourierWillotR  F:19130-19152: tan(q / 2) / (4 w) and 1 + e^{iq} per axis, host libm; built and uploaded on
+// the first pass of the scheme (the grid of a solver never changes), so solvers that never ask for it pay nothing
+WillotTables Solver::willot_tables() {
+  const int len[3] = {nxg_, g_.ny, g_.nz};
+  const double d[3] = {g_.dx, g_.dy, g_.dz};
+  for (int a = 0; a < 3; ++a) {
+    if (wil_e_[a]) continue;
+    const int cnt = (a == 2) ? g_.nzc : len[a];
+    std::vector<double> wt;
+    std::vector<cplx> we;
+    willot_axis_table(len[a], d[a], cnt, &wt, &we);
+    FG_HIP_CHECK(hipMalloc(&wil_t_[a], cnt * sizeof(double)));
+    FG_HIP_CHECK(hipMalloc(&wil_e_[a], cnt * sizeof(cplx)));
+    FG_HIP_CHECK(hipMemcpy(wil_t_[a], wt.data(), cnt * sizeof(double), hipMemcpyHostToDevice));
+    FG_HIP_CHECK(hipMemcpy(wil_e_[a], we.data(), cnt * sizeof(cplx), hipMemcpyHostToDevice));
+  }
+  WillotTables t;
+  for (int a = 0; a < 3; ++a) t.t[a] = wil_t_[a], t.e[a] = wil_e_[a];
+  return t;
+}
+
+// gamma_scheme willot, one pass.  Elasticity: GammaOperatorWillotR  F:20322-20330 = fftTensor, initBCProjector(tau_hat),
+// GammaOperatorFourierWillotR, applyBCProjector(eta_hat), fftInvTensor on the six components, routed like the collocated
+// scheme.  Viscosity: DeltaOperatorWillotR  F:20380-20418: m = 1 / (4 mu0); adj = E - 2 alpha m <tau>;
+// eta = GammaWillotR(adj; mu = -1 / (4 m), lambda = inf)(tau) + 2 alpha m tau_copy -- tau_copy lives in dst (the strain the
+// polarisation was made from is dead by then), <tau> stays on the device as in the staggered Delta path.
+void Solver::willot_scheme(const double* E6, double* src, double* dst, const FieldPtrs<kMaxPhases>& phi, const FieldPtrs<3>& nrm) {
+  const double alpha = -1.0;  // GammaOperator(..., -1)  F:20575
+  const bool visc = opt_.mode == 2;
+  const bool mixed_bc = !(frobenius(BC_MQ_) < kEps);
+  const double m = visc ? 1 / (4 * opt_.mu_0) : 0.0;
+  const WillotTables wt = willot_tables();
+  Vec6 Ev;
+  for (int c = 0; c < 6; ++c) Ev.v[c] = E6[c];
+  time_begin(0);
+  stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), src, phi, nrm);
+  time_end(0);
+  if (visc) {
+    launch_sum6(g_, ptrs6(tau_), false, partial_, dscal_ + kSlotMean, stream_);   // tau_copy->average(), stays on the device
+    if (mixed_bc) {   // applyBCProjector(eta_hat, alpha): R = alpha MQ <tau> folded into the sums, as in the staggered Delta path
+      Mat36 B;
+      for (int j = 0; j < 6; ++j) {
+        double e[6] = {0, 0, 0, 0, 0, 0}, col[6];
+        e[j] = 1.0;
+        voigt_mv(BC_MQ_, e, col);
+        for (int c = 0; c < 6; ++c) B.a[c * 6 + j] = col[c];
+      }
+      hipLaunchKernelGGL(k_bc_adjust_sums, dim3(1), dim3(64), 0, stream_, dscal_ + kSlotMean, B, alpha / (2 * alpha * m));
+      FG_HIP_CHECK(hipGetLastError());
+    }
+    launch_copy(tau_, dst, 6 * g_.n, stream_);   // tau_copy
+  }
+  time_begin(2);
+  fft_->forward(tau_, 6, g_.n, 1 / (double)nglobal_);   // fftTensor: 1/N on the forward transform  F:18531-18560
+  time_end(2);
+  if (!visc && (mixed_bc || opt_.bc_relax != 1.0)) {
+    // F0 = Re tau_hat(0) (initBCProjector(tau_hat) F:20219-20225), the zero frequency of eta_hat becomes E + R
+    // (applyBCProjector(eta_hat, alpha) F:20272-20279), as in the collocated branch of basic_scheme
+    double F0[6], t1[6], t2[6], t3[6];
+    for (int c = 0; c < 6; ++c)
+      FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean + c, tau_ + (long)c * g_.n, sizeof(double), hipMemcpyDeviceToHost, stream_));
+    FG_HIP_CHECK(hipStreamSynchronize(stream_));
+    for (int c = 0; c < 6; ++c) F0[c] = hscal_[kSlotMean + c];
+    voigt_mv(BC_MQ_, F0, t1);
+    voigt_mv(BC_QC0_, F00_, t2);
+    voigt_mv(BC_M_, t2, t3);
+    for (int c = 0; c < 6; ++c) Ev.v[c] += alpha * (opt_.bc_relax * t1[c] - (1 - opt_.bc_relax) * t3[c]);
+  }
+  time_begin(5);
+  if (visc)
+    launch_gamma_willot(g_, ptrs6(tau_), wt, -1.0 / (4 * m), INFINITY, alpha, 0.0, Ev, dscal_ + kSlotMean,
+                        -(2 * alpha * m) / (double)nglobal_, stream_);
+  else
+    launch_gamma_willot(g_, ptrs6(tau_), wt, opt_.mu_0, opt_.lambda_0, alpha, 0.0, Ev, nullptr, 0.0, stream_);
+  time_end(5);
+  time_begin(8);
+  fft_->inverse(tau_, 6, g_.n);
+  time_end(8);
+  time_begin(9);
+  if (visc) {   // eta.xpay(eta, 2 alpha m, tau_copy)  F:20411
+    const double* in[2] = {tau_, dst};
+    const double w[2] = {1.0, 2 * alpha * m};
+    launch_lincomb(2, in, w, dst, 6 * g_.n, stream_);
+  } else {
+    launch_copy(tau_, dst, 6 * g_.n, stream_);
+  }
+  launch_sum6(g_, ptrs6(dst), true, partial_, dscal_ + kSlotSumSq, stream_);
+  time_end(9);
+  if (timing_) times_.count++;
+  u_valid_ = false;
   if (dst == eps_) eps_stale_ = false;
   for (int c = 0; c < 6; ++c) E_cur_[c] = E6[c];
 }
@@ -1037,6 +1144,12 @@ FieldPtrs<2> Solver::effective_moduli() {
   return mod;
 }
 
+void Solver::willot_check() const {
+  if (opt_.mode == 1)
+    throw std::runtime_error("gamma_scheme willot is not available in heat / porous mode (the reference has no such operator)");
+  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("gamma_scheme willot is not available on slab-decomposed solvers");
+}
+
 void Solver::dfg_check() const {
   if (opt_.mode == 1)
     throw std::runtime_error("gamma_scheme full_staggered is not available in heat / porous mode (the reference's 3-component "
@@ -1232,6 +1345,7 @@ void Solver::ensure_eps() {
 void Solver::iterate(const double* E6, int n) {
   FG_HIP_CHECK(hipSetDevice(device_));
   if (dfg()) dfg_check();
+  if (willot()) willot_check();
   int i = 0;
   if (u_loop_eligible()) {
     if (!u_valid_ && n > 0 && opt_.mode == 1) {
@@ -1522,6 +1636,7 @@ bool Solver::run_load_steps(const double* E6, const double* S6, const double* pa
 // runSolver  F:21400-21433 for one load step
 bool Solver::run_one_step(const double* E0, const double* S0) {
   if (dfg()) dfg_check();
+  if (willot()) willot_check();
   // EpsilonErrorEstimator  F:14591-14637: constructed on the field the step starts from (zero for the first step)
   const double prev0 = fresh_step_ ? 0.0 : current_norm9();
   if (opt_.error_estimator >= 2) {

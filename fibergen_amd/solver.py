@@ -17,7 +17,9 @@ MIXING = {"voigt": 0, "laminate": 1}
 # gamma_scheme option values; full_staggered and half_staggered are the staggered operator with the material evaluated on
 # the doubly fine grid (use_dfg F:14894-14897, alias "full-staggered" F:15068): they differ only in how the fine phase
 # fields are made (voxelised on the fine grid, or replicated from the coarse one)
-GAMMA_SCHEMES = {"staggered": 0, "collocated": 1, "full_staggered": 2, "full-staggered": 2, "half_staggered": 2}
+# willot ("Willot-R" in readSettings): Willot's rotated scheme, GammaOperatorWillotR F:20322-20330 (elasticity, viscosity)
+GAMMA_SCHEMES = {"staggered": 0, "collocated": 1, "full_staggered": 2, "full-staggered": 2, "half_staggered": 2,
+                 "willot": 3, "Willot-R": 3}
 
 STAGES = {"stress": 0, "div": 1, "fft_forward": 2, "g0": 3, "fft_inverse": 4, "eps": 5, "iteration": 6,
           "stress_const": 7}

@@ -88,7 +88,15 @@ int fg_set_normals(fg_solver* s, const double* normals /* [3][nx][ny][nz] */);
  * and restrict (restrict_from_dfg F:14273-14335); for Voigt mixing of linear laws this equals a coarse evaluation in which
  * each component group reads its own staggered phase fractions, which is how it runs here.  The reference medium
  * (calcRefMaterial F:22283-22313), "phi" and fg_volume_fraction stay on the coarse field.  Elasticity and viscosity with
- * Voigt mixing, basic scheme and CG; laminate mixing, mode heat / porous and slab-decomposed solvers are refused),
+ * Voigt mixing, basic scheme and CG; laminate mixing, mode heat / porous and slab-decomposed solvers are refused;
+ * 3 = willot ("Willot-R"): Willot's rotated scheme in Fourier space on the six components, GammaOperatorWillotR F:20322-20330
+ * / GammaOperatorFourierWillotR F:19083-19299; in mode viscosity DeltaOperatorWillotR F:20380-20418, the same operator for
+ * lambda_0 = infinity.  lambda_0 rule, the one deviation from the reference: its active branch F:19233-19240 forms
+ * mu_0 / lambda_0 and is NaN for lambda_0 = 0 (the default here); every finite lambda_0, 0 included, takes the same expression
+ * multiplied through by lambda_0 (the reference's disabled sibling F:19243-19250; equal to rounding for lambda_0 != 0),
+ * lambda_0 = infinity the active branch with mu_0 / lambda_0 = 0.  Elasticity (Voigt and laminate mixing, basic scheme and CG,
+ * every error estimator, load steps, mixed boundary conditions: the strain-state loops, like collocated) and viscosity; mode
+ * heat / porous, slab-decomposed solvers and fg_set_phase_field_fine are refused),
  * method (0 = basic scheme, runBasic F:21716-21805; 1 = conjugate gradients, runCGElasticity
  * F:23153-23247, the reference's default), error_estimator (0 = epsilon F:14591-14637; 1 = residual F:14382-14405, method
  * cg only; 2 = sigma F:14514-14587; 3 = energy F:14410-14468; 4 = none F:14370-14378 -- 2 and 3 re-measure <sigma> / <W> of
