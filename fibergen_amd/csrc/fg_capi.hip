@@ -268,6 +268,10 @@ int fg_set_option_i(fg_solver* s, const char* key, long value) {
     else if (k == "plane_fft") o.plane_fft = value < 0 ? -1 : (value != 0);
     else if (k == "pair_chunk") o.pair_chunk = value < 0 ? 0 : (int)value;
     else if (k == "joint_x") o.joint_x = value != 0;
+    else if (k == "bluestein") {
+      o.bluestein = value != 0;
+      v.apply_bluestein();
+    }
     else if (k == "tile_plans") {
       o.tile_plans = value != 0;
       fg::fft::smooth_plan_kernels(value != 0);

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fg_common.h"
+#include "fg_fft_bluestein.h"
 #include "fg_fft_smooth.h"
 
 namespace fg {
@@ -77,6 +78,13 @@ class Fft3 {
   // image per component: the same butterflies in either form
   void set_joint_x(bool on);
 
+  // lengths with a prime factor above 13, from fft::kBluesteinMin points on: Bluestein's algorithm on the tile kernels
+  // (fg_fft_bluestein.h; default) or the O(n^2) sums every such length took before.  Per Fft3, not per process.
+  void set_bluestein(bool on) { bluestein_ = on; }
+  // how an axis is transformed: 0 length 1, 1 power of two, 2 sub-lines p * 2^k, 3 tile kernels, 4 Bluestein, 5 O(n^2)
+  int path(int axis) const;
+  int bluestein_m(int axis) const { return path(axis) == 4 ? blue_[axis].m() : 0; }   // the padded length, 0: not on Bluestein
+
   bool fast_x() const { return fast_[0]; }
   bool fast_y() const { return fast_[1]; }
   bool fast_z() const { return fast_[2]; }
@@ -94,6 +102,10 @@ class Fft3 {
   bool zodd_ = false;           // odd nz with a plan: the rows are transformed as nz complex points
   fft::SmoothPlan xfused_plan_[2];   // fused x pass of the tile kernels: [0] one component, [1] three (n = 0: none)
   bool joint_x_ = true;
+  bool blue_on(int axis) const { return bluestein_ && blue_[axis].n != 0; }
+  fft::BluesteinPlan blue_[3];   // n != 0: the axis has neither of the faster passes and a Bluestein plan (z: of nz / 2, odd nz: of nz)
+  cplx* blue_tab_[3][3];         // per axis: chirp c[k], k < n; filter B^[p], p < M; roots of M
+  bool bluestein_ = true;
   int stream_stores_ = 0;  // FFT passes use cache-bypassing stores (fields larger than the Infinity Cache)
   cplx* tw_[3];      // per-axis pass twiddles (fast path) ; z: for M = nz/2
   cplx* half_root_[2];  // e^{-i pi j/n}, j < n/8, of x and y (fused Green-operator pass)

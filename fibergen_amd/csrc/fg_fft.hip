@@ -16,6 +16,7 @@
 #include "fg_fft_kernels.h"
 #include "fg_fft_plane.h"
 #include "fg_fft_smooth.h"
+#include "fg_fft_bluestein_dev.h"
 #include "fg_fft_smooth_dev.h"
 #include "fg_fft_tables.h"
 #include "fg_hip_util.h"
@@ -1012,6 +1013,7 @@ Fft3::Fft3(const Grid& g, hipStream_t stream) : g_(g), stream_(stream), wz_(null
   for (int a = 0; a < 3; ++a) {
     tw_[a] = nullptr;
     wgen_[a] = nullptr;
+    for (int k = 0; k < 3; ++k) blue_tab_[a][k] = nullptr;
   }
   half_root_[0] = half_root_[1] = nullptr;
   fast_[0] = fast_len(g.nx);
@@ -1043,6 +1045,17 @@ Fft3::Fft3(const Grid& g, hipStream_t stream) : g_(g), stream_(stream), wz_(null
       if (m > 1 && !one_kernel_mixed && (a == 2 ? smooth_plan_z(m, &sp) : smooth_plan_strided(m, &sp))) smooth_[a] = sp;
       wgen_[a] = upload(make_unit_roots(len[a], len[a]));
       need_scratch = true;
+      // what is left -- a prime factor above 13 -- from kBluesteinMin points on: Bluestein on the tile kernels of a padded length
+      if (!smooth_[a].n && !odd_[a]) {
+        const int line = a == 2 ? (len[a] % 2 ? len[a] : len[a] / 2) : len[a];
+        BluesteinPlan bp;
+        if (a == 2 ? bluestein_plan_z(line, &bp) : bluestein_plan_strided(line, &bp)) {
+          blue_[a] = bp;
+          blue_tab_[a][0] = upload(make_bluestein_chirp(line));
+          blue_tab_[a][1] = upload(make_bluestein_filter(line, bp.m()));
+          blue_tab_[a][2] = upload(make_unit_roots(bp.m(), bp.m()));
+        }
+      }
     }
   }
   if (smooth_[0].n) {   // plans of the tile kernels' fused x pass (one / three components)
@@ -1073,11 +1086,22 @@ void Fft3::set_joint_x(bool on) {
   }
 }
 
+int Fft3::path(int axis) const {
+  const int len = axis == 0 ? g_.nx : (axis == 1 ? g_.ny : g_.nz);
+  if (len == 1) return 0;
+  if (fast_[axis]) return 1;
+  if (smooth_[axis].n) return 3;
+  if (odd_[axis]) return 2;
+  return blue_on(axis) ? 4 : 5;
+}
+
 Fft3::~Fft3() {
   for (int a = 0; a < 3; ++a) {
     if (tw_[a]) (void)hipFree(tw_[a]);
     if (a < 2 && half_root_[a]) (void)hipFree(half_root_[a]);
     if (wgen_[a]) (void)hipFree(wgen_[a]);
+    for (int k = 0; k < 3; ++k)
+      if (blue_tab_[a][k]) (void)hipFree(blue_tab_[a][k]);
   }
   if (wz_) (void)hipFree(wz_);
   if (scratch_) (void)hipFree(scratch_);
@@ -1232,6 +1256,22 @@ void Fft3::strided(double* data, int ncomp, long comp_stride, int axis, int dir,
       combine();
       subs();
     }
+    return;
+  }
+  if (blue_on(axis)) {
+    BluesteinArgs a;
+    a.data = reinterpret_cast<cplx*>(data);
+    a.ls = ls;
+    a.os = os;
+    a.ncols = ncols;
+    a.tiles_per_outer = 0;
+    a.scale = scale;
+    a.nt = stream_stores_ ? 3 : 0;
+    a.dir = dir;
+    a.n = n;
+    a.t = BluesteinTables{blue_tab_[axis][0], blue_tab_[axis][1], blue_tab_[axis][2]};
+    a.plan = blue_[axis].pass;
+    launch_bluestein_strided(a, nouter, ncomp, comp_stride / 2, stream_);
     return;
   }
   // generic: component by component through the scratch buffer
@@ -1528,6 +1568,12 @@ void Fft3::r2c_z(double* data, int ncomp, long comp_stride, const PlaneWindow* w
     }
     return;
   }
+  if (blue_on(2)) {
+    BluesteinZArgs a = {data, nrows, g_.nzp, stream_stores_ ? 3 : 0, 1, g_.nz % 2, blue_[2].n,
+                        BluesteinTables{blue_tab_[2][0], blue_tab_[2][1], blue_tab_[2][2]}, wgen_[2], blue_[2].pass};
+    launch_bluestein_z(a, ncomp, comp_stride, stream_);
+    return;
+  }
   const long total = nrows * g_.nzc;
   const int bs = 256;
   for (int c = 0; c < ncomp; ++c) {
@@ -1617,6 +1663,12 @@ void Fft3::c2r_z(double* data, int ncomp, long comp_stride, const PlaneWindow* w
     a.nt = 0;
     a.xcd_order = 0;
     strided_pow2_narrow(m, a, (int)nrows, +1, ncomp, comp_stride / 2, stream_);
+    return;
+  }
+  if (blue_on(2)) {
+    BluesteinZArgs a = {data, nrows, g_.nzp, stream_stores_ ? 3 : 0, 0, g_.nz % 2, blue_[2].n,
+                        BluesteinTables{blue_tab_[2][0], blue_tab_[2][1], blue_tab_[2][2]}, wgen_[2], blue_[2].pass};
+    launch_bluestein_z(a, ncomp, comp_stride, stream_);
     return;
   }
   const long total = nrows * g_.nz;

@@ -100,6 +100,7 @@ void Solver::slab_alloc() {
   gu_.xw_lo = g_.nx + 4;   // plane -1 -> spare plane nx + 3
   gu_.xw_hi = 0;           // planes nx, nx + 1, nx + 2 -> themselves (the last two are loaded by the march, never used)
   fft_ys_.reset(new Fft3(make_grid(nxg_, nyl_, g_.nz, 1.0, 1.0, 1.0), stream_));
+  fft_ys_->set_bluestein(opt_.bluestein != 0);
   FG_HIP_CHECK(hipEventCreateWithFlags(&ev_c2x_, hipEventDisableTiming));
   FG_HIP_CHECK(hipEventCreateWithFlags(&ev_norm_, hipEventDisableTiming));
   for (int k = 0; k < kCommSlots; ++k) FG_HIP_CHECK(hipEventCreateWithFlags(&ev_x_[k], hipEventDisableTiming));

@@ -513,7 +513,20 @@ void Solver::enable_stage_timing(bool on) {
   }
   timing_ = on;
 }
+void Solver::apply_bluestein() {
+  if (fft_) fft_->set_bluestein(opt_.bluestein != 0);
+  if (fft_ys_) fft_ys_->set_bluestein(opt_.bluestein != 0);
+}
+
 long Solver::counter(const std::string& name) const {
+  // how each axis is transformed (Fft3::path) and the padded length of its Bluestein pass; slab solvers transform x on the y-slab
+  if (fft_ && (name.rfind("fft_path_", 0) == 0 || name.rfind("fft_bluestein_m_", 0) == 0) && !name.empty()) {
+    const char c = name.back();
+    const int axis = c == 'x' ? 0 : (c == 'y' ? 1 : (c == 'z' ? 2 : -1));
+    const Fft3* f = axis == 0 && fft_ys_ ? fft_ys_.get() : fft_.get();
+    if (axis >= 0 && name == std::string("fft_path_") + c) return f->path(axis);
+    if (axis >= 0 && name == std::string("fft_bluestein_m_") + c) return f->bluestein_m(axis);
+  }
   if (name == "interface_voxels") return (long)mixed_n_;
   if (name == "affected_voxels") return (long)aff_n_;
   if (name == "pair_chunk_planes") return (long)pair_chunk_planes(opt_.mode == 1 ? 1 : 3);

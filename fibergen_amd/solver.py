@@ -117,7 +117,7 @@ class LSSolver:
                 if v not in kinds:
                     raise RuntimeError("Unknown error estimator '%s'" % v)
                 self._check(self._lib.fg_set_option_i(self._h, b"error_estimator", kinds[v]))
-            elif k in ("u_loop", "fuse_x", "cg_fused", "fuse_stress_div", "u_tile", "x_layout", "plane_fft", "slab_split", "slab_interleave", "slab_loopback", "laminate_overlap", "phi_sweep", "pair_chunk", "joint_x", "tile_plans", "staged_copy", "stage_chunk_kb"):
+            elif k in ("u_loop", "fuse_x", "cg_fused", "fuse_stress_div", "u_tile", "x_layout", "plane_fft", "slab_split", "slab_interleave", "slab_loopback", "laminate_overlap", "phi_sweep", "pair_chunk", "joint_x", "bluestein", "tile_plans", "staged_copy", "stage_chunk_kb"):
                 self._check(self._lib.fg_set_option_i(self._h, k.encode(), int(v)))
             elif k in ("maxiter", "loadstep_extrapolation_order"):
                 self._check(self._lib.fg_set_option_i(self._h, k.encode(), int(v)))
@@ -184,7 +184,9 @@ class LSSolver:
         return bool(failed.value)
 
     def counter(self, name):
-        """fg_get_counter: "interface_voxels", "affected_voxels" (lengths of the laminate lists); -1 = unknown name."""
+        """fg_get_counter: "interface_voxels", "affected_voxels" (lengths of the laminate lists); "fft_path_x|y|z" (how the axis
+        is transformed: 0 length 1, 1 power of two, 2 sub-lines p * 2^k, 3 tile kernels, 4 Bluestein, 5 O(n^2)),
+        "fft_bluestein_m_x|y|z" (padded length of the axis' Bluestein pass, 0 = not on Bluestein); -1 = unknown name."""
         return int(self._lib.fg_get_counter(self._h, name.encode()))
 
     def iterate(self, E, n):

@@ -126,7 +126,11 @@ int fg_set_normals(fg_solver* s, const double* normals /* [3][nx][ny][nz] */);
  * 8 MB and more through the pinned-buffer pipeline; 1 both directions, 0 one strided copy), stage_chunk_kb (pipeline stage),
  * joint_x (tile kernels of the lengths that are not powers of two: 1 = default, fused x pass on one joint LDS image of the three
  * components; 0 = one image per component), tile_plans (1 = default: tile kernels built for one plan each where the plan is in
- * the tables of fg_fft_smooth_plans.h; 0 = the class kernels for every plan; a process-wide switch). */
+ * the tables of fg_fft_smooth_plans.h; 0 = the class kernels for every plan; a process-wide switch), bluestein (1 = default: an
+ * axis whose length has a prime factor above 13 -- 67, 170, 190, 340, every prime -- and at least 64 points (z: nz / 2 points
+ * for even nz) is transformed by Bluestein's algorithm on the tile kernels of a padded 13-smooth length M >= 2 n - 1, so every
+ * length up to about 2 490 points per axis runs in O(n log n); longer such lines, lines below 64 points and bluestein = 0 take
+ * the O(n^2) sums through a scratch component; per solver). */
 int fg_set_option_d(fg_solver* s, const char* key, double value);
 int fg_set_option_i(fg_solver* s, const char* key, long value);
 
@@ -203,7 +207,10 @@ int fg_get_stage_timing_bias(const fg_solver* s, double* ms);
 /* Sizes and set-up facts of this solver (no counterpart in the reference; bench.py prices the laminate correction with them):
  * "interface_voxels" / "affected_voxels" = lengths of the laminate correction's voxel lists (0 until a laminate pass built
  * them); "pair_chunk_planes" = x planes per chunk of the paired z / y transform passes (option pair_chunk; 0 = whole-field
- * passes: stage timing then reports each pair in the slot of its first pass).  Unknown names give -1. */
+ * passes: stage timing then reports each pair in the slot of its first pass); "fft_path_x" / "_y" / "_z" = how the axis is
+ * transformed: 0 length 1, 1 power of two, 2 sub-lines p * 2^k, 3 tile kernels, 4 Bluestein, 5 O(n^2) sums;
+ * "fft_bluestein_m_x" / "_y" / "_z" = the padded length of the axis' Bluestein pass (0: the axis is not on Bluestein).
+ * Unknown names give -1. */
 long fg_get_counter(const fg_solver* s, const char* name);
 
 /* Measurement helper (no counterpart in the reference): achieved HBM bandwidth of a streaming copy a = b and of the
