@@ -37,6 +37,8 @@ class FgPlanOp(ctypes.Structure):
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(FgXop), ctypes.c_int)
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int)
 
+FG_VOX_NORMALS, FG_VOX_FINE = 1, 2   # flags of fg_voxelize_into
+
 # name -> (restype, argtypes); mirrors include/fibergen_amd.h one to one
 SIGNATURES = {
     "fg_abi_version": (ctypes.c_int, []),
@@ -95,6 +97,8 @@ SIGNATURES = {
                                    ctypes.c_int, ctypes.c_int, ctypes.c_double, c_double_p, c_double_p, c_double_p,
                                    ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
     "fg_voxelize_team_depth": (ctypes.c_int, [ctypes.c_int]),
+    "fg_voxelize_into": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(FgFiber), ctypes.c_int, c_double_p, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_double, ctypes.c_int, c_double_p]),
 }
 
 _lib = None

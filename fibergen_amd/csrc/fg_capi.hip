@@ -215,6 +215,13 @@ int fg_set_normals(fg_solver* s, const double* normals) {
   });
 }
 
+int fg_voxelize_into(fg_solver* s, const fg_fiber* fibers, int nfibers, const double* x0, int matrix_mat, int smooth_levels,
+                     double smooth_tol, int flags, double* real_volume) {
+  return guarded(s, [&](fg::Solver& v) {
+    v.voxelize_into(fibers, nfibers, x0, matrix_mat, smooth_levels, smooth_tol, flags, real_volume);
+  });
+}
+
 int fg_set_option_d(fg_solver* s, const char* key, double value) {
   return guarded(s, [&](fg::Solver& v) {
     const std::string k = key ? key : "";

@@ -24,6 +24,8 @@
 #include "fg_stop_rule.h"
 #include "fg_transfer.h"
 
+struct fg_fiber;   // include/fibergen_amd.h
+
 namespace fg {
 
 class SlabGroup;
@@ -152,6 +154,12 @@ class Solver {
   // the device to its coarse field and its three shear-group fractions; the image is not kept
   void set_phase_field_fine(int p, const double* fine_host);
   void set_normals(const double* n_host);                // [3][nx][ny][nz]
+  // init_phase F:25026-25038 for <place_fiber> shapes without the host: initPhi F:17489-17581 + normalizePhi F:17588-17646 on
+  // this solver's device and stream, straight into phi_ (flags & FG_VOX_FINE: on the doubly fine grid, then reduced like
+  // set_phase_field_fine) and, with FG_VOX_NORMALS, into normals_.  Leaves the state the per-phase set_phase_field /
+  // set_phase_field_fine calls and set_normals leave.  The caller's current device is restored.
+  void voxelize_into(const fg_fiber* fibers, int nfibers, const double* x0, int matrix_mat, int smooth_levels, double smooth_tol,
+                     int flags, double* real_volume /* [nphases] or nullptr */);
   void set_bc_projector(const double* P36);              // row-major 6x6
   void set_callback(ConvergenceCallback cb, void* user) { cb_ = cb; cb_user_ = user; }
   void cancel() { cancel_ = true; }
@@ -208,7 +216,7 @@ class Solver {
   void reset_stage_times();
   double event_bias_ms() const { return event_bias_ms_; }
   // fg_get_counter: "interface_voxels" / "affected_voxels" = lengths of the laminate correction's lists (0 before they are
-  // built); -1 = unknown name
+  // built); "phase_uploads" = host arrays received by set_phase_field / set_phase_field_fine / set_normals; -1 = unknown name
   long counter(const std::string& name) const;
 
  private:
@@ -369,6 +377,7 @@ class Solver {
   bool mod_dirty_ = true;
   double* phis_ = nullptr;     // gamma_scheme 2: [nphase][3] shear-group fractions phi^(23), phi^(13), phi^(12)
   unsigned fine_set_ = 0;      // phases whose phis_ came from a fine image (the others are built from phi_ as replicas)
+  long phase_uploads_ = 0;     // host-array phase / normal uploads (voxelize_into adds none)
   double* mod5_ = nullptr;     // gamma_scheme 2: the five moduli
   bool mod5_dirty_ = true;
   bool complement_dirty_ = true, complementary_ = false;

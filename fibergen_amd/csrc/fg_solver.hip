@@ -1,4 +1,5 @@
 #include "fg_solver.h"
+#include "fg_voxelize.h"
 
 #include <algorithm>
 #include <cmath>
@@ -260,6 +261,7 @@ void Solver::set_phase_field(int p, const double* phi_host) {
   complement_dirty_ = true;
   mixed_dirty_ = true;
   fine_set_ &= ~(1u << p);
+  ++phase_uploads_;
   upload_padded(phi_ + (long)p * g_.n, phi_host);
 }
 
@@ -269,6 +271,7 @@ void Solver::set_phase_field_fine(int p, const double* fine_host) {
   if (!dfg()) throw std::runtime_error("a phase field on the doubly fine grid needs gamma_scheme full_staggered (2)");
   if (nranks_ != 1 || slab_layout_) throw std::runtime_error("full_staggered is not available on slab-decomposed solvers");
   FG_HIP_CHECK(hipSetDevice(device_));
+  ++phase_uploads_;
   const size_t nfine = 8 * (size_t)g_.nxyz;
   if (!phis_) {
     FG_HIP_CHECK(hipMalloc(&phis_, 3 * (size_t)pt_.n * g_.n * sizeof(double)));
@@ -290,11 +293,90 @@ void Solver::set_phase_field_fine(int p, const double* fine_host) {
 void Solver::set_normals(const double* n_host) {
   FG_HIP_CHECK(hipSetDevice(device_));
   mixed_dirty_ = true;   // the interface lists carry compact copies of the normals
+  ++phase_uploads_;
   if (!normals_) {
     FG_HIP_CHECK(hipMalloc(&normals_, 3 * g_.n * sizeof(double)));
     FG_HIP_CHECK(hipMemsetAsync(normals_, 0, 3 * g_.n * sizeof(double), stream_));
   }
   upload_padded(normals_, n_host, 3, g_.n);
+}
+
+namespace {
+struct DeviceDoubles {   // scratch images of voxelize_into
+  std::vector<double*> p;
+  ~DeviceDoubles() {
+    for (double* q : p)
+      if (q) (void)hipFree(q);
+  }
+  double* alloc(size_t n) {
+    double* q = nullptr;
+    FG_HIP_CHECK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(double)));
+    p.push_back(q);
+    return q;
+  }
+};
+}  // namespace
+
+void Solver::voxelize_into(const fg_fiber* fibers, int nfibers, const double* x0, int matrix_mat, int smooth_levels,
+                           double smooth_tol, int flags, double* real_volume) {
+  const bool fine = (flags & FG_VOX_FINE) != 0, want_normals = (flags & FG_VOX_NORMALS) != 0;
+  const int nph = pt_.n;
+  if (nph < 1 || !x0 || nfibers < 0 || !phi_) throw std::runtime_error("fg_voxelize: bad arguments");
+  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("fg_voxelize_into is not available on slab-decomposed solvers");
+  if (fine) {
+    if (willot()) throw std::runtime_error("gamma_scheme willot takes phase fields on the solver's grid (a fine phase field needs full_staggered)");
+    if (!dfg()) throw std::runtime_error("a phase field on the doubly fine grid needs gamma_scheme full_staggered (2)");
+  }
+  DeviceScope scope(device_);
+  Voxelizer vox(fibers, nfibers, nph);   // host part: the argument errors come before anything changes
+  if (real_volume) vox.real_volume(real_volume);
+  const int f = fine ? 2 : 1;
+  const int vx = f * g_.nx, vy = f * g_.ny, vz = f * g_.nz;
+  const size_t nvox = (size_t)vx * vy * vz;
+  vox.begin(vx, vy, vz, g_.dx, g_.dy, g_.dz, x0, stream_);
+  // dense images before normalizePhi; the matrix enters as the constant 1 and needs one only where its normalised image
+  // is read again (the reduction of the fine form)
+  DeviceDoubles scratch;
+  const double* in[kMaxPhases] = {};
+  double* out[kMaxPhases] = {};
+  for (int m = 0; m < nph; ++m) {
+    double* img = (m != matrix_mat || fine) ? scratch.alloc(nvox) : nullptr;
+    in[m] = img;
+    out[m] = fine ? img : phi_ + (long)m * g_.n;
+    if (m != matrix_mat) vox.material(m, smooth_levels, smooth_tol, img);
+  }
+  vox.check_refinement();
+
+  mod_dirty_ = mod5_dirty_ = true;
+  smod_dirty_ = complement_dirty_ = mixed_dirty_ = true;
+  if (!fine) {
+    launch_vox_normalize(in, out, nph, matrix_mat, (long)nvox, g_.nz, g_.nzp, stream_);
+    fine_set_ = 0;
+  } else {
+    if (!phis_) {
+      FG_HIP_CHECK(hipMalloc(&phis_, 3 * (size_t)nph * g_.n * sizeof(double)));
+      FG_HIP_CHECK(hipMemsetAsync(phis_, 0, 3 * (size_t)nph * g_.n * sizeof(double), stream_));
+    }
+    launch_vox_normalize(in, out, nph, matrix_mat, (long)nvox, vz, vz, stream_);   // in place
+    for (int p = 0; p < nph; ++p) {
+      FieldPtrs<3> s;
+      for (int c = 0; c < 3; ++c) s.p[c] = phis_ + (3L * p + c) * g_.n;
+      launch_dfg_fractions_fine(g_, out[p], phi_ + (long)p * g_.n, s, stream_);
+      fine_set_ |= 1u << p;
+    }
+  }
+  if (want_normals) {   // always on the solver's own grid
+    if (!normals_) {
+      FG_HIP_CHECK(hipMalloc(&normals_, 3 * g_.n * sizeof(double)));
+      FG_HIP_CHECK(hipMemsetAsync(normals_, 0, 3 * g_.n * sizeof(double), stream_));
+    }
+    if (vox.num_shapes() == 0) {
+      FG_HIP_CHECK(hipMemsetAsync(normals_, 0, 3 * g_.n * sizeof(double), stream_));
+    } else {
+      vox.normals(g_.nx, g_.ny, g_.nz, normals_, g_.nzp, g_.n);
+    }
+  }
+  FG_HIP_CHECK(hipStreamSynchronize(stream_));   // the scratch images go now
 }
 
 void Solver::set_bc_projector(const double* P36) {
@@ -529,6 +611,7 @@ long Solver::counter(const std::string& name) const {
   }
   if (name == "interface_voxels") return (long)mixed_n_;
   if (name == "affected_voxels") return (long)aff_n_;
+  if (name == "phase_uploads") return phase_uploads_;
   if (name == "pair_chunk_planes") return (long)pair_chunk_planes(opt_.mode == 1 ? 1 : 3);
   return -1;
 }

@@ -36,6 +36,8 @@
 #include "../../include/fibergen_amd.h"
 #include "fg_hip_util.h"
 #include "fg_plane_cut.h"
+#include "fg_stage_math.h"
+#include "fg_voxelize.h"
 
 namespace {
 
@@ -335,8 +337,10 @@ __global__ __launch_bounds__((1 << (3 * D)) < 64 ? 64 : (1 << (3 * D))) void k_v
 }
 
 // interface normals: gradient of the distance to the closest shape of ANY material at the voxel centre
-// (sampleSlice NORMALS  F:6905-6925); shapes staged through LDS in tiles
-__global__ __launch_bounds__(256) void k_vox_normals(VoxGrid g, const Shape* shapes, int nshapes, double* normals) {
+// (sampleSlice NORMALS  F:6905-6925); shapes staged through LDS in tiles.  Component c of voxel (i, j, k) goes to
+// normals[c * cstride + (i * ny + j) * pitch + k]: dense (pitch = nz) or a solver's padded rows
+__global__ __launch_bounds__(256) void k_vox_normals(VoxGrid g, const Shape* shapes, int nshapes, double* normals, long pitch,
+                                                     long cstride) {
   __shared__ Shape tile[32];
   const size_t N = (size_t)g.nx * g.ny * g.nz;
   const size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -362,9 +366,34 @@ __global__ __launch_bounds__(256) void k_vox_normals(VoxGrid g, const Shape* sha
     }
   }
   if (live) {
-    normals[o] = nbest.x;
-    normals[N + o] = nbest.y;
-    normals[2 * N + o] = nbest.z;
+    const size_t d = ((size_t)i * g.ny + j) * (size_t)pitch + k;
+    normals[d] = nbest.x;
+    normals[(size_t)cstride + d] = nbest.y;
+    normals[2 * (size_t)cstride + d] = nbest.z;
+  }
+}
+
+// normalizePhi  F:17588-17646 per voxel (fg::launch_vox_normalize): streaming, z fastest, one voxel per thread
+struct NormalizeArgs {
+  const double* in[fg::kMaxPhases];
+  double* out[fg::kMaxPhases];
+};
+
+__global__ __launch_bounds__(256) void k_vox_normalize(NormalizeArgs a, int nph, int matrix_mat, long nvox, int nz, long pitch) {
+  // nvox < 2^32 (launch_vox_normalize): the row of a voxel by a 32-bit division; only the padded offset needs 64 bits
+  const unsigned o = blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= nvox) return;
+  const unsigned row = o / (unsigned)nz;
+  const size_t d = (size_t)row * (size_t)pitch + (o - row * (unsigned)nz);
+  double rem = 1.0;
+#pragma unroll
+  for (int m = fg::kMaxPhases - 1; m >= 0; --m) {
+    if (m < nph) {
+      const double v = m == matrix_mat ? 1.0 : a.in[m][o];
+      const double vol = fmin(rem, v);
+      a.out[m][d] = vol;
+      rem = rem - vol;
+    }
   }
 }
 
@@ -376,24 +405,226 @@ V3 any_orthonormal(V3 v) {
   return (1.0 / norm(w)) * w;
 }
 
+// device memory of the current device; copies and memsets go to the stream handed in
 template <class T>
 struct DeviceArray {
   T* p = nullptr;
+  DeviceArray() = default;
+  DeviceArray(const DeviceArray&) = delete;
+  DeviceArray& operator=(const DeviceArray&) = delete;
   ~DeviceArray() {
     if (p) (void)hipFree(p);
   }
   void alloc(size_t n) { FG_HIP_CHECK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T))); }
-  void upload(const std::vector<T>& v) {
+  // the vector must stay alive until the stream has been waited for
+  void upload(const std::vector<T>& v, hipStream_t stream) {
     alloc(v.size());
-    if (!v.empty()) FG_HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    if (!v.empty()) FG_HIP_CHECK(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
   }
 };
 
+std::atomic<int> g_team_depth{-1};   // fg_voxelize_team_depth: -1 = by the number of interface voxels
+
 }  // namespace
 
-namespace {
-std::atomic<int> g_team_depth{-1};   // fg_voxelize_team_depth: -1 = by the number of interface voxels
+namespace fg {
+
+DeviceScope::DeviceScope(int device) {
+  FG_HIP_CHECK(hipGetDevice(&prev_));
+  if (prev_ != device) FG_HIP_CHECK(hipSetDevice(device));
+  else prev_ = -1;
 }
+
+DeviceScope::~DeviceScope() {
+  if (prev_ >= 0) (void)hipSetDevice(prev_);
+}
+
+struct Voxelizer::Impl {
+  std::vector<Shape> shapes;
+  int nphases = 0;
+  // device part
+  VoxGrid g;
+  double x0[3] = {0, 0, 0}, box[3] = {1, 1, 1};   // origin and edges of the cell
+  size_t N = 0;
+  long nbricks = 0;
+  hipStream_t stream = nullptr;
+  DeviceArray<Shape> d_shapes;
+  DeviceArray<unsigned> d_iface, d_count;
+  DeviceArray<int> d_error;
+};
+
+Voxelizer::Voxelizer(const fg_fiber* fibers, int nfibers, int nphases) : impl_(new Impl) {
+  if (nfibers > 0 && !fibers) throw std::runtime_error("fg_voxelize: fibers is NULL");
+  impl_->nphases = nphases;
+  std::vector<Shape>& shapes = impl_->shapes;
+  shapes.resize(std::max(nfibers, 0));
+  for (int i = 0; i < nfibers; ++i) {
+    const fg_fiber& f = fibers[i];
+    Shape& s = shapes[i];
+    s = Shape();
+    s.kind = f.kind;
+    s.material = f.material;
+    if (f.material < 0 || f.material >= nphases) throw std::runtime_error("fg_voxelize: fiber material out of range");
+    const V3 c = mk(f.c[0], f.c[1], f.c[2]), a = mk(f.a[0], f.a[1], f.a[2]);
+    const double na = norm(a);
+    if (f.kind == 0) {
+      // CapsuleFiber(c, a, L0, R)  F:5254-5275: L0 is the length of the cylinder of equal volume, the cylindrical part
+      // of the capsule is L0 - 4/3 R long
+      s.R = std::fabs(f.R);
+      s.L = std::max(0.0, std::fabs(f.L) - (4.0 / 3.0) * s.R);
+      if (na != 0) s.a = (1.0 / na) * a;
+      else if (s.L != 0) throw std::runtime_error("CapsuleFiber: given nonzero fiber length without orientation vector!");
+      else s.a = mk(0, 0, 0);
+      s.c = c;
+      s.c1 = c - (s.L / 2) * s.a;
+      s.B = s.L / 2 + s.R;
+      s.rvec = na != 0 ? s.R * any_orthonormal(s.a) : mk(0, 0, 0);
+    } else if (f.kind == 1) {   // HalfSpaceFiber(p, n)  F:5537-5549
+      if (na == 0) throw std::runtime_error("HalfSpaceFiber: given zero normal vector!");
+      s.n = (1.0 / na) * a;
+      s.p = c;
+    } else {
+      throw std::runtime_error("Unknown fiber type");
+    }
+  }
+}
+
+Voxelizer::~Voxelizer() = default;
+
+int Voxelizer::num_shapes() const { return (int)impl_->shapes.size(); }
+
+void Voxelizer::real_volume(double* out) const {
+  for (int m = 0; m < impl_->nphases; ++m) out[m] = 0.0;
+  for (const Shape& s : impl_->shapes)
+    out[s.material] += s.kind == 1 ? std::numeric_limits<double>::infinity() : M_PI * s.R * s.R * (s.L + 4.0 / 3.0 * s.R);
+}
+
+namespace {
+VoxGrid make_vox_grid(int nx, int ny, int nz, double dx, double dy, double dz, const double* x0) {
+  VoxGrid g;
+  g.nx = nx, g.ny = ny, g.nz = nz;
+  g.hx = dx / nx, g.hy = dy / ny, g.hz = dz / nz;
+  g.x0 = x0[0], g.y0 = x0[1], g.z0 = x0[2];
+  g.r0 = 0.5 * std::sqrt(g.hx * g.hx + g.hy * g.hy + g.hz * g.hz);
+  g.bx = (nx + kBrick - 1) / kBrick, g.by = (ny + kBrick - 1) / kBrick, g.bz = (nz + kBrick - 1) / kBrick;
+  return g;
+}
+}  // namespace
+
+void Voxelizer::begin(int nx, int ny, int nz, double dx, double dy, double dz, const double* x0, hipStream_t stream) {
+  Impl& v = *impl_;
+  v.g = make_vox_grid(nx, ny, nz, dx, dy, dz, x0);
+  for (int a = 0; a < 3; ++a) v.x0[a] = x0[a];
+  v.box[0] = dx, v.box[1] = dy, v.box[2] = dz;
+  v.N = (size_t)nx * ny * nz;
+  v.nbricks = (long)v.g.bx * v.g.by * v.g.bz;
+  v.stream = stream;
+  if (v.N >= (1ull << 32)) throw std::runtime_error("fg_voxelize: grid too large");
+  v.d_shapes.upload(v.shapes, stream);
+  v.d_iface.alloc(v.N);
+  v.d_count.alloc(1);
+  v.d_error.alloc(1);
+  FG_HIP_CHECK(hipMemsetAsync(v.d_error.p, 0, sizeof(int), stream));
+}
+
+void Voxelizer::material(int m, int smooth_levels, double smooth_tol, double* d_phi) {
+  Impl& v = *impl_;
+  const VoxGrid& g = v.g;
+  const std::vector<Shape>& shapes = v.shapes;
+  const double* x0 = v.x0;
+  const long nbricks = v.nbricks;
+  hipStream_t stream = v.stream;
+  // candidate shapes of every brick: bounding ball within (brick half diagonal + r0) of the brick centre
+  std::vector<std::vector<int>> per_brick(nbricks);
+  const double ebx = kBrick * g.hx, eby = kBrick * g.hy, ebz = kBrick * g.hz;
+  const double rb = 0.5 * std::sqrt(ebx * ebx + eby * eby + ebz * ebz) + g.r0;
+  for (int si = 0; si < (int)shapes.size(); ++si) {
+    const Shape& s = shapes[si];
+    if (s.material != m) continue;
+    int lo[3] = {0, 0, 0}, hi[3] = {g.bx - 1, g.by - 1, g.bz - 1};
+    if (s.kind == 0) {
+      const double reach = s.B + g.r0;
+      const double cc[3] = {s.c.x - x0[0], s.c.y - x0[1], s.c.z - x0[2]}, eb[3] = {ebx, eby, ebz};
+      for (int a = 0; a < 3; ++a) {
+        lo[a] = std::max(lo[a], (int)std::floor((cc[a] - reach) / eb[a]) - 1);
+        hi[a] = std::min(hi[a], (int)std::floor((cc[a] + reach) / eb[a]) + 1);
+      }
+    }
+    for (int bi = lo[0]; bi <= hi[0]; ++bi)
+      for (int bj = lo[1]; bj <= hi[1]; ++bj)
+        for (int bk = lo[2]; bk <= hi[2]; ++bk) {
+          const V3 bc = mk(x0[0] + (bi + 0.5) * ebx, x0[1] + (bj + 0.5) * eby, x0[2] + (bk + 0.5) * ebz);
+          if (s.kind == 0 && norm(bc - s.c) - s.B > rb) continue;
+          per_brick[((long)bi * g.by + bj) * g.bz + bk].push_back(si);
+        }
+  }
+  std::vector<int> start(nbricks + 1, 0), list;
+  for (long b = 0; b < nbricks; ++b) {
+    start[b] = (int)list.size();
+    list.insert(list.end(), per_brick[b].begin(), per_brick[b].end());
+  }
+  start[nbricks] = (int)list.size();
+  DeviceArray<int> d_start, d_list;
+  d_start.upload(start, stream);
+  d_list.upload(list, stream);
+  FG_HIP_CHECK(hipMemsetAsync(v.d_count.p, 0, sizeof(unsigned), stream));
+  hipLaunchKernelGGL(k_vox_classify, dim3((unsigned)nbricks), dim3(kBrick * kBrick * kBrick), 0, stream, g, v.d_shapes.p, d_start.p,
+                     d_list.p, d_phi, v.d_iface.p, v.d_count.p);
+  FG_HIP_CHECK(hipGetLastError());
+  unsigned n_iface = 0;
+  FG_HIP_CHECK(hipMemcpyAsync(&n_iface, v.d_count.p, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+  FG_HIP_CHECK(hipStreamSynchronize(stream));
+  if (n_iface) {
+    // threads per interface voxel: 8^depth, so that a coarse grid still fills the device (fg_voxelize_team_depth: test hook)
+    int depth = n_iface <= 2048 ? 3 : n_iface <= 16384 ? 2 : n_iface <= 65536 ? 1 : 0;
+    if (const int forced = g_team_depth.load(); forced >= 0) depth = forced;
+    if (smooth_levels >= 0) depth = std::min(depth, smooth_levels);
+#define FG_REFINE(KERNEL, BLOCKS, THREADS)                                                                                  \
+  hipLaunchKernelGGL(KERNEL, dim3(BLOCKS), dim3(THREADS), 0, stream, g, v.d_shapes.p, d_start.p, d_list.p, v.d_iface.p, n_iface, \
+                     smooth_levels, smooth_tol, d_phi, v.d_error.p)
+    if (depth == 3) FG_REFINE(k_vox_refine_team<3>, n_iface, 512);
+    else if (depth == 2) FG_REFINE(k_vox_refine_team<2>, n_iface, 64);
+    else if (depth == 1) FG_REFINE(k_vox_refine_team<1>, (n_iface + 7) / 8, 64);
+    else FG_REFINE(k_vox_refine, (n_iface + 63) / 64, 64);
+#undef FG_REFINE
+    FG_HIP_CHECK(hipGetLastError());
+    FG_HIP_CHECK(hipStreamSynchronize(stream));   // the brick lists go with this scope
+  }
+}
+
+void Voxelizer::check_refinement() {
+  Impl& v = *impl_;
+  int herr = 0;
+  FG_HIP_CHECK(hipMemcpyAsync(&herr, v.d_error.p, sizeof(int), hipMemcpyDeviceToHost, v.stream));
+  FG_HIP_CHECK(hipStreamSynchronize(v.stream));
+  if (herr) throw std::runtime_error("fg_voxelize: interface refinement exceeded 20 levels (shapes far below the voxel size?)");
+}
+
+void Voxelizer::normals(int nx, int ny, int nz, double* d_normals, long row_pitch, long comp_stride) {
+  Impl& v = *impl_;
+  const VoxGrid g = make_vox_grid(nx, ny, nz, v.box[0], v.box[1], v.box[2], v.x0);
+  const size_t N = (size_t)nx * ny * nz;
+  hipLaunchKernelGGL(k_vox_normals, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, v.stream, g, v.d_shapes.p,
+                     (int)v.shapes.size(), d_normals, row_pitch, comp_stride);
+  FG_HIP_CHECK(hipGetLastError());
+}
+
+void launch_vox_normalize(const double* const* in, double* const* out, int nphases, int matrix_mat, long nvox, int nz,
+                          long row_pitch, hipStream_t stream) {
+  if (nphases < 1 || nphases > fg::kMaxPhases) throw std::runtime_error("number of phases must be in [1, 8]");
+  // (the last block's thread index stays below 2^32)
+  if (nvox < 0 || nvox > (1L << 32) - 256 || nz < 1) throw std::runtime_error("fg_voxelize: grid too large");
+  NormalizeArgs a;
+  for (int m = 0; m < fg::kMaxPhases; ++m) {
+    a.in[m] = m < nphases ? in[m] : nullptr;
+    a.out[m] = m < nphases ? out[m] : nullptr;
+  }
+  hipLaunchKernelGGL(k_vox_normalize, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, stream, a, nphases, matrix_mat, nvox, nz,
+                     row_pitch);
+  FG_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace fg
 
 extern "C" int fg_voxelize_team_depth(int depth) { return g_team_depth.exchange(depth < 0 ? -1 : std::min(depth, 3)); }
 
@@ -406,142 +637,36 @@ extern "C" int fg_voxelize(const fg_fiber* fibers, int nfibers, int nx, int ny, 
   };
   try {
     if (nx < 1 || ny < 1 || nz < 1 || nphases < 1 || !phi || !x0) return fail("fg_voxelize: bad arguments");
-    if (nfibers > 0 && !fibers) return fail("fg_voxelize: fibers is NULL");
-    std::vector<Shape> shapes(nfibers);
-    for (int i = 0; i < nfibers; ++i) {
-      const fg_fiber& f = fibers[i];
-      Shape& s = shapes[i];
-      s = Shape();
-      s.kind = f.kind;
-      s.material = f.material;
-      if (f.material < 0 || f.material >= nphases) return fail("fg_voxelize: fiber material out of range");
-      const V3 c = mk(f.c[0], f.c[1], f.c[2]), a = mk(f.a[0], f.a[1], f.a[2]);
-      const double na = norm(a);
-      if (f.kind == 0) {
-        // CapsuleFiber(c, a, L0, R)  F:5254-5275: L0 is the length of the cylinder of equal volume, the cylindrical part
-        // of the capsule is L0 - 4/3 R long
-        s.R = std::fabs(f.R);
-        s.L = std::max(0.0, std::fabs(f.L) - (4.0 / 3.0) * s.R);
-        if (na != 0) s.a = (1.0 / na) * a;
-        else if (s.L != 0) return fail("CapsuleFiber: given nonzero fiber length without orientation vector!");
-        else s.a = mk(0, 0, 0);
-        s.c = c;
-        s.c1 = c - (s.L / 2) * s.a;
-        s.B = s.L / 2 + s.R;
-        s.rvec = na != 0 ? s.R * any_orthonormal(s.a) : mk(0, 0, 0);
-      } else if (f.kind == 1) {   // HalfSpaceFiber(p, n)  F:5537-5549
-        if (na == 0) return fail("HalfSpaceFiber: given zero normal vector!");
-        s.n = (1.0 / na) * a;
-        s.p = c;
-      } else {
-        return fail("Unknown fiber type");
-      }
-    }
-    if (real_volume) {
-      for (int m = 0; m < nphases; ++m) real_volume[m] = 0.0;
-      for (const Shape& s : shapes)
-        real_volume[s.material] += s.kind == 1 ? std::numeric_limits<double>::infinity() : M_PI * s.R * s.R * (s.L + 4.0 / 3.0 * s.R);
-    }
+    fg::Voxelizer vox(fibers, nfibers, nphases);
+    if (real_volume) vox.real_volume(real_volume);
     int ndev = 0;
     FG_HIP_CHECK(hipGetDeviceCount(&ndev));
     if (ndev < 1) return fail("no HIP device available: fibergen_amd needs an AMD GPU (gfx950)");
     if (device < 0 || device >= ndev) return fail("invalid device index");
     FG_HIP_CHECK(hipSetDevice(device));
 
-    VoxGrid g;
-    g.nx = nx, g.ny = ny, g.nz = nz;
-    g.hx = dx / nx, g.hy = dy / ny, g.hz = dz / nz;
-    g.x0 = x0[0], g.y0 = x0[1], g.z0 = x0[2];
-    g.r0 = 0.5 * std::sqrt(g.hx * g.hx + g.hy * g.hy + g.hz * g.hz);
-    g.bx = (nx + kBrick - 1) / kBrick, g.by = (ny + kBrick - 1) / kBrick, g.bz = (nz + kBrick - 1) / kBrick;
     const size_t N = (size_t)nx * ny * nz;
-    const long nbricks = (long)g.bx * g.by * g.bz;
-    if (N >= (1ull << 32)) return fail("fg_voxelize: grid too large");
-
-    DeviceArray<Shape> d_shapes;
-    d_shapes.upload(shapes);
+    hipStream_t stream = nullptr;   // the default stream: every copy below blocks the host
+    vox.begin(nx, ny, nz, dx, dy, dz, x0, stream);
     DeviceArray<double> d_phi;
     d_phi.alloc(N);
-    DeviceArray<unsigned> d_iface, d_count;
-    d_iface.alloc(N);
-    d_count.alloc(1);
-    DeviceArray<int> d_error;
-    d_error.alloc(1);
-    FG_HIP_CHECK(hipMemset(d_error.p, 0, sizeof(int)));
-
     for (int m = 0; m < nphases; ++m) {
       double* out = phi + (size_t)m * N;
       if (m == matrix_mat) {   // the matrix is present everywhere until normalizePhi hands it the remainder
         std::fill(out, out + N, 1.0);
         continue;
       }
-      // candidate shapes of every brick: bounding ball within (brick half diagonal + r0) of the brick centre
-      std::vector<std::vector<int>> per_brick(nbricks);
-      const double ebx = kBrick * g.hx, eby = kBrick * g.hy, ebz = kBrick * g.hz;
-      const double rb = 0.5 * std::sqrt(ebx * ebx + eby * eby + ebz * ebz) + g.r0;
-      for (int si = 0; si < nfibers; ++si) {
-        const Shape& s = shapes[si];
-        if (s.material != m) continue;
-        int lo[3] = {0, 0, 0}, hi[3] = {g.bx - 1, g.by - 1, g.bz - 1};
-        if (s.kind == 0) {
-          const double reach = s.B + g.r0;
-          const double cc[3] = {s.c.x - x0[0], s.c.y - x0[1], s.c.z - x0[2]}, eb[3] = {ebx, eby, ebz};
-          for (int a = 0; a < 3; ++a) {
-            lo[a] = std::max(lo[a], (int)std::floor((cc[a] - reach) / eb[a]) - 1);
-            hi[a] = std::min(hi[a], (int)std::floor((cc[a] + reach) / eb[a]) + 1);
-          }
-        }
-        for (int bi = lo[0]; bi <= hi[0]; ++bi)
-          for (int bj = lo[1]; bj <= hi[1]; ++bj)
-            for (int bk = lo[2]; bk <= hi[2]; ++bk) {
-              const V3 bc = mk(x0[0] + (bi + 0.5) * ebx, x0[1] + (bj + 0.5) * eby, x0[2] + (bk + 0.5) * ebz);
-              if (s.kind == 0 && norm(bc - s.c) - s.B > rb) continue;
-              per_brick[((long)bi * g.by + bj) * g.bz + bk].push_back(si);
-            }
-      }
-      std::vector<int> start(nbricks + 1, 0), list;
-      for (long b = 0; b < nbricks; ++b) {
-        start[b] = (int)list.size();
-        list.insert(list.end(), per_brick[b].begin(), per_brick[b].end());
-      }
-      start[nbricks] = (int)list.size();
-      DeviceArray<int> d_start, d_list;
-      d_start.upload(start);
-      d_list.upload(list);
-      FG_HIP_CHECK(hipMemset(d_count.p, 0, sizeof(unsigned)));
-      hipLaunchKernelGGL(k_vox_classify, dim3((unsigned)nbricks), dim3(kBrick * kBrick * kBrick), 0, 0, g, d_shapes.p, d_start.p,
-                         d_list.p, d_phi.p, d_iface.p, d_count.p);
-      FG_HIP_CHECK(hipGetLastError());
-      unsigned n_iface = 0;
-      FG_HIP_CHECK(hipMemcpy(&n_iface, d_count.p, sizeof(unsigned), hipMemcpyDeviceToHost));
-      if (n_iface) {
-        // threads per interface voxel: 8^depth, so that a coarse grid still fills the device (fg_voxelize_team_depth: test hook)
-        int depth = n_iface <= 2048 ? 3 : n_iface <= 16384 ? 2 : n_iface <= 65536 ? 1 : 0;
-        if (const int forced = g_team_depth.load(); forced >= 0) depth = forced;
-        if (smooth_levels >= 0) depth = std::min(depth, smooth_levels);
-#define FG_REFINE(KERNEL, BLOCKS, THREADS)                                                                                   \
-  hipLaunchKernelGGL(KERNEL, dim3(BLOCKS), dim3(THREADS), 0, 0, g, d_shapes.p, d_start.p, d_list.p, d_iface.p, n_iface, \
-                     smooth_levels, smooth_tol, d_phi.p, d_error.p)
-        if (depth == 3) FG_REFINE(k_vox_refine_team<3>, n_iface, 512);
-        else if (depth == 2) FG_REFINE(k_vox_refine_team<2>, n_iface, 64);
-        else if (depth == 1) FG_REFINE(k_vox_refine_team<1>, (n_iface + 7) / 8, 64);
-        else FG_REFINE(k_vox_refine, (n_iface + 63) / 64, 64);
-#undef FG_REFINE
-        FG_HIP_CHECK(hipGetLastError());
-      }
+      vox.material(m, smooth_levels, smooth_tol, d_phi.p);
       FG_HIP_CHECK(hipMemcpy(out, d_phi.p, N * sizeof(double), hipMemcpyDeviceToHost));
     }
-    int herr = 0;
-    FG_HIP_CHECK(hipMemcpy(&herr, d_error.p, sizeof(int), hipMemcpyDeviceToHost));
-    if (herr) return fail("fg_voxelize: interface refinement exceeded 20 levels (shapes far below the voxel size?)");
+    vox.check_refinement();
     if (normals) {
-      if (shapes.empty()) {
+      if (vox.num_shapes() == 0) {
         std::fill(normals, normals + 3 * N, 0.0);
       } else {
         DeviceArray<double> d_n;
         d_n.alloc(3 * N);
-        hipLaunchKernelGGL(k_vox_normals, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, g, d_shapes.p, nfibers, d_n.p);
-        FG_HIP_CHECK(hipGetLastError());
+        vox.normals(nx, ny, nz, d_n.p, nz, (long)N);
         FG_HIP_CHECK(hipMemcpy(normals, d_n.p, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
       }
     }

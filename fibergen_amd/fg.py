@@ -46,6 +46,10 @@ class _Fiber:
 class FG:
     """The fibergen solver class (reference: PyFG, F:26785-26851)."""
 
+    # <place_fiber> geometry is voxelised and normalised inside the solver (fg_voxelize_into); False: through host arrays
+    # (geometry.voxelize, _normalize_phi, set_phase / set_normals), as slabs and raw data always go.  Same results bit for bit.
+    device_geometry = True
+
     def __init__(self, device=0):
         self._device = device
         self._shard = False
@@ -81,8 +85,9 @@ class FG:
         self._phase_names = []
         self._phase_materials = []
         self._matrix_mat = 0
-        self._phi = None        # host copy of the phase fields [nphase][nx][ny][nz]
+        self._phi = None        # host copy of the phase fields [nphase][nx][ny][nz] (_host_phi)
         self._normals = None
+        self._phi_on_device = self._normals_on_device = False   # the solver holds fields the host copies above lack
         self._raw_normals = None
         self._want_normals = False
         self._method = "cg"
@@ -399,6 +404,12 @@ class FG:
         """FG::init_phase  F:25026-25038: discretise the geometry into phase fractions (+ normals)."""
         if self._phase_valid:
             return
+        # a geometry kept only in the solver so far: its normals become the host copy every later step starts from, as if
+        # they had come through host arrays; from here on the marks describe the geometry about to be made.  The fetch is
+        # a deliberate device-to-host copy of one normals field per re-init after a device-path geometry, paid even where
+        # the next geometry overwrites it: the host path lets stale normals survive a re-init, and so does this one
+        self._host_normals()
+        self._phi_on_device = self._normals_on_device = False
         self.init_lss()
         lss = self._lss
         shape = lss.shape
@@ -421,12 +432,28 @@ class FG:
         # full_staggered: <place_fiber> geometry is voxelised on the doubly fine grid and normalised there (initPhi under
         # select_dfg(true) F:17152-17230); the solver keeps the coarse 8-cell means and the staggered fractions of the image
         fine = getattr(self, "_scheme", "staggered") in ("full_staggered", "full-staggered") and not self._raw_phase
+        levels, tol = self._solver_int("smooth_levels", -1), self._solver_float("smooth_tol", 0.001)
+        # placed shapes go straight into the solver's device fields (fg_voxelize_into): no host image, no NumPy sweep, no
+        # upload; host copies of phi and the normals are fetched when somebody asks (_host_phi, _host_normals).  Which
+        # normals the solver ends up with is decided exactly as on the host path below.
+        if self.device_geometry and not self._raw_phase and type(lss) is LSSolver:
+            vox_normals = self._want_normals or (self._mixing == "laminate" and not fine)
+            self._real_vf = lss.voxelize_into(self._fibers, self._x0, self._matrix_mat, want_normals=vox_normals, fine=fine,
+                                              smooth_levels=levels, smooth_tol=tol)
+            self._phi, self._phi_on_device = None, True
+            if vox_normals:
+                self._normals, self._normals_on_device = None, True
+            elif self._normals is not None:
+                lss.set_normals(self._normals)
+            elif self._mixing == "laminate":
+                raise RuntimeError("laminate mixing needs interface normals (init_phase normals=\"1\" or set_normals)")
+            self._phase_valid = True
+            return
         if fine:
             from . import geometry
             fshape = tuple(2 * n for n in shape)
             phif, _n, real_vf = geometry.voxelize(self._fibers, fshape, self._dims, self._x0, nph, self._matrix_mat,
-                                                  want_normals=False, smooth_levels=self._solver_int("smooth_levels", -1),
-                                                  smooth_tol=self._solver_float("smooth_tol", 0.001), device=self._device)
+                                                  want_normals=False, smooth_levels=levels, smooth_tol=tol, device=self._device)
             phif = _normalize_phi(phif)
             self._real_vf = real_vf
             if self._want_normals:
@@ -443,9 +470,7 @@ class FG:
             from . import geometry
             phi, normals, real_vf = geometry.voxelize(self._fibers, shape, self._dims, self._x0, nph, self._matrix_mat,
                                                       want_normals=(self._want_normals or self._mixing == "laminate"),
-                                                      smooth_levels=self._solver_int("smooth_levels", -1),
-                                                      smooth_tol=self._solver_float("smooth_tol", 0.001),
-                                                      device=self._device)
+                                                      smooth_levels=levels, smooth_tol=tol, device=self._device)
             if normals is not None:
                 self._normals = normals
             self._real_vf = real_vf
@@ -459,6 +484,18 @@ class FG:
         elif self._mixing == "laminate":
             raise RuntimeError("laminate mixing needs interface normals (init_phase normals=\"1\" or set_normals)")
         self._phase_valid = True
+
+    def _host_phi(self):
+        """host copy of the phase fields [nphase][nx][ny][nz]; after the device path it is fetched on first use"""
+        if self._phi is None and self._phi_on_device:
+            self._phi = self._lss.get_field("phi")
+        return self._phi
+
+    def _host_normals(self):
+        """host copy of the normals [3][nx][ny][nz] or None (see _host_phi)"""
+        if self._normals is None and self._normals_on_device:
+            self._normals = self._lss.get_field("normals")
+        return self._normals
 
     def _solver_float(self, key, default):
         return self._child_value(self._settings().find("solver"), key, default)
@@ -973,11 +1010,12 @@ class FG:
             nx, ny, nz = self._lss.shape
             cols = [np.repeat(np.arange(nx), ny * nz), np.tile(np.repeat(np.arange(ny), nz), nx), np.tile(np.arange(nz), nx * ny)]
             head = ["i_x", "i_y", "i_z"]
-            if self._normals is not None:
+            normals, phi = self._host_normals(), self._host_phi()
+            if normals is not None:
                 head += ["n_x", "n_y", "n_z"]
-                cols += [np.asarray(self._normals[c]).reshape(-1) for c in range(3)]
+                cols += [np.asarray(normals[c]).reshape(-1) for c in range(3)]
             head += list(self._phase_names)
-            cols += [np.asarray(self._phi[m]).reshape(-1) for m in range(len(self._phase_names))]
+            cols += [np.asarray(phi[m]).reshape(-1) for m in range(len(self._phase_names))]
             # (the reference adds a_x a_y a_z when the solver holds an orientation field, F:17091-17093: the projects of this
             # path never do -- the field belongs to the fibre-orientation materials outside SURVEY 8)
             table = np.column_stack(cols)

@@ -1,6 +1,7 @@
 """Geometry pre-processing of the project layer: shapes placed with <place_fiber> ->
 phase volume fractions + interface normals, through the GPU voxeliser fg_voxelize
-(fibergen_amd/csrc/fg_voxelize.hip).  No CPU fallback: without a GPU it fails loudly."""
+(fibergen_amd/csrc/fg_voxelize.hip).  No CPU fallback: without a GPU it fails loudly.
+voxelize() returns host arrays; LSSolver.voxelize_into (fg_voxelize_into) leaves the same fields in the solver."""
 from __future__ import annotations
 
 import ctypes
@@ -12,11 +13,8 @@ from . import _lib
 KINDS = {"capsule": 0, "halfspace": 1}
 
 
-def voxelize(fibers, shape, dims, x0, nphases, matrix_mat, want_normals=False, smooth_levels=-1, smooth_tol=1e-3,
-             device=0):
-    """Returns (phi[nphases,nx,ny,nz] before normalisation, normals[3,...] or None, {material: real volume fraction})."""
-    lib = _lib.load()
-    nx, ny, nz = shape
+def fiber_array(fibers):
+    """The placed shapes as the fg_fiber array the C ABI takes (at least one element, so that the pointer is valid)."""
     arr = (_lib.FgFiber * max(len(fibers), 1))()
     for i, f in enumerate(fibers):
         arr[i].kind = KINDS[f.kind]
@@ -26,6 +24,15 @@ def voxelize(fibers, shape, dims, x0, nphases, matrix_mat, want_normals=False, s
             arr[i].a[k] = float(f.a[k])
         arr[i].L = float(f.L)
         arr[i].R = float(f.R)
+    return arr
+
+
+def voxelize(fibers, shape, dims, x0, nphases, matrix_mat, want_normals=False, smooth_levels=-1, smooth_tol=1e-3,
+             device=0):
+    """Returns (phi[nphases,nx,ny,nz] before normalisation, normals[3,...] or None, {material: real volume fraction})."""
+    lib = _lib.load()
+    nx, ny, nz = shape
+    arr = fiber_array(fibers)
     phi = np.zeros((nphases, nx, ny, nz))
     normals = np.zeros((3, nx, ny, nz)) if want_normals else None
     real = np.zeros(nphases)

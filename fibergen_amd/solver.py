@@ -93,6 +93,22 @@ class LSSolver:
             raise ValueError("normals must have shape %r" % ((3,) + self.shape,))
         self._check(self._lib.fg_set_normals(self._h, _dp(normals)))
 
+    def voxelize_into(self, fibers, x0, matrix_mat, want_normals=False, fine=False, smooth_levels=-1, smooth_tol=1e-3):
+        """fg_voxelize_into: the placed shapes (objects with kind, material, c, a, L, R as geometry.voxelize takes them) are
+        voxelised and normalised on the device, straight into this solver's phase fields (fine: on the doubly fine grid,
+        gamma_scheme full_staggered) and, with want_normals, its normals.  Returns {material: real volume fraction}."""
+        from . import geometry
+        arr = geometry.fiber_array(fibers)
+        x0a = np.ascontiguousarray(x0, dtype=np.float64)
+        if x0a.shape != (3,):
+            raise ValueError("x0 must have 3 entries")
+        real = np.zeros(max(self.nphases, 1))
+        flags = (_lib.FG_VOX_NORMALS if want_normals else 0) | (_lib.FG_VOX_FINE if fine else 0)
+        self._check(self._lib.fg_voxelize_into(self._h, arr, len(fibers), _dp(x0a), int(matrix_mat), int(smooth_levels),
+                                               float(smooth_tol), flags, _dp(real)))
+        vol = self.dx * self.dy * self.dz
+        return {m: real[m] / vol for m in range(self.nphases)}
+
     def set_options(self, **kw):
         for k, v in kw.items():
             if k == "mixing_rule":
@@ -186,7 +202,8 @@ class LSSolver:
     def counter(self, name):
         """fg_get_counter: "interface_voxels", "affected_voxels" (lengths of the laminate lists); "fft_path_x|y|z" (how the axis
         is transformed: 0 length 1, 1 power of two, 2 sub-lines p * 2^k, 3 tile kernels, 4 Bluestein, 5 O(n^2)),
-        "fft_bluestein_m_x|y|z" (padded length of the axis' Bluestein pass, 0 = not on Bluestein); -1 = unknown name."""
+        "fft_bluestein_m_x|y|z" (padded length of the axis' Bluestein pass, 0 = not on Bluestein), "phase_uploads" (host
+        arrays received by set_phase / set_phase_fine / set_normals); -1 = unknown name."""
         return int(self._lib.fg_get_counter(self._h, name.encode()))
 
     def iterate(self, E, n):

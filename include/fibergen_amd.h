@@ -209,8 +209,9 @@ int fg_get_stage_timing_bias(const fg_solver* s, double* ms);
  * them); "pair_chunk_planes" = x planes per chunk of the paired z / y transform passes (option pair_chunk; 0 = whole-field
  * passes: stage timing then reports each pair in the slot of its first pass); "fft_path_x" / "_y" / "_z" = how the axis is
  * transformed: 0 length 1, 1 power of two, 2 sub-lines p * 2^k, 3 tile kernels, 4 Bluestein, 5 O(n^2) sums;
- * "fft_bluestein_m_x" / "_y" / "_z" = the padded length of the axis' Bluestein pass (0: the axis is not on Bluestein).
- * Unknown names give -1. */
+ * "fft_bluestein_m_x" / "_y" / "_z" = the padded length of the axis' Bluestein pass (0: the axis is not on Bluestein);
+ * "phase_uploads" = host arrays this solver has received through fg_set_phase (with a field), fg_set_phase_field_fine and
+ * fg_set_normals (fg_voxelize_into adds none).  Unknown names give -1. */
 long fg_get_counter(const fg_solver* s, const char* name);
 
 /* Measurement helper (no counterpart in the reference): achieved HBM bandwidth of a streaming copy a = b and of the
@@ -335,6 +336,27 @@ int fg_voxelize(const fg_fiber* fibers, int nfibers, int nx, int ny, int nz, dou
  * follow in this process, depth 0 ... 3; -1 (the default) = chosen from the number of interface voxels.  Every depth gives
  * bit-identical fractions (tests/test_gpu_voxelize.py).  Returns the previous setting. */
 int fg_voxelize_team_depth(int depth);
+
+/* FG::init_phase F:25026-25038 for placed shapes without the host in between: the shapes are voxelised (initPhi
+ * F:17489-17581, the kernels of fg_voxelize in the same order) on the solver's device and stream, normalised there
+ * (normalizePhi F:17588-17646: walking the materials from last to first each takes min(remaining, phi), the matrix material
+ * `matrix_mat` entering as the constant 1) and written straight into the solver's phase fields; no field-sized data crosses
+ * to the host.  Cell, grid and the number of phases are the solver's (fg_create, fg_set_num_phases); x0 is the cell's origin.
+ * flags: FG_VOX_NORMALS also writes the interface normals (NORMALS sampling F:6905-6925; all zero without shapes) as
+ * fg_set_normals would; FG_VOX_FINE (gamma_scheme 2 only) voxelises and normalises on the doubly fine grid
+ * [2nx][2ny][2nz] (initPhi after select_dfg(true) F:17152-17230) and reduces every phase as fg_set_phase_field_fine does,
+ * the normals staying on the solver's own grid.  The solver is left exactly as nphases calls of fg_set_phase with a field
+ * (resp. fg_set_phase_field_fine) and fg_set_normals on the host-normalised output of fg_voxelize leave it, bit for bit.
+ * real_volume (may be NULL) receives the analytic volume per phase.  Errors (fg_last_error) carry fg_voxelize's texts: bad
+ * arguments, material out of range, zero normal, capsule without orientation, refinement beyond 20 levels; slab-decomposed
+ * solvers are refused.  The caller's current HIP device is restored on return.  Device memory during the call, freed before
+ * it returns: one dense image per non-matrix phase, (nphases - 1) * nxyz doubles; with FG_VOX_FINE one fine image per phase,
+ * nphases * 8 nxyz doubles (the normalisation needs all phases of a voxel at once: 25.8 GB for three phases at 512^3, where
+ * the host path holds one fine image on the device and the others in host memory), plus 4 bytes per voxelised cell. */
+#define FG_VOX_NORMALS 1
+#define FG_VOX_FINE 2
+int fg_voxelize_into(fg_solver* s, const fg_fiber* fibers, int nfibers, const double* x0 /* [3] */, int matrix_mat,
+                     int smooth_levels, double smooth_tol, int flags, double* real_volume /* [nphases] or NULL */);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,12 @@
-"""Where the set-up time of FG.run() goes: the Hashin demo project run three times in one process.
-    python tools/setup_cost.py [n=64]
+"""Where the set-up time of FG.run() goes: a <place_fiber> project run four times in one process.
+    python tools/setup_cost.py [n=64] [--device-geometry 0|1] [--project hashin|capsules] [--skip-create]
 Prints per run: wall time of run(), the solver's own solve time (six load cases), and the difference = set-up (project layer,
-voxeliser, fg_create, phase upload); then the cost of fg_create + fg_destroy alone for a few grids (first and later calls)."""
+voxeliser, fg_create, phase upload), then its breakdown: parse (set_xml), create (settings + fg_create), voxelise, normalise,
+upload (clocks this tool wraps around geometry.voxelize, _normalize_phi, LSSolver.set_phase / set_phase_fine / set_normals
+and LSSolver.voxelize_into; with --device-geometry 1 the three are that one call, booked under voxelise), solve, rest.
+--project capsules places the 126 capsules of bench_rve_parameters(n).  Then the cost of fg_create + fg_destroy alone for a
+few grids (first and later calls)."""
+import argparse
 import os
 import sys
 import time
@@ -19,19 +24,77 @@ def project(n):
       <calc_effective_properties /></actions></settings>""" % (n, n, n)
 
 
+def capsule_project(n):
+    """the capsules of the benchmark family (bench_rve_parameters) as <place_fiber> actions; L is the equal-volume length"""
+    from fibergen_amd.rve import bench_rve_parameters, place_capsules
+    par = bench_rve_parameters(n)
+    centres, axes = place_capsules(par["K"], par["R"], par["L"])
+    L = par["L"] - 2 * par["R"] + 4 / 3 * par["R"]
+    fibers = "".join('<place_fiber type="capsule" cx="%r" cy="%r" cz="%r" ax="%r" ay="%r" az="%r" L="%r" R="%r" />'
+                     % (*[float(v) for v in c], *[float(v) for v in a], float(L), float(par["R"])) for c, a in zip(centres, axes))
+    return """<settings><solver nx="%d" ny="%d" nz="%d"><tol>1e-5</tol><method>cg</method><mixing_rule>voigt</mixing_rule>
+      <materials><matrix E="1" nu="0.3" /><fiber E="10" nu="0.2" /></materials></solver>
+      <actions><select_material name="fiber" />%s<calc_effective_properties /></actions></settings>""" % (n, n, n, fibers)
+
+
+CLOCKS = {"voxelise": 0.0, "normalise": 0.0, "upload": 0.0}
+
+
+def clocked(fn, key):
+    def wrapper(*a, **kw):
+        t0 = time.perf_counter()
+        try:
+            return fn(*a, **kw)
+        finally:
+            CLOCKS[key] += time.perf_counter() - t0
+    return wrapper
+
+
+def install_clocks():
+    """the pieces of FG.init_phase, timed from outside"""
+    from fibergen_amd import LSSolver, geometry
+    from fibergen_amd import fg as fg_module
+    geometry.voxelize = clocked(geometry.voxelize, "voxelise")
+    fg_module._normalize_phi = clocked(fg_module._normalize_phi, "normalise")
+    LSSolver.voxelize_into = clocked(LSSolver.voxelize_into, "voxelise")
+    for name in ("set_phase", "set_phase_fine", "set_normals"):
+        setattr(LSSolver, name, clocked(getattr(LSSolver, name), "upload"))
+
+
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+    ap = argparse.ArgumentParser()
+    ap.add_argument("n", nargs="?", type=int, default=64)
+    ap.add_argument("--device-geometry", type=int, choices=(0, 1), default=1)
+    ap.add_argument("--project", choices=("hashin", "capsules"), default="hashin")
+    ap.add_argument("--skip-create", action="store_true", help="only the FG.run() part")
+    args = ap.parse_args()
+    n = args.n
     from fibergen_amd import FG, LSSolver
+    xml = project(n) if args.project == "hashin" else capsule_project(n)
+    install_clocks()
     fg = FG()
-    fg.set_xml(project(n))
+    fg.device_geometry = bool(args.device_geometry)
     for i in range(4):
         t0 = time.perf_counter()
-        rc = fg.run()
+        fg.set_xml(xml)
         t1 = time.perf_counter()
-        print("FG.run #%d at %d^3: rc %s, wall %.1f ms, solver %.1f ms, set-up %.1f ms" %
-              (i, n, rc, 1e3 * (t1 - t0), 1e3 * fg.get_solve_time(), 1e3 * (t1 - t0 - fg.get_solve_time())), flush=True)
+        fg.init_lss()
+        for k in CLOCKS:   # (set_phase without a field, inside "create", is no upload)
+            CLOCKS[k] = 0.0
+        t2 = time.perf_counter()
+        rc = fg.run()
+        t3 = time.perf_counter()
+        wall, solve = t3 - t0, fg.get_solve_time()
+        print("FG.run #%d %s at %d^3, device_geometry %d: rc %s, wall %.1f ms, solver %.1f ms, set-up %.1f ms" %
+              (i, args.project, n, args.device_geometry, rc, 1e3 * wall, 1e3 * solve, 1e3 * (wall - solve)), flush=True)
+        parts = [("parse", t1 - t0), ("create", t2 - t1), ("voxelise", CLOCKS["voxelise"]), ("normalise", CLOCKS["normalise"]),
+                 ("upload", CLOCKS["upload"]), ("solve", solve)]
+        parts.append(("rest", wall - sum(v for _, v in parts)))
+        print("    " + ", ".join("%s %.1f" % (k, 1e3 * v) for k, v in parts) + " ms; phase_uploads %d"
+              % fg._lss.counter("phase_uploads"), flush=True)
         fg.reset()
-        fg.set_xml(project(n))
+    if args.skip_create:
+        return
     for g in (32, 64, 128, 256):
         ts = []
         for i in range(4):
