@@ -96,6 +96,15 @@ void launch_u_tile_cg(const Grid& g, double mu_0, double lambda_0, const FieldPt
                       const FieldPtrs<3>& p_new, const FieldPtrs<2>& mod, const FieldPtrs<3>& f, const Vec6& E, const double* sc,
                       int i_num, int i_den, double nvox, double small, double* partial, double* sumsq6, hipStream_t s,
                       const PhaseTable* two_phase);
+// the same two sweeps for two complementary phases of which at least one is a general phase (PhaseTable::law): phi1 = phi_1,
+// tau = (C_0 - C0) : eps + phi_1 (C_1 - C_0) : eps with the full 6 x 6 stiffnesses (k_u_tile ANISO)
+void launch_u_tile_aniso(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& u, const double* phi1,
+                         const FieldPtrs<3>& f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s, bool sum_tau,
+                         const PhaseTable& two_phase);
+void launch_u_tile_aniso_cg(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& p_old, const FieldPtrs<3>& r,
+                            const FieldPtrs<3>& p_new, const double* phi1, const FieldPtrs<3>& f, const Vec6& E, const double* sc,
+                            int i_num, int i_den, double nvox, double small, double* partial, double* sumsq6, hipStream_t s,
+                            const PhaseTable& two_phase);
 void launch_complement_check(const Grid& g, const double* phi0, const double* phi1, int* flag, hipStream_t s);
 // u_k -> sums of squares of eps_k and tau = (C - C0) : eps_k for any mixing rule (strain never stored)
 void launch_u_stress(const Grid& g, const StressParams& sp, const FieldPtrs<3>& u, const FieldPtrs<kMaxPhases>& phi,

@@ -1322,7 +1322,9 @@ __global__ __launch_bounds__(kBlock) void k_set_const6(long n2, FieldPtrs<6> x, 
   }
 }
 
-// min / max of the tangent spectrum over all voxels (reference-material scan)
+// min / max of the tangent spectrum over all voxels (reference-material scan); GENERAL: a phase with a constant 6 x 6
+// stiffness is present (Voigt mixing) and every voxel's tangent is diagonalised (tangent_eigs)
+template <bool GENERAL>
 __global__ __launch_bounds__(kBlock) void k_tangent_minmax(Grid g, PhaseTable pt, int mixing, FieldPtrs<kMaxPhases> phi,
                                                            double* partial, int* error_flag) {
   __shared__ double smem[4 * 2];
@@ -1336,7 +1338,7 @@ __global__ __launch_bounds__(kBlock) void k_tangent_minmax(Grid g, PhaseTable pt
 #pragma unroll
       for (int q = 0; q < kMaxPhases; ++q) ph[q] = q < pt.n ? phi.p[q][p.off + s] : 0.0;
       double lo, hi;
-      if (tangent_eigs<kMaxPhases>(ph, pt, mixing, &lo, &hi) != 0) {
+      if (tangent_eigs<kMaxPhases, GENERAL>(ph, pt, mixing, &lo, &hi) != 0) {
         atomicOr(error_flag, 1);
         continue;
       }
@@ -1889,7 +1891,10 @@ void launch_sum1(const Grid& g, const double* x, double* partial, double* out1, 
 void launch_tangent_minmax(const Grid& g, const PhaseTable& pt, int mixing, const FieldPtrs<kMaxPhases>& phi,
                            double* partial, double* out2, int* error_flag, hipStream_t s) {
   const int nb = reduce_blocks(g);
-  hipLaunchKernelGGL(k_tangent_minmax, dim3(nb), dim3(kBlock), 0, s, g, pt, mixing, phi, partial, error_flag);
+  if (any_general_phase(pt) && mixing == kMixVoigt)
+    hipLaunchKernelGGL(k_tangent_minmax<true>, dim3(nb), dim3(kBlock), 0, s, g, pt, mixing, phi, partial, error_flag);
+  else
+    hipLaunchKernelGGL(k_tangent_minmax<false>, dim3(nb), dim3(kBlock), 0, s, g, pt, mixing, phi, partial, error_flag);
   FG_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_fold<OpMin>, dim3(1), dim3(kBlock), 0, s, partial, nb, 2, 1.0 / 0.0, out2);
   FG_HIP_CHECK(hipGetLastError());

@@ -7,6 +7,7 @@
 #include "fg_kernels.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "fg_hip_util.h"
 #include "fg_kernels_common.h"
@@ -218,22 +219,39 @@ struct CgDirection {
   double nvox, small;
 };
 
+// ANISO: two complementary phases of which at least one has a constant 6 x 6 stiffness (law "general", fg_stage_math.h).  Like
+// PHI2 the sweep reads phi_1 (mod.p[0]) and nothing else, so the bytes per voxel stay at the PHI2 figure; the polarisation is
+//   tau = D0 : eps + phi_1 (D1 : eps),   D0 = C_0 - C0,  D1 = C_1 - C_0   (C0 = the isotropic reference 2 mu_0, lambda_0)
+// with the full 6 x 6 products.  D0 and D1 are symmetric: d0 / d1 hold their upper triangles packed row by row (21 + 21
+// wave-uniform kernel arguments, scalar loads; 72 would not stay in SGPRs), and the factor 2 of the tensor shear strains is
+// applied to the sum over columns 3..5 as in general6.
+struct AnisoLin {
+  double d0[21], d1[21];
+};
+constexpr int aniso_idx(int i, int j) {   // entry (i, j) of a packed symmetric 6 x 6
+  return i <= j ? i * 6 - i * (i - 1) / 2 + (j - i) : j * 6 - j * (j - 1) / 2 + (i - j);
+}
+
 // NMOD = 5: gamma_scheme full_staggered (doubly fine grid): mod = {A_n, B_n, A_23, A_13, A_12}, the moduli of the normal
 // components and of each shear component from its own staggered phase fractions (see fg_kernels_dfg.hip); 3 more 16-byte
 // loads per plane.  NMOD = 2 is the staggered sweep, unchanged.
-template <int TYR, int ZS, bool SUMT, bool PHI2, bool CGP = false, int NMOD = 2>
+template <int TYR, int ZS, bool SUMT, bool PHI2, bool CGP = false, int NMOD = 2, bool ANISO = false>
 __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, double beta, double gamma, FieldPtrs<3> u,
                                                                       FieldPtrs<NMOD> mod, FieldPtrs<3> fo, Vec6 E, double* partial,
-                                                                      int nty, int ntz, int LX, int nt, PhaseLin lin,
+                                                                      int nty, int ntz, int LX, int nt,
+                                                                      std::conditional_t<ANISO, AnisoLin, PhaseLin> lin,
                                                                       CgDirection cg) {
+  static_assert(!ANISO || (PHI2 && NMOD == 2), "the anisotropic form reads phi_1 like PHI2");
   constexpr bool FULLROW = ZS > 0;
   constexpr int NZS = ZS ? ZS : 1;        // waves per row
   constexpr int TYU = TYR - 2;            // rows with output
   constexpr int TZU = FULLROW ? 64 * NZS : 62;  // pairs with output per tile row
   constexpr int RW = NZS * 64;            // LDS entries per row
   extern __shared__ __align__(16) double2 tile_lds[];
-  double2(*Ub)[TYR][RW] = reinterpret_cast<double2(*)[TYR][RW]>(tile_lds);                  // [3][TYR][RW]
-  double2(*Tb)[TYR][RW] = reinterpret_cast<double2(*)[TYR][RW]>(tile_lds + 3 * TYR * RW);   // [3][TYR][RW]
+  // ANISO: the image of u has one more row on either side (the rows before halo row 0 and after the last halo row), UO = 1
+  constexpr int UO = ANISO ? 1 : 0, UR = TYR + 2 * UO;
+  double2(*Ub)[UR][RW] = reinterpret_cast<double2(*)[UR][RW]>(tile_lds);                    // [3][UR][RW]
+  double2(*Tb)[TYR][RW] = reinterpret_cast<double2(*)[TYR][RW]>(tile_lds + 3 * UR * RW);    // [3][TYR][RW]
   // SUMT: also the six sums of the polarisation (<tau> drives the mixed boundary conditions): 12 values per workgroup
   constexpr int NS = SUMT ? 12 : 6;
   __shared__ double red[TYR * NZS * NS];
@@ -267,7 +285,9 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, dou
   const double hx = g.hx, hy = g.hy, hz = g.hz;
   const int nsteps = surplus ? -2 : (x0 + LX <= g.nx ? LX : g.nx - x0);   // surplus: no steps at all
 
-  auto plane = [&](int q) {  // element offset of x plane q (periodic, or the halo planes of an x-slab; q in [-1, 2 nx))
+  // element offset of x plane q (periodic, or the halo planes of an x-slab; q in [-1, 2 nx)).  The anisotropic form also asks for
+  // q = -2: it runs on whole grids only (general phases are refused on slabs), where xw_lo = nx >= 4 wraps any q in [-nx, 0)
+  auto plane = [&](int q) {
     const int x = q < 0 ? q + g.xw_lo : (q >= g.nx ? q - g.xw_hi : q);
     return (long)x * g.nyzp + rowoff;
   };
@@ -309,6 +329,21 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, dou
     }
   }
   double2 dx1 = make_double2(0.0, 0.0), dx2 = dx1;          // U1, U2 minus their previous plane (warm-up: unused)
+  // ANISO: every polarisation component needs all six strains, also where a halo value is formed -- tau_0 of the warm-up plane
+  // needs its e4, e5 (the plane before it), tau_1 of halo row 0 its e3, e5 (u_2, u_0 of the row before it) and tau_3, tau_5 of
+  // the last halo row their e1 (u_1 of the row after it).  The isotropic forms never read these; here they are loaded: two
+  // components of plane x0 - 2 once, and per plane one row of u_0, u_2 (by the waves of row 0) or u_1 (last row), requested with
+  // the moduli and handed over through the two extra rows of the LDS image, so no register outlives the exchange.
+  [[maybe_unused]] long hoff = 0;
+  if constexpr (ANISO) {
+    const long om = plane(x0 - 2);
+    const double2 a1 = load_u(1, om, false), a2 = load_u(2, om, false);
+    dx1.x = uc[1].x - a1.x; dx1.y = uc[1].y - a1.y;
+    dx2.x = uc[2].x - a2.x; dx2.y = uc[2].y - a2.y;
+    const int jh0 = r == 0 ? j - 1 : j + 1;
+    const int jh = jh0 < 0 ? jh0 + g.ny : (jh0 >= g.ny ? jh0 - g.ny : jh0);
+    hoff = (long)jh * g.nzp + 2 * kp - rowoff;
+  }
   double2 t0m = dx1, t5m = dx1, t4m = dx1, part1 = dx1, part2 = dx1;
   double acc[NS];
 #pragma unroll
@@ -334,22 +369,38 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, dou
 #pragma unroll
       for (int c = 0; c < 3; ++c) Sc[c] = ld2(mod.p[2 + c], oq);
     }
+    [[maybe_unused]] double2 ha, hb;
+    if constexpr (ANISO) {   // wave-uniform branches
+      if (r == 0) {
+        ha = load_u(0, oq + hoff, false);
+        hb = load_u(2, oq + hoff, false);
+      }
+      if (r == TYR - 1) ha = load_u(1, oq + hoff, false);
+    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) u2[c] = load_u(c, o2, st + 2 >= 0 && st + 2 < nsteps);
     // ---- y neighbours of u through LDS
 #pragma unroll
-    for (int c = 0; c < 3; ++c) Ub[c][r][li] = uc[c];
+    for (int c = 0; c < 3; ++c) Ub[c][r + UO][li] = uc[c];
+    if constexpr (ANISO) {
+      if (r == 0) {
+        Ub[0][0][li] = ha;
+        Ub[2][0][li] = hb;
+      }
+      if (r == TYR - 1) Ub[1][UR - 1][li] = ha;
+    }
     FG_K1_MARK(2);
     __syncthreads();
     FG_K1_MARK(3);
-    const double2 U0yb = Ub[0][rm][li], U1yf = Ub[1][rp][li], U2yb = Ub[2][rm][li];
+    const int ub = ANISO ? r : rm, uf = ANISO ? r + 2 : rp;   // ANISO: rows r - 1, r + 1 of the extended image
+    const double2 U0yb = Ub[0][ub][li], U1yf = Ub[1][uf][li], U2yb = Ub[2][ub][li];
     double U0zb = prev_y(uc[0].y), U1zb = prev_y(uc[1].y), U2zf = next_x(uc[2].x);
     if (FULLROW) {   // wave edges: the neighbour pair lives in the adjacent wave of the same row
       if (l == 0) {
-        U0zb = Ub[0][r][zprev * 64 + 63].y;
-        U1zb = Ub[1][r][zprev * 64 + 63].y;
+        U0zb = Ub[0][r + UO][zprev * 64 + 63].y;
+        U1zb = Ub[1][r + UO][zprev * 64 + 63].y;
       }
-      if (l == 63) U2zf = Ub[2][r][znext * 64].x;
+      if (l == 63) U2zf = Ub[2][r + UO][znext * 64].x;
     }
     // ---- strain of the two voxels  (F:18632-18686)
     double2 e0, e1, e2, e3, e4, e5;
@@ -365,11 +416,35 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, dou
     e4.y = E.v[4] + 0.5 * (dx2.y * hx + (uc[0].y - uc[0].x) * hz);
     e5.x = E.v[5] + 0.5 * (dx1.x * hx + (uc[0].x - U0yb.x) * hy);
     e5.y = E.v[5] + 0.5 * (dx1.y * hx + (uc[0].y - U0yb.y) * hy);
+    double2 t0, t1, t2, t3, t4, t5;
+    if constexpr (ANISO) {
+      // ---- polarisation  tau = D0 : eps + phi_1 (D1 : eps), all 36 entries of each (see AnisoLin)
+      const double2 ee[6] = {e0, e1, e2, e3, e4, e5};
+      double2 tt[6];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        double2 n0 = make_double2(0.0, 0.0), n1 = n0, s0 = n0, s1 = n0;   // normal and shear columns of D0, D1
+#pragma unroll
+        for (int jj = 0; jj < 3; ++jj) {
+          const double a = lin.d0[aniso_idx(i, jj)], b = lin.d1[aniso_idx(i, jj)];
+          n0.x += a * ee[jj].x; n0.y += a * ee[jj].y;
+          n1.x += b * ee[jj].x; n1.y += b * ee[jj].y;
+        }
+#pragma unroll
+        for (int jj = 3; jj < 6; ++jj) {
+          const double a = lin.d0[aniso_idx(i, jj)], b = lin.d1[aniso_idx(i, jj)];
+          s0.x += a * ee[jj].x; s0.y += a * ee[jj].y;
+          s1.x += b * ee[jj].x; s1.y += b * ee[jj].y;
+        }
+        tt[i].x = (n0.x + 2.0 * s0.x) + Ac.x * (n1.x + 2.0 * s1.x);
+        tt[i].y = (n0.y + 2.0 * s0.y) + Ac.y * (n1.y + 2.0 * s1.y);
+      }
+      t0 = tt[0]; t1 = tt[1]; t2 = tt[2]; t3 = tt[3]; t4 = tt[4]; t5 = tt[5];
+    } else {
     // ---- polarisation  tau = (A - 2 mu0) eps + (B - lambda0) tr(eps) I
     const double ax = PHI2 ? lin.a0 + Ac.x * lin.da : Ac.x + beta, ay = PHI2 ? lin.a0 + Ac.y * lin.da : Ac.y + beta;
     const double bx = PHI2 ? lin.b0 + Bc.x * lin.db : Bc.x + gamma, by = PHI2 ? lin.b0 + Bc.y * lin.db : Bc.y + gamma;
     const double trx = e0.x + e1.x + e2.x, try_ = e0.y + e1.y + e2.y;
-    double2 t0, t1, t2, t3, t4, t5;
     t0.x = e0.x * ax + bx * trx; t0.y = e0.y * ay + by * try_;
     t1.x = e1.x * ax + bx * trx; t1.y = e1.y * ay + by * try_;
     t2.x = e2.x * ax + bx * trx; t2.y = e2.y * ay + by * try_;
@@ -381,6 +456,7 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, dou
       t3.x = e3.x * ax; t3.y = e3.y * ay;
       t4.x = e4.x * ax; t4.y = e4.y * ay;
       t5.x = e5.x * ax; t5.y = e5.y * ay;
+    }
     }
     const bool inside = st >= 0 && st < nsteps;
     if (own && inside) {
@@ -984,10 +1060,11 @@ inline int march_length(int nx, long tiles, int cus) {
   return best;
 }
 
-template <int TYR, int ZS, bool SUMT, bool PHI2 = false, bool CGP = false, int NMOD = 2>
+template <int TYR, int ZS, bool SUMT, bool PHI2 = false, bool CGP = false, int NMOD = 2, bool ANISO = false>
 void launch_u_tile_t(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& u, const FieldPtrs<NMOD>& mod,
                      const FieldPtrs<3>& f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s,
-                     const PhaseLin& lin = PhaseLin{0, 0, 0, 0}, const CgDirection& cg = CgDirection{}) {
+                     const std::conditional_t<ANISO, AnisoLin, PhaseLin>& lin = std::conditional_t<ANISO, AnisoLin, PhaseLin>{},
+                     const CgDirection& cg = CgDirection{}) {
   constexpr int NZS = ZS ? ZS : 1;
   constexpr int TYU = TYR - 2, TZU = ZS ? 64 * ZS : 62;
   const int nzh = g.nz / 2;
@@ -998,14 +1075,14 @@ void launch_u_tile_t(const Grid& g, double mu_0, double lambda_0, const FieldPtr
   const int ntx = (g.nx + LX - 1) / LX;
   int nb = nty * ntz * ntx;
   if (nb >= 8) nb = ((nb + 7) / 8) * 8;
-  const size_t lds = 6 * TYR * NZS * 64 * sizeof(double2);
+  const size_t lds = (6 * TYR + (ANISO ? 6 : 0)) * NZS * 64 * sizeof(double2);   // ANISO: two more rows of u per component
   static PerDeviceOnce configured;
   if (auto once = configured.first_use()) {
-    FG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_u_tile<TYR, ZS, SUMT, PHI2, CGP, NMOD>),
+    FG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_u_tile<TYR, ZS, SUMT, PHI2, CGP, NMOD, ANISO>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
   const int nt = 3.0 * (double)g.n * sizeof(double) > 256.0 * 1024 * 1024 ? 1 : 0;
-  hipLaunchKernelGGL((k_u_tile<TYR, ZS, SUMT, PHI2, CGP, NMOD>), dim3(nb), dim3(TYR * NZS * 64), lds, s, g, -2 * mu_0, -lambda_0, u, mod, f,
+  hipLaunchKernelGGL((k_u_tile<TYR, ZS, SUMT, PHI2, CGP, NMOD, ANISO>), dim3(nb), dim3(TYR * NZS * 64), lds, s, g, -2 * mu_0, -lambda_0, u, mod, f,
                      E, partial, nty, ntz, LX, nt, lin, cg);
   FG_HIP_CHECK(hipGetLastError());
   fold_sum(partial, nb, SUMT ? 12 : 6, sumsq6, s);
@@ -1074,6 +1151,77 @@ void launch_u_tile_cg(const Grid& g, double mu_0, double lambda_0, const FieldPt
   else if (nzh == 128) FG_CGK(6, 2);
   else FG_CGK(8, 0);
 #undef FG_CGK
+}
+
+// D0 = C_0 - C0 and D1 = C_1 - C_0 of two phases, an isotropic one expanded to its 6 x 6 (Voigt shear entries: C44 = mu), as
+// packed upper triangles (fg_set_phase_stiffness admits |C_ij - C_ji| <= 1e-12 max|C|: the mean of the two)
+static AnisoLin make_aniso_lin(const PhaseTable& pt, double mu_0, double lambda_0) {
+  double C[2][36], C0[36];
+  auto iso = [](double mu, double lambda, double* out) {
+    for (int i = 0; i < 36; ++i) out[i] = 0.0;
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) out[6 * i + j] = lambda;
+      out[6 * i + i] = 2 * mu + lambda;
+      out[6 * (3 + i) + 3 + i] = mu;
+    }
+  };
+  iso(mu_0, lambda_0, C0);
+  for (int p = 0; p < 2; ++p) {
+    if (pt.law[p] != kLawIso)
+      for (int i = 0; i < 36; ++i) C[p][i] = pt.C[p][i];
+    else
+      iso(pt.mu[p], pt.lambda[p], C[p]);
+  }
+  AnisoLin lin;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) {
+      const double c0 = 0.5 * (C[0][6 * i + j] + C[0][6 * j + i]), c1 = 0.5 * (C[1][6 * i + j] + C[1][6 * j + i]);
+      lin.d0[aniso_idx(i, j)] = c0 - C0[6 * i + j];
+      lin.d1[aniso_idx(i, j)] = c1 - c0;
+    }
+  return lin;
+}
+
+// the tiled sweep of two complementary phases with a general phase (k_u_tile ANISO): phi1 = phi_1, the default tile shapes
+void launch_u_tile_aniso(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& u, const double* phi1,
+                         const FieldPtrs<3>& f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s, bool sum_tau,
+                         const PhaseTable& two_phase) {
+  const int nzh = g.nz / 2;
+  const AnisoLin lin = make_aniso_lin(two_phase, mu_0, lambda_0);
+  FieldPtrs<2> mod;
+  mod.p[0] = const_cast<double*>(phi1);
+  mod.p[1] = nullptr;
+#define FG_ANI(R, Z)                                                                                                              \
+  do {                                                                                                                            \
+    if (sum_tau) launch_u_tile_t<R, Z, true, true, false, 2, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s, lin);    \
+    else launch_u_tile_t<R, Z, false, true, false, 2, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s, lin);           \
+  } while (0)
+  // (no <6, 2> form: a workgroup of 768 threads may use 168 VGPRs and every variant tried spills past them into scratch, which
+  // this kernel must not use -- figures in DESIGN.md 4a; rows of 128 pairs take the general tiles of 62 pairs)
+  if (nzh == 64) FG_ANI(8, 1);
+  else FG_ANI(8, 0);
+#undef FG_ANI
+}
+
+// ... with the search direction of the conjugate gradients formed on the fly (see launch_u_tile_cg)
+void launch_u_tile_aniso_cg(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& p_old, const FieldPtrs<3>& r,
+                            const FieldPtrs<3>& p_new, const double* phi1, const FieldPtrs<3>& f, const Vec6& E, const double* sc,
+                            int i_num, int i_den, double nvox, double small, double* partial, double* sumsq6, hipStream_t s,
+                            const PhaseTable& two_phase) {
+  CgDirection cg;
+  for (int c = 0; c < 3; ++c) cg.r[c] = r.p[c], cg.po[c] = p_new.p[c];
+  cg.sc = sc;
+  cg.i_num = i_num;
+  cg.i_den = i_den;
+  cg.nvox = nvox;
+  cg.small = small;
+  const int nzh = g.nz / 2;
+  const AnisoLin lin = make_aniso_lin(two_phase, mu_0, lambda_0);
+  FieldPtrs<2> mod;
+  mod.p[0] = const_cast<double*>(phi1);
+  mod.p[1] = nullptr;
+  if (nzh == 64) launch_u_tile_t<8, 1, false, true, true, 2, true>(g, mu_0, lambda_0, p_old, mod, f, E, partial, sumsq6, s, lin, cg);
+  else launch_u_tile_t<8, 0, false, true, true, 2, true>(g, mu_0, lambda_0, p_old, mod, f, E, partial, sumsq6, s, lin, cg);
 }
 
 // gamma_scheme full_staggered: the same sweeps on the five moduli of the doubly fine grid (default tile shapes)

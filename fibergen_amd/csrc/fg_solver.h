@@ -86,6 +86,8 @@ struct SolverOptions {
   int u_tile = 1;               // fast displacement sweep (u_loop = 2) as the LDS-tiled marching kernel where the grid allows
                                 // (0 = the untiled sweep everywhere).  512^3: 2.8 -> 1.95 ms per sweep
   int phi_sweep = 1;            // two complementary phases: the tiled sweep reads phi_1 instead of the two moduli arrays
+  int aniso_tile = 1;           // general (6 x 6 stiffness) phases, two complementary phases: the displacement loop on the tiled sweep's
+                                // anisotropic form (1) or the strain-state pass everywhere (0; also what every other case runs)
   int laminate_overlap = 1;     // displacement loop with laminate mixing: interface kernels on a second stream beside the sweep
   int slab_loopback = 0;        // test mode: a lone slab sends to itself through its transport (see Solver::slab_loopback)
   int slab_split = -1;          // slab driver: all-to-all per component, overlapping the next component's transforms (1), one
@@ -149,6 +151,11 @@ class Solver {
   void set_num_phases(int n);
   int num_phases() const { return pt_.n; }
   void set_phase_material(int p, double mu, double lambda);
+  // LinearGeneralMaterialLaw  F:11233: phase p gets the constant stiffness C (36, row-major; Voigt shear entries, the factor 2
+  // of the tensor shear strains sits in the product -- general6, fg_stage_math.h) and becomes a general phase until
+  // set_phase_material makes it isotropic again.  Throws unless |C_ij - C_ji| <= 1e-12 max|C|.
+  void set_phase_stiffness(int p, const double* C36);
+  bool general_phase() const { return any_general_phase(pt_); }
   void set_phase_field(int p, const double* phi_host);  // [nx][ny][nz], copied
   // gamma_scheme 2: phase p's image on the doubly fine grid [2nx][2ny][2nz] (initPhi under select_dfg F:17152-17230), reduced on
   // the device to its coarse field and its three shear-group fractions; the image is not kept
@@ -216,7 +223,8 @@ class Solver {
   void reset_stage_times();
   double event_bias_ms() const { return event_bias_ms_; }
   // fg_get_counter: "interface_voxels" / "affected_voxels" = lengths of the laminate correction's lists (0 before they are
-  // built); "phase_uploads" = host arrays received by set_phase_field / set_phase_field_fine / set_normals; -1 = unknown name
+  // built); "phase_uploads" = host arrays received by set_phase_field / set_phase_field_fine / set_normals; "u_tile_aniso" =
+  // launches of the tiled sweep's anisotropic form; -1 = unknown name
   long counter(const std::string& name) const;
 
  private:
@@ -238,8 +246,10 @@ class Solver {
   bool run_cg(const double* E0, const double* S0, double prev0);
   bool run_cg_scalar(const double* E0, double prev0);  // heat / porous: CG in potential space
   bool run_cg_u(const double* E0, double prev0);      // the same CG carried in displacement space (Voigt, prescribed mean strains)
-  bool u_loop_eligible(bool allow_mixed_bc = false) const;
+  bool u_loop_eligible(bool allow_mixed_bc = false);   // (may run the complement check on the device)
   bool two_phase_complementary();       // phi_0 == 1 - phi_1 everywhere (checked once per geometry)
+  void general_check() const;           // throws for the combinations general phases do not cover
+  bool aniso_tile_ok();                 // general phases: the displacement loop has a sweep for this problem (k_u_tile ANISO)
   FieldPtrs<2> effective_moduli();      // per-voxel sums of the phase moduli for the fast kernels (allocated on first use)
   bool dfg() const { return opt_.gamma_scheme == 2; }
   void dfg_check() const;               // throws for the combinations full_staggered does not cover
@@ -381,6 +391,7 @@ class Solver {
   double* mod5_ = nullptr;     // gamma_scheme 2: the five moduli
   bool mod5_dirty_ = true;
   bool complement_dirty_ = true, complementary_ = false;
+  long u_tile_aniso_ = 0;   // launches of the tiled sweep's anisotropic form (fg_get_counter "u_tile_aniso")
   double* fu_alt_ = nullptr;   // 3: second f/u buffer of the displacement-based loop (swapped with fu_)
   double* phi_ = nullptr;      // nphase
   double* normals_ = nullptr;  // 3 (allocated on demand)

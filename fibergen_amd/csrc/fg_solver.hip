@@ -90,7 +90,11 @@ Solver::Solver(int nx, int ny, int nz, double dx, double dy, double dz, int devi
   FG_HIP_CHECK(hipEventCreate(&ev_[1]));
   FG_HIP_CHECK(hipEventCreateWithFlags(&ev_copy_, hipEventDisableTiming));
   pt_.n = 0;
-  for (int i = 0; i < kMaxPhases; ++i) pt_.mu[i] = pt_.lambda[i] = 0.0;
+  for (int i = 0; i < kMaxPhases; ++i) {
+    pt_.mu[i] = pt_.lambda[i] = 0.0;
+    pt_.law[i] = kLawIso;
+    for (int k = 0; k < 36; ++k) pt_.C[i][k] = 0.0;
+  }
   opt_.mu_0 = std::numeric_limits<double>::quiet_NaN();  // F:15340
   opt_.eps_a = std::pow(kEps, 2.0 / 3.0);
 
@@ -252,6 +256,27 @@ void Solver::set_phase_material(int p, double mu, double lambda) {
   mixed_dirty_ = true;
   pt_.mu[p] = mu;
   pt_.lambda[p] = lambda;
+  pt_.law[p] = kLawIso;
+}
+
+void Solver::set_phase_stiffness(int p, const double* C36) {
+  if (p < 0 || p >= pt_.n) throw std::runtime_error("phase index out of range");
+  if (!C36) throw std::runtime_error("stiffness pointer is NULL");
+  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("general (anisotropic) phases are not available on slab-decomposed solvers");
+  double cmax = 0.0;
+  for (int i = 0; i < 36; ++i) {
+    if (!std::isfinite(C36[i])) throw std::runtime_error("phase stiffness is not finite");
+    cmax = std::max(cmax, std::fabs(C36[i]));
+  }
+  for (int i = 0; i < 6; ++i)
+    for (int j = i + 1; j < 6; ++j)
+      if (std::fabs(C36[6 * i + j] - C36[6 * j + i]) > 1e-12 * cmax) throw std::runtime_error("phase stiffness is not symmetric");
+  invalidate_moduli();
+  mixed_dirty_ = true;
+  for (int i = 0; i < 36; ++i) pt_.C[p][i] = C36[i];
+  pt_.law[p] = kLawGeneral;
+  // the safety net: whatever still reads (mu, lambda) of a general phase computes NaN, not an isotropic answer
+  pt_.mu[p] = pt_.lambda[p] = std::numeric_limits<double>::quiet_NaN();
 }
 
 void Solver::set_phase_field(int p, const double* phi_host) {
@@ -612,6 +637,7 @@ long Solver::counter(const std::string& name) const {
   if (name == "interface_voxels") return (long)mixed_n_;
   if (name == "affected_voxels") return (long)aff_n_;
   if (name == "phase_uploads") return phase_uploads_;
+  if (name == "u_tile_aniso") return u_tile_aniso_;
   if (name == "pair_chunk_planes") return (long)pair_chunk_planes(opt_.mode == 1 ? 1 : 3);
   return -1;
 }
@@ -644,6 +670,7 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
   if (opt_.mixing == kMixLaminate && !normals_) throw std::runtime_error("laminate mixing needs interface normals");
   if (dfg()) dfg_check();
   if (willot()) willot_check();
+  general_check();
   FieldPtrs<kMaxPhases> phi;
   for (int q = 0; q < kMaxPhases; ++q) phi.p[q] = q < pt_.n ? phi_ + (long)q * g_.n : nullptr;
   FieldPtrs<3> nrm;
@@ -787,10 +814,11 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
   const bool mq_zero = frobenius(BC_MQ_) < kEps;
   // Voigt mixing: polarisation and divergence in one sweep (tau never stored); the laminate rule keeps the
   // two-kernel form (its per-voxel Newton solve is too costly to repeat at the six neighbours)
-  const bool fuse_sd = opt_.fuse_stress_div && opt_.mixing == kMixVoigt && mq_zero && !dfg();
+  // (general phases: both fused forms evaluate the polarisation from (mu, lambda) -- the stored-polarisation form serves them)
+  const bool fuse_sd = opt_.fuse_stress_div && opt_.mixing == kMixVoigt && mq_zero && !dfg() && !general_phase();
   // with the fast kernels allowed (u_loop = 2) the LDS-tiled form takes over where the grid fits; it also delivers
   // the sums of tau, so mixed boundary conditions keep the fused sweep
-  const bool tile_sd = opt_.fuse_stress_div && opt_.mixing == kMixVoigt && opt_.u_loop >= 2 && u_tile_supported(g_);
+  const bool tile_sd = opt_.fuse_stress_div && opt_.mixing == kMixVoigt && opt_.u_loop >= 2 && u_tile_supported(g_) && !general_phase();
   if (tile_sd) {
     time_begin(0);
     if (dfg())
@@ -1182,7 +1210,7 @@ FieldPtrs<kMaxPhases> Solver::phase_ptrs() const {
   return phi;
 }
 
-bool Solver::u_loop_eligible(bool allow_mixed_bc) const {
+bool Solver::u_loop_eligible(bool allow_mixed_bc) {
   if (opt_.mode == 1) {
     // the scalar modes only have the potential-based loop
     if (nranks_ != 1) throw std::runtime_error("heat / porous mode is not available on slab-decomposed solvers");
@@ -1192,6 +1220,9 @@ bool Solver::u_loop_eligible(bool allow_mixed_bc) const {
       throw std::runtime_error("heat / porous mode: mixed boundary conditions run with method=basic (fg_run_load_case) only");
     return pt_.n >= 1;
   }
+  // general phases: the displacement loop exists as the tiled sweep's anisotropic form only; everything else takes the
+  // strain-state pass
+  if (general_phase() && !aniso_tile_ok()) return false;
   // full_staggered: the displacement loop runs the tiled Voigt sweep only (the untiled sweep has no five-moduli form)
   const bool scheme_ok = opt_.gamma_scheme == 0 ||
                          (dfg() && opt_.mixing == kMixVoigt && opt_.u_loop >= 2 && opt_.u_tile && u_tile_supported(g_));
@@ -1223,6 +1254,7 @@ bool Solver::two_phase_complementary() {
 
 // A = sum_p phi_p 2 mu_p, B = sum_p phi_p lambda_p per voxel (k_effective_moduli), computed once per geometry
 FieldPtrs<2> Solver::effective_moduli() {
+  if (general_phase()) throw std::logic_error("effective moduli (sum phi 2 mu, sum phi lambda) do not exist with a general phase");
   if (!mod_) {
     FG_HIP_CHECK(hipMalloc(&mod_, 2 * (size_t)g_.n * sizeof(double)));
     mod_dirty_ = mod5_dirty_ = true;
@@ -1238,6 +1270,21 @@ FieldPtrs<2> Solver::effective_moduli() {
     mod_dirty_ = false;
   }
   return mod;
+}
+
+// law "general" (constant 6 x 6 stiffness per phase): elasticity, Voigt mixing, staggered / collocated / willot, one GPU
+void Solver::general_check() const {
+  if (!general_phase()) return;
+  if (opt_.mode != 0) throw std::runtime_error("general (anisotropic) phases are available in elasticity mode only");
+  if (opt_.mixing != kMixVoigt)
+    throw std::runtime_error("general (anisotropic) phases support Voigt mixing only (the laminate split is written for isotropic phases)");
+  if (dfg()) throw std::runtime_error("general (anisotropic) phases are not available with gamma_scheme full_staggered / half_staggered");
+  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("general (anisotropic) phases are not available on slab-decomposed solvers");
+}
+
+bool Solver::aniso_tile_ok() {
+  return opt_.aniso_tile && opt_.mode == 0 && opt_.gamma_scheme == 0 && opt_.mixing == kMixVoigt && opt_.u_loop >= 2 && opt_.u_tile &&
+         nranks_ == 1 && !slab_layout_ && u_tile_supported(g_) && two_phase_complementary();
 }
 
 void Solver::willot_check() const {
@@ -1371,6 +1418,10 @@ void Solver::u_pass_front(const double* E6) {
       if (dfg()) {   // full_staggered: the five moduli, also for two complementary phases
         launch_u_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), dfg_moduli(), ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq,
                       stream_, sum_tau);
+      } else if (general_phase()) {   // u_loop_eligible: two complementary phases
+        launch_u_tile_aniso(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), phi_ + g_.n, ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq,
+                            stream_, sum_tau, phase_table());
+        ++u_tile_aniso_;
       } else if (two_phase_complementary()) {
         // two phases with phi_0 = 1 - phi_1: the sweep reads phi_1 and forms the moduli itself (8 B per voxel less)
         FieldPtrs<2> ph;
@@ -1442,6 +1493,7 @@ void Solver::iterate(const double* E6, int n) {
   FG_HIP_CHECK(hipSetDevice(device_));
   if (dfg()) dfg_check();
   if (willot()) willot_check();
+  general_check();
   int i = 0;
   if (u_loop_eligible()) {
     if (!u_valid_ && n > 0 && opt_.mode == 1) {
@@ -1558,6 +1610,7 @@ double Solver::volume_fraction(int p) {
 void Solver::calc_ref_material() {
   FG_HIP_CHECK(hipSetDevice(device_));
   if (pt_.n < 1) throw std::runtime_error("No materials specified");
+  general_check();
   FieldPtrs<kMaxPhases> phi;
   for (int q = 0; q < kMaxPhases; ++q) phi.p[q] = q < pt_.n ? phi_ + (long)q * g_.n : nullptr;
   if (opt_.mode == 1)
@@ -1733,6 +1786,7 @@ bool Solver::run_load_steps(const double* E6, const double* S6, const double* pa
 bool Solver::run_one_step(const double* E0, const double* S0) {
   if (dfg()) dfg_check();
   if (willot()) willot_check();
+  general_check();
   // EpsilonErrorEstimator  F:14591-14637: constructed on the field the step starts from (zero for the first step)
   const double prev0 = fresh_step_ ? 0.0 : current_norm9();
   if (opt_.error_estimator >= 2) {
@@ -1906,6 +1960,17 @@ bool Solver::run_cg_u(const double* E0, double prev0) {
     }
     FieldPtrs<2> m;
     const PhaseTable t = phase_table();
+    if (general_phase()) {
+      time_begin(0);
+      launch_u_tile_aniso_cg(g_, opt_.mu_0, opt_.lambda_0, ptrs3(u_p), ptrs3(u_r), ptrs3(p_alt), phi_ + g_.n, ptrs3(fu_alt_), Z, dscal_,
+                             i_num, i_den, (double)nglobal_, std::numeric_limits<double>::min(), partial_, dscal_ + kSlotSumSq,
+                             stream_, t);
+      ++u_tile_aniso_;
+      time_end(0);
+      fft_g0_chain(fu_alt_, -1.0, nullptr, tau_);
+      std::swap(u_p, p_alt);
+      return;
+    }
     const bool two = two_phase_complementary();
     if (two) {
       m.p[0] = phi_ + g_.n;

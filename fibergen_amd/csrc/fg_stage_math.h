@@ -14,11 +14,25 @@ namespace fg {
 
 constexpr int kMaxPhases = 8;
 
+// law[p] = kLawIso: (mu, lambda).  law[p] = kLawGeneral: the constant stiffness C[p] (LinearGeneralMaterialLaw  F:11233-11349),
+// 6 x 6 row-major; its shear entries are Voigt (C44 = mu for an isotropic body) while strain components 3..5 are tensor
+// components, so the factor 2 sits in the product (general6).  A general phase carries mu = lambda = NaN: a path that still
+// reads them poisons its result instead of computing an isotropic answer.
+enum PhaseLaw { kLawIso = 0, kLawGeneral = 1 };
+
 struct PhaseTable {
   int n;
   double mu[kMaxPhases];
   double lambda[kMaxPhases];
+  int law[kMaxPhases];
+  double C[kMaxPhases][36];
 };
+
+FG_HD bool any_general_phase(const PhaseTable& pt) {
+  bool g = false;
+  for (int p = 0; p < kMaxPhases; ++p) g = g || (p < pt.n && pt.law[p] != kLawIso);
+  return g;
+}
 
 enum MixingRule { kMixVoigt = 0, kMixLaminate = 1 };
 
@@ -43,6 +57,17 @@ FG_HD void hooke6(const double* E, double mu, double lambda, double alpha, bool 
   }
 }
 
+// LinearGeneralMaterialLaw::PK1  F:11254-11272  (gamma = accumulate), C row-major 6 x 6
+FG_HD void general6(const double* E, const double* C, double alpha, bool accumulate, double* S) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    const double* Ci = C + 6 * i;
+    const double v = alpha * (E[0] * Ci[0] + E[1] * Ci[1] + E[2] * Ci[2] + 2.0 * (E[3] * Ci[3] + E[4] * Ci[4] + E[5] * Ci[5]));
+    if (accumulate) S[i] += v;
+    else S[i] = v;
+  }
+}
+
 // VoigtMixedMaterialLaw::PK1  F:12752-12761 ; threshold 10*eps  F:12736
 template <int NPH>
 FG_HD void pk1_voigt(const double* F, const double* phi, const PhaseTable& pt, double alpha, bool gamma, double* P) {
@@ -52,7 +77,8 @@ FG_HD void pk1_voigt(const double* F, const double* phi, const PhaseTable& pt, d
   for (int p = 0; p < NPH; ++p) {
     if (p >= pt.n) break;
     if (phi[p] <= threshold) continue;
-    hooke6(F, pt.mu[p], pt.lambda[p], phi[p] * alpha, any, P);
+    if (pt.law[p] != kLawIso) general6(F, pt.C[p], phi[p] * alpha, any, P);
+    else hooke6(F, pt.mu[p], pt.lambda[p], phi[p] * alpha, any, P);
     any = true;
   }
   if (!any) {
@@ -284,7 +310,14 @@ FG_HD double voigt_tau_shear(double Ec, const double* phi, const StressParams& s
 // Voigt tangent (F:12763-12771) and the laminate tangent="approx" (F:13611-13624)
 // are isotropic: diag block 2mu I + lam 11^T, shear block 2mu I, eigenvalues
 // {2mu (x5), 2mu + 3 lam}.  (The reference obtains them with LAPACK dsyev.)
-template <int NPH>
+//
+// GENERAL (a phase with a constant stiffness is present, Voigt mixing): the tangent sum_p phi_p C_p is no longer isotropic.
+// The reference hands dsyev the 6 x 6 matrix dPK1 fills from the identity rows (F:12518-12522, F:9068-9075, F:11274-11298):
+// row m holds C(:, m) f_m with f = (1, 1, 1, 2, 2, 2), read through its upper triangle [[C_nn, C_ns], [C_ns^T, 2 C_ss]];
+// built here phase by phase like VoigtMixedMaterialLaw::dPK1 and diagonalised by jacobi_minmax6.
+FG_HD void jacobi_minmax6(double (&A)[6][6], double* emin, double* emax);
+
+template <int NPH, bool GENERAL = false>
 FG_HD int tangent_eigs(const double* phi, const PhaseTable& pt, int mixing, double* emin, double* emax) {
   double two_mu = 0.0, lam = 0.0;
   if (mixing == kMixLaminate) {
@@ -296,6 +329,38 @@ FG_HD int tangent_eigs(const double* phi, const PhaseTable& pt, int mixing, doub
       two_mu += 2 * m.c2 * pt.mu[m.p2];
       lam += m.c2 * pt.lambda[m.p2];
     }
+  } else if (GENERAL) {
+    const double threshold = 10 * 2.220446049250313e-16;
+    double A[6][6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) A[i][j] = 0.0;
+#pragma unroll
+    for (int p = 0; p < NPH; ++p) {
+      if (p >= pt.n) break;
+      if (phi[p] <= threshold) continue;
+      if (pt.law[p] != kLawIso) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+          for (int j = i; j < 6; ++j) A[i][j] += phi[p] * ((i >= 3 ? 2.0 : 1.0) * pt.C[p][6 * j + i]);
+      } else {
+        const double tm = 2 * phi[p] * pt.mu[p], l = phi[p] * pt.lambda[p];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) A[i][i] += tm;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = i; j < 3; ++j) A[i][j] += l;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j < i; ++j) A[i][j] = A[j][i];
+    jacobi_minmax6(A, emin, emax);
+    return 0;
   } else {
     const double threshold = 10 * 2.220446049250313e-16;
 #pragma unroll
@@ -310,6 +375,53 @@ FG_HD int tangent_eigs(const double* phi, const PhaseTable& pt, int mixing, doub
   *emin = e1 < e2 ? e1 : e2;
   *emax = e1 < e2 ? e2 : e1;
   return 0;
+}
+
+// Smallest and largest eigenvalue of a symmetric 6 x 6 matrix (destroyed) by cyclic Jacobi rotations -- the eigenvalue half
+// of hostmath::jacobi_eig, with every index a compile-time constant so that the matrix stays in registers on the device.
+// Converged when the off-diagonal mass is below rounding of the diagonal (at most 30 sweeps; 6 x 6 takes 6 to 8).
+FG_HD void jacobi_minmax6(double (&A)[6][6], double* emin, double* emax) {
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    double off = 0.0, diag = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      diag += A[i][i] * A[i][i];
+#pragma unroll
+      for (int j = i + 1; j < 6; ++j) off += A[i][j] * A[i][j];
+    }
+    if (off <= 1e-34 * diag) break;
+#pragma unroll
+    for (int p = 0; p < 6; ++p) {
+#pragma unroll
+      for (int q = p + 1; q < 6; ++q) {
+        const double apq = A[p][q];
+        if (apq == 0.0) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          const double akp = A[k][p], akq = A[k][q];
+          A[k][p] = c * akp - s * akq;
+          A[k][q] = s * akp + c * akq;
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          const double apk = A[p][k], aqk = A[q][k];
+          A[p][k] = c * apk - s * aqk;
+          A[q][k] = s * apk + c * aqk;
+        }
+      }
+    }
+  }
+  double lo = A[0][0], hi = A[0][0];
+#pragma unroll
+  for (int i = 1; i < 6; ++i) {
+    lo = A[i][i] < lo ? A[i][i] : lo;
+    hi = A[i][i] > hi ? A[i][i] : hi;
+  }
+  *emin = lo;
+  *emax = hi;
 }
 
 // G0OperatorFourierStaggeredGeneral frequency body  F:19873-19913

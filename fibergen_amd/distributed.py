@@ -283,6 +283,10 @@ class SlabGroup:
         for m in self.members:
             m.set_phase(p, mu, lam, None if phi is None else m.slab(phi))
 
+    def set_phase_stiffness(self, p, C):
+        from .materials import GENERAL_SLAB_ERROR
+        raise RuntimeError(GENERAL_SLAB_ERROR)
+
     def set_normals(self, normals):
         for m in self.members:
             m.set_normals(m.slab(normals))

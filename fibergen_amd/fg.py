@@ -304,6 +304,20 @@ class FG:
             raise RuntimeError("gamma scheme '%s' is not available with mixing rule '%s' on the MI355X path (voigt only: the "
                                "laminate split is not linear in phi)" % (scheme, mixing))
 
+        # law="general" (a constant 6x6 stiffness): what it does not cover is refused before a solver exists, in the wording of
+        # the solver library (Solver::general_check)
+        mats_el = solver.find("materials") if solver is not None else None
+        if mats_el is not None and any(isinstance(m.tag, str) and m.tag != "ref" and m.attrib.get("law", "iso") == "general"
+                                       for m in mats_el):
+            if scalar:
+                raise RuntimeError(_materials.GENERAL_MODE_ERROR)
+            if mixing != "voigt":
+                raise RuntimeError(_materials.GENERAL_MIXING_ERROR)
+            if dfg:
+                raise RuntimeError(_materials.GENERAL_DFG_ERROR)
+            if getattr(self, "_slabs", False):
+                raise RuntimeError(_materials.GENERAL_SLAB_ERROR)
+
         if getattr(self, "_slabs", False):
             from .distributed import GlobalViewSolver
             if scheme != "staggered":
@@ -368,10 +382,13 @@ class FG:
                     matrix_set = True
                     matrix_mat = len(names)
                 law = attrs.get("law", "iso")
-                if law != "iso":
+                if law not in ("iso", "general"):
                     raise RuntimeError("Unknown material law '%s'" % law)
                 names.append(m.tag)
-                if scalar:
+                if law == "general":
+                    # LinearGeneralMaterialLaw  F:11233-11349, read at F:15215-15218: a constant 6x6 stiffness
+                    consts.append({"C": _materials.general_stiffness(attrs, self._eval)})
+                elif scalar:
                     # ScalarLinearIsotropicMaterialLaw::readSettings  F:11170-11173: one constant, mu (default 1)
                     consts.append({"mu": self._eval(attrs.get("mu", "1")), "lambda": 0.0})
                 else:
@@ -379,8 +396,9 @@ class FG:
         if not names:
             raise RuntimeError("No materials specified")
         lss.set_num_phases(len(names))
-        for p, c in enumerate(consts):
-            lss.set_phase(p, c["mu"], c["lambda"])
+        self._phase_materials = consts
+        for p in range(len(consts)):
+            self._set_phase(lss, p)
         lss.set_options(**opts)
         lss.set_convergence_callback(self._on_iteration)
         self._lss = lss
@@ -389,6 +407,15 @@ class FG:
         self._matrix_mat = matrix_mat
         self._mixing = mixing
         self._solver_valid = True
+
+    def _set_phase(self, lss, p, phi=None):
+        """phase p's constants (and field) into the solver: (mu, lambda), or the stiffness of a law="general" material"""
+        c = self._phase_materials[p]
+        if "C" in c:
+            lss.set_phase(p, 0.0, 0.0, phi)
+            lss.set_phase_stiffness(p, c["C"])
+        else:
+            lss.set_phase(p, c["mu"], c["lambda"], phi)
 
     def init_fibers(self):
         """Random fibre generation is out of scope; placed fibres need no generation."""
@@ -461,7 +488,7 @@ class FG:
                                                     want_normals=True, device=self._device)
                 self._normals = normals
             for p in range(nph):
-                lss.set_phase(p, self._phase_materials[p]["mu"], self._phase_materials[p]["lambda"])
+                self._set_phase(lss, p)
                 lss.set_phase_fine(p, phif[p])
             self._phi = lss.get_field("phi")   # the coarse field F:17180-17228
         elif self._raw_phase:
@@ -478,7 +505,7 @@ class FG:
             phi = _normalize_phi(phi)  # normalizePhi  F:17588-17646 (last material wins)
             self._phi = phi
             for p in range(nph):
-                lss.set_phase(p, self._phase_materials[p]["mu"], self._phase_materials[p]["lambda"], phi[p])
+                self._set_phase(lss, p, phi[p])
         if self._normals is not None:
             lss.set_normals(self._normals)
         elif self._mixing == "laminate":

@@ -78,3 +78,27 @@ def material_constants(attrs, evaluate=float):
         raise RuntimeError("Ambiguous material definition")
     r = _CALC[icalc](evaluate(attrs[icalc[0]]), evaluate(attrs[icalc[1]]))
     return {"K": r["K"], "E": r["E"], "lambda": r["lam"], "mu": r["mu"], "nu": r["nu"], "M": r["M"]}
+
+
+# law="general": the combinations it does not cover, in the wording of the solver library (Solver::general_check)
+GENERAL_MODE_ERROR = "general (anisotropic) phases are available in elasticity mode only"
+GENERAL_MIXING_ERROR = ("general (anisotropic) phases support Voigt mixing only (the laminate split is written for isotropic "
+                        "phases)")
+GENERAL_DFG_ERROR = "general (anisotropic) phases are not available with gamma_scheme full_staggered / half_staggered"
+GENERAL_SLAB_ERROR = "general (anisotropic) phases are not available on slab-decomposed solvers"
+
+
+def general_stiffness(attrs, evaluate=float):
+    """LinearGeneralMaterialLaw::readSettings  F:11240-11245 = read_matrix(attr, C, "c", true)  F:1101-1119 on Voigt::Id4(6)
+    F:501-512 (diag 1, 1, 1, 0.5, 0.5, 0.5 -- not the plain identity): i, j row-major, every attribute c<i><j> found sets (i, j)
+    and (j, i), so of c12 and c21 the one later in the loop (c21) wins.  Returns the 6x6 list of rows."""
+    C = [[0.0] * 6 for _ in range(6)]
+    for i in range(6):
+        C[i][i] = 1.0 if i < 3 else 0.5
+    for i in range(6):
+        for j in range(6):
+            name = "c%d%d" % (i + 1, j + 1)
+            if name in attrs:
+                C[i][j] = evaluate(attrs[name])
+                C[j][i] = C[i][j]
+    return C

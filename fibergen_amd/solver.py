@@ -79,6 +79,15 @@ class LSSolver:
             ptr = _dp(phi)
         self._check(self._lib.fg_set_phase(self._h, int(p), float(mu), float(lam), ptr))
 
+    def set_phase_stiffness(self, p, C):
+        """fg_set_phase_stiffness (LinearGeneralMaterialLaw F:11233): phase p becomes a general phase with the symmetric 6x6
+        stiffness C -- Voigt shear entries (C44 = mu for an isotropic body), tensor shear strains, the factor 2 in the product.
+        A later set_phase(p, mu, lam) makes it isotropic again."""
+        C = np.ascontiguousarray(C, dtype=np.float64)
+        if C.shape != (6, 6):
+            raise ValueError("the stiffness must be 6x6")
+        self._check(self._lib.fg_set_phase_stiffness(self._h, int(p), _dp(C)))
+
     def set_phase_fine(self, p, phi):
         """gamma_scheme full_staggered: phase p's fractions on the doubly fine grid, shape (2nx, 2ny, 2nz)."""
         phi = np.ascontiguousarray(phi, dtype=np.float64)
@@ -133,7 +142,7 @@ class LSSolver:
                 if v not in kinds:
                     raise RuntimeError("Unknown error estimator '%s'" % v)
                 self._check(self._lib.fg_set_option_i(self._h, b"error_estimator", kinds[v]))
-            elif k in ("u_loop", "fuse_x", "cg_fused", "fuse_stress_div", "u_tile", "x_layout", "plane_fft", "slab_split", "slab_interleave", "slab_loopback", "laminate_overlap", "phi_sweep", "pair_chunk", "joint_x", "bluestein", "tile_plans", "staged_copy", "stage_chunk_kb"):
+            elif k in ("u_loop", "fuse_x", "cg_fused", "fuse_stress_div", "u_tile", "x_layout", "plane_fft", "slab_split", "slab_interleave", "slab_loopback", "laminate_overlap", "phi_sweep", "aniso_tile", "pair_chunk", "joint_x", "bluestein", "tile_plans", "staged_copy", "stage_chunk_kb"):
                 self._check(self._lib.fg_set_option_i(self._h, k.encode(), int(v)))
             elif k in ("maxiter", "loadstep_extrapolation_order"):
                 self._check(self._lib.fg_set_option_i(self._h, k.encode(), int(v)))
@@ -203,7 +212,8 @@ class LSSolver:
         """fg_get_counter: "interface_voxels", "affected_voxels" (lengths of the laminate lists); "fft_path_x|y|z" (how the axis
         is transformed: 0 length 1, 1 power of two, 2 sub-lines p * 2^k, 3 tile kernels, 4 Bluestein, 5 O(n^2)),
         "fft_bluestein_m_x|y|z" (padded length of the axis' Bluestein pass, 0 = not on Bluestein), "phase_uploads" (host
-        arrays received by set_phase / set_phase_fine / set_normals); -1 = unknown name."""
+        arrays received by set_phase / set_phase_fine / set_normals), "u_tile_aniso" (launches of the tiled sweep's anisotropic
+        form); -1 = unknown name."""
         return int(self._lib.fg_get_counter(self._h, name.encode()))
 
     def iterate(self, E, n):

@@ -65,6 +65,17 @@ void fg_destroy(fg_solver* s);
  * (F:7333-7454).  Phase order = materials order.  phi may be NULL to keep the current field. */
 int fg_set_num_phases(fg_solver* s, int nphases);
 int fg_set_phase(fg_solver* s, int p, double mu, double lambda, const double* phi /* [nx][ny][nz] */);
+/* Law "general", LinearGeneralMaterialLaw F:11233-11349: phase p gets the constant stiffness C, 36 doubles row-major, and is a
+ * general (anisotropic) phase until a later fg_set_phase(p, mu, lambda, ...) makes it isotropic again.  Convention of
+ * PK1 F:11254-11272: S_i = C_i0 E_0 + C_i1 E_1 + C_i2 E_2 + 2 (C_i3 E_3 + C_i4 E_4 + C_i5 E_5) -- the shear entries of C are Voigt
+ * (C44 = mu for an isotropic body), strain components 3..5 (23, 13, 12) are tensor components, the factor 2 sits in the product.
+ * FG_ERROR with "phase stiffness is not symmetric" unless |C_ij - C_ji| <= 1e-12 max|C|, "phase index out of range" for a bad
+ * p.  Elasticity mode, Voigt mixing, gamma_scheme staggered / collocated / willot, methods basic and cg, one GPU; laminate
+ * mixing, full_staggered / half_staggered, the modes heat / porous / viscosity and slab-decomposed solvers are refused with a
+ * message when the run (or the reference-material scan) starts.  The reference-material scan diagonalises every voxel's
+ * Voigt tangent ("General phases").  Two complementary phases run the displacement loop on the tiled sweep's
+ * anisotropic form (option aniso_tile); everything else runs the strain-state pass and the strain-space CG. */
+int fg_set_phase_stiffness(fg_solver* s, int p, const double* C /* [6][6] */);
 /* gamma_scheme 2: phase p's fractions on the doubly fine grid, [2nx][2ny][2nz] over the same box (initPhi after
  * select_dfg(true) F:17152-17230, normalised there).  The image is reduced on the device to the coarse field (the 8-cell
  * means of F:17180-17228, what "phi" returns) and to the three shear-group fractions, and is not kept.  A phase given through
@@ -112,7 +123,9 @@ int fg_set_normals(fg_solver* s, const double* normals /* [3][nx][ny][nz] */);
  * convergence callback also selects the four-kernel form, whose accessors see the iterate in place -- its residual history
  * equals the fused one's to rounding (different summation order), tests/test_gpu_cg_fused.py),
  * phi_sweep (1 = default: with two phases whose fractions are complementary bit for bit the tiled sweep reads phi_1 and
- * forms the effective moduli itself; 0 = always the two precomputed moduli arrays), laminate_overlap (1 = default: the interface kernels of the laminate correction run on a second stream beside the
+ * forms the effective moduli itself; 0 = always the two precomputed moduli arrays), aniso_tile (1 = default: two complementary
+ * phases with a general phase -- fg_set_phase_stiffness -- run the displacement loop on the tiled sweep's 6 x 6 form where
+ * u_tile, phi_sweep and the grid allow; 0 = the strain-state pass), laminate_overlap (1 = default: the interface kernels of the laminate correction run on a second stream beside the
  * displacement sweep; 0 = one stream), slab_split (slab driver: 1 = one all-to-all per component, overlapping the transforms of the next component; 0 = one
  * exchange for the three components; -1 = by slab size, default), slab_interleave (-1 = default: in the one-exchange mode a
  * peer's three components travel as ONE message where the sizes allow; 0 = one message per peer and component),
@@ -211,7 +224,8 @@ int fg_get_stage_timing_bias(const fg_solver* s, double* ms);
  * transformed: 0 length 1, 1 power of two, 2 sub-lines p * 2^k, 3 tile kernels, 4 Bluestein, 5 O(n^2) sums;
  * "fft_bluestein_m_x" / "_y" / "_z" = the padded length of the axis' Bluestein pass (0: the axis is not on Bluestein);
  * "phase_uploads" = host arrays this solver has received through fg_set_phase (with a field), fg_set_phase_field_fine and
- * fg_set_normals (fg_voxelize_into adds none).  Unknown names give -1. */
+ * fg_set_normals (fg_voxelize_into adds none); "u_tile_aniso" = launches of the tiled sweep's anisotropic form (general
+ * phases, option aniso_tile).  Unknown names give -1. */
 long fg_get_counter(const fg_solver* s, const char* name);
 
 /* Measurement helper (no counterpart in the reference): achieved HBM bandwidth of a streaming copy a = b and of the
