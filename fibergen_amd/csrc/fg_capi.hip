@@ -280,6 +280,10 @@ int fg_set_option_i(fg_solver* s, const char* key, long value) {
     else if (k == "plane_fft") o.plane_fft = value < 0 ? -1 : (value != 0);
     else if (k == "pair_chunk") o.pair_chunk = value < 0 ? 0 : (int)value;
     else if (k == "joint_x") o.joint_x = value != 0;
+    else if (k == "fft_images") {
+      o.fft_images = (value == 1 || value == 2) ? (int)value : -1;
+      v.apply_fft_images();
+    }
     else if (k == "bluestein") {
       o.bluestein = value != 0;
       v.apply_bluestein();

@@ -78,6 +78,12 @@ class Fft3 {
   // image per component: the same butterflies in either form
   void set_joint_x(bool on);
 
+  // exchange planes in LDS of the power-of-two y, x and (mirrored) z passes: 2 = real and imaginary plane side by side, 1 = one
+  // plane that the two parts cross in turn (half the LDS per workgroup, two more barriers per exchange), -1 = the measured
+  // default per pass and length (images_for).  Bit-identical results.  Per Fft3, not per process; other lengths: no effect.
+  void set_images(int images) { images_ = images; }
+  int images_for(int axis, int n) const;
+
   // lengths with a prime factor above 13, from fft::kBluesteinMin points on: Bluestein's algorithm on the tile kernels
   // (fg_fft_bluestein.h; default) or the O(n^2) sums every such length took before.  Per Fft3, not per process.
   void set_bluestein(bool on) { bluestein_ = on; }
@@ -102,6 +108,7 @@ class Fft3 {
   bool zodd_ = false;           // odd nz with a plan: the rows are transformed as nz complex points
   fft::SmoothPlan xfused_plan_[2];   // fused x pass of the tile kernels: [0] one component, [1] three (n = 0: none)
   bool joint_x_ = true;
+  int images_ = -1;
   bool blue_on(int axis) const { return bluestein_ && blue_[axis].n != 0; }
   fft::BluesteinPlan blue_[3];   // n != 0: the axis has neither of the faster passes and a Bluestein plan (z: of nz / 2, odd nz: of nz)
   cplx* blue_tab_[3][3];         // per axis: chirp c[k], k < n; filter B^[p], p < M; roots of M

@@ -34,12 +34,12 @@ template <class K>
 struct WaveLocal {
   static constexpr bool value = false;
 };
-template <int M, int LINES, bool MIRROR>
-struct WaveLocal<R2CKernel<M, LINES, MIRROR>> {
+template <int M, int LINES, bool MIRROR, int IMAGES>
+struct WaveLocal<R2CKernel<M, LINES, MIRROR, IMAGES>> {
   static constexpr bool value = (M / 8) <= 64 && 64 % (M / 8) == 0;
 };
-template <int M, int LINES, bool MIRROR>
-struct WaveLocal<C2RKernel<M, LINES, MIRROR>> {
+template <int M, int LINES, bool MIRROR, int IMAGES>
+struct WaveLocal<C2RKernel<M, LINES, MIRROR, IMAGES>> {
   static constexpr bool value = (M / 8) <= 64 && 64 % (M / 8) == 0;
 };
 
@@ -955,14 +955,27 @@ void xfused_nc(XFusedArgs a, int nouter, hipStream_t s) {
   FG_HIP_CHECK(hipGetLastError());
 }
 
+// StridedArgs::images picks the kernel with one or two exchange planes (a one-pass line, N = 8, exchanges nothing)
+template <int N, int C>
+void launch_strided_images(const StridedArgs& a, long nblocks, int dir, int ncomp, long comp_stride, hipStream_t s) {
+  if constexpr (num_passes(N) > 1) {
+    if (a.images == 1) {
+      if (dir < 0) launch_strided<StridedKernel<N, C, -1, 1>>(a, nblocks, ncomp, comp_stride, s);
+      else launch_strided<StridedKernel<N, C, +1, 1>>(a, nblocks, ncomp, comp_stride, s);
+      return;
+    }
+  }
+  if (dir < 0) launch_strided<StridedKernel<N, C, -1>>(a, nblocks, ncomp, comp_stride, s);
+  else launch_strided<StridedKernel<N, C, +1>>(a, nblocks, ncomp, comp_stride, s);
+}
+
 template <int N>
 void strided_n(const StridedArgs& a0, int nouter, int dir, int ncomp, long comp_stride, hipStream_t s) {
   constexpr int C = TileCols<N>::value;
   StridedArgs a = a0;
   a.tiles_per_outer = (a.ncols + C - 1) / C;
   long nblocks = (long)a.tiles_per_outer * nouter;
-  if (dir < 0) launch_strided<StridedKernel<N, C, -1>>(a, nblocks, ncomp, comp_stride, s);
-  else launch_strided<StridedKernel<N, C, +1>>(a, nblocks, ncomp, comp_stride, s);
+  launch_strided_images<N, C>(a, nblocks, dir, ncomp, comp_stride, s);
 }
 
 // the same with 8-column tiles whatever the length (sub-rows of the z pass have only p <= 15 columns)
@@ -971,8 +984,7 @@ void strided_n8(const StridedArgs& a0, int nouter, int dir, int ncomp, long comp
   StridedArgs a = a0;
   a.tiles_per_outer = (a.ncols + 7) / 8;
   long nblocks = (long)a.tiles_per_outer * nouter;
-  if (dir < 0) launch_strided<StridedKernel<N, 8, -1>>(a, nblocks, ncomp, comp_stride, s);
-  else launch_strided<StridedKernel<N, 8, +1>>(a, nblocks, ncomp, comp_stride, s);
+  launch_strided_images<N, 8>(a, nblocks, dir, ncomp, comp_stride, s);
 }
 void strided_pow2_narrow(int n, const StridedArgs& a, int nouter, int dir, int ncomp, long cs, hipStream_t s) {
   switch (n) {
@@ -1086,6 +1098,15 @@ void Fft3::set_joint_x(bool on) {
   }
 }
 
+// Exchange planes of the power-of-two y / x pass (axis 1 / 0) and of the mirrored z passes (axis 2, n = nz / 2 packed points).
+// The sub-line, plane, tile-plan, slab and fused-x kernels instantiate Line<N> with its default of two planes and are not asked.
+int Fft3::images_for(int axis, int n) const {
+  if (images_ == 1 || images_ == 2) return images_;
+  (void)axis;
+  (void)n;
+  return 2;
+}
+
 int Fft3::path(int axis) const {
   const int len = axis == 0 ? g_.nx : (axis == 1 ? g_.ny : g_.nz);
   if (len == 1) return 0;
@@ -1131,6 +1152,7 @@ void Fft3::strided(double* data, int ncomp, long comp_stride, int axis, int dir,
     a.nt = stream_stores_ ? (1 | ((nt_loads_env() & 1) ? 2 : 0)) : 0;
     if (w && w->nt >= 0) a.nt = w->nt;
     a.xcd_order = 0;   // (measured for the y passes: 512^3 -1..2 %, 256^3 +2 %)
+    a.images = images_for(axis, n);
     strided_pow2(n, a, nouter, dir, ncomp, comp_stride / 2, stream_);
     return;
   }
@@ -1350,6 +1372,7 @@ void Fft3::c2c_y_xlayout(double* in, long in_cs, double* out, long out_cs, int n
     a.data += (long)x0 * xl_os;
     a.out += (long)x0 * plain_os;
   }
+  a.images = images_for(1, g_.ny);
   strided_pow2_narrow(g_.ny, a, np, dir, ncomp, in_cs / 2, stream_);   // 8-column tiles: the layout's inner dimension
 }
 
@@ -1496,11 +1519,15 @@ void Fft3::r2c_z(double* data, int ncomp, long comp_stride, const PlaneWindow* w
   if (fast_[2]) {
     ZArgs a = {data, nrows, g_.nzp, tw_[2], wz_, stream_stores_ ? (1 | ((nt_loads_env() & 4) ? 2 : 0)) : 0};
     if (w && w->nt >= 0) a.nt = w->nt;
+    a.images = images_for(2, g_.nz / 2);
     // the real split right after the last pass, mirrored values by wave shuffle instead of a round trip of the spectrum
     // through LDS (R2CKernel<.., MIRROR>): 512^3 1.30 -> 1.16 ms, 256^3 0.158 -> 0.155 ms
     {
       switch (g_.nz / 2) {
-#define FG_CASE(m) case m: launch_z<R2CKernel<m, ZLines<m>::value, true>>(a, ncomp, comp_stride, ZLines<m>::value, stream_); return;
+#define FG_CASE(m) case m:                                                                                         \
+    if (a.images == 1) launch_z<R2CKernel<m, ZLines<m>::value, true, 1>>(a, ncomp, comp_stride, ZLines<m>::value, stream_); \
+    else launch_z<R2CKernel<m, ZLines<m>::value, true>>(a, ncomp, comp_stride, ZLines<m>::value, stream_);                \
+    return;
         FG_CASE(64) FG_CASE(128) FG_CASE(256) FG_CASE(512)
 #undef FG_CASE
         default: break;
@@ -1596,11 +1623,15 @@ void Fft3::c2r_z(double* data, int ncomp, long comp_stride, const PlaneWindow* w
   if (fast_[2]) {
     ZArgs a = {data, nrows, g_.nzp, tw_[2], wz_, stream_stores_ ? (1 | ((nt_loads_env() & 8) ? 2 : 0)) : 0};
     if (w && w->nt >= 0) a.nt = w->nt;
+    a.images = images_for(2, g_.nz / 2);
     // every coefficient read once: the mirrored one comes from the neighbouring lane (C2RKernel<.., MIRROR>); 256^3
     // 0.164 -> 0.151 ms, 512^3 1.38 -> 1.19 ms
     {
       switch (g_.nz / 2) {
-#define FG_CASE(m) case m: launch_z<C2RKernel<m, ZLines<m>::value, true>>(a, ncomp, comp_stride, ZLines<m>::value, stream_); return;
+#define FG_CASE(m) case m:                                                                                         \
+    if (a.images == 1) launch_z<C2RKernel<m, ZLines<m>::value, true, 1>>(a, ncomp, comp_stride, ZLines<m>::value, stream_); \
+    else launch_z<C2RKernel<m, ZLines<m>::value, true>>(a, ncomp, comp_stride, ZLines<m>::value, stream_);                \
+    return;
         FG_CASE(64) FG_CASE(128) FG_CASE(256) FG_CASE(512)
 #undef FG_CASE
         default: break;

@@ -154,6 +154,26 @@ struct Pass {
 #pragma unroll
       for (int r = 0; r < R; ++r) v[b * R + r] = lds_get(lds, L, in_index(jt, b, r), c);
   }
+  // One plane of the image at a time (Line<N, 1>): PART 0 moves the real parts, PART 1 the imaginary parts, both through the
+  // plane at offset 0 -- the same places and the same values as to_lds / from_lds, half the LDS.
+  template <int PART>
+  FG_HD static void to_lds_part(const cplx* v, int jt, double* lds, const LdsMap& L, int c) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int r = 0; r < R; ++r) lds[pad8(out_index(jt, b, r)) * L.sm + c * L.sc] = PART ? v[b * R + r].im : v[b * R + r].re;
+  }
+  template <int PART>
+  FG_HD static void from_lds_part(cplx* v, int jt, const double* lds, const LdsMap& L, int c) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const double x = lds[pad8(in_index(jt, b, r)) * L.sm + c * L.sc];
+        if (PART) v[b * R + r].im = x;
+        else v[b * R + r].re = x;
+      }
+  }
 };
 
 // Whole line transform split into barrier-separated phases so that the device
@@ -165,19 +185,50 @@ struct Pass {
 //   phase 2k           : compute pass k, scatter to LDS (not for the last pass)
 // After the last compute phase v holds the outputs for out_index of the last
 // pass, i.e. point  jt + b*T + r*N/R_last  in  v[b*R_last + r].
-template <int N>
+//
+// IMAGES = 2 (above): the exchange image holds the real and the imaginary plane side by side, 16 (N + N/8) bytes per line.
+// IMAGES = 1: ONE plane of 8 (N + N/8) bytes per line, which the real parts cross first and the imaginary parts second -- half
+// the LDS of a workgroup, so that more workgroups fit a CU, for two more phase boundaries per exchange:
+//   phase 4k     : compute pass k, scatter the real parts (not for the last pass)
+//   phase 4k + 1 : gather the real parts of the pass-(k+1) inputs      (v[].im still holds the pass-k outputs)
+//   phase 4k + 2 : scatter the imaginary parts
+//   phase 4k + 3 : gather the imaginary parts
+// Hazards that the boundary after each phase fences (a workgroup barrier, or the wave-local fence where a line stays inside
+// one wave): 4k+1 | 4k+2 and 4k+3 | 4k+4 -- a thread must not overwrite a place of the plane that another thread of the line
+// has yet to read; 4k | 4k+1 and 4k+2 | 4k+3 -- the usual write-before-read.  Same butterflies, twiddles and operation order
+// as IMAGES = 2: the results are bit-identical.
+template <int N, int IMAGES = 2>
 struct Line {
+  static_assert(IMAGES == 1 || IMAGES == 2, "Line: one or two exchange planes");
   static constexpr int NP = num_passes(N);
-  static constexpr int NPHASE = 2 * NP - 1;
+  static constexpr int NPHASE = IMAGES == 2 ? 2 * NP - 1 : 4 * (NP - 1) + 1;
   static constexpr int T = N / 8;
 
   template <int DIR, int PH>
   FG_HD static void phase(cplx* v, int jt, double* lds, const LdsMap& L, int c, const cplx* tw) {
+    if constexpr (IMAGES == 1) {
+      constexpr int P = PH / 4, S = PH % 4;
+      if constexpr (S == 0) {
+        constexpr int TW = tw_offset(N, P);
+        Pass<N, P>::template compute<DIR>(v, jt, tw + TW);
+        if constexpr (P + 1 < NP) Pass<N, P>::template to_lds_part<0>(v, jt, lds, L, c);
+      } else if constexpr (S == 1) {
+        Pass<N, P + 1>::template from_lds_part<0>(v, jt, lds, L, c);
+      } else if constexpr (S == 2) {
+        Pass<N, P>::template to_lds_part<1>(v, jt, lds, L, c);
+      } else {
+        Pass<N, P + 1>::template from_lds_part<1>(v, jt, lds, L, c);
+      }
+      return;
+    }
     constexpr int P = (PH + 1) / 2;
     if (PH % 2 == 1) {
       Pass<N, P>::from_lds(v, jt, lds, L, c);
     } else {
-      Pass<N, P>::template compute<DIR>(v, jt, tw + tw_offset(N, P));
+      // (a constant: left in the expression, the recursive tw_offset survived as a run-time call with a stack frame in every
+      // kernel of three and more passes)
+      constexpr int TW = tw_offset(N, P);
+      Pass<N, P>::template compute<DIR>(v, jt, tw + TW);
       if (P + 1 < NP) Pass<N, P>::to_lds(v, jt, lds, L, c);
     }
   }

@@ -55,15 +55,17 @@ struct StridedArgs {
   // plain layout's o*os + z*C)
   long ls_out = 0;
   long ts_in = 0, ts_out = 0;
+  int images = 2;            // exchange planes of the kernel to launch (Line<N, IMAGES>; Fft3::images_for), read by the host only
 };
 
-template <int N, int C, int DIR>
+template <int N, int C, int DIR, int IMAGES = 2>
 struct StridedKernel {
+  using Ln = Line<N, IMAGES>;
   static constexpr int T = N / 8;
   static constexpr int THREADS = T * C;
   static constexpr int PN = N + N / 8;
-  static constexpr int LDS_DOUBLES = 2 * PN * C;
-  static constexpr int NPHASE = Line<N>::NPHASE;
+  static constexpr int LDS_DOUBLES = IMAGES * PN * C;   // N = 256, C = 8: 36.9 KB (4 workgroups in 160 KB) / 18.4 KB (8)
+  static constexpr int NPHASE = Ln::NPHASE;
   struct Regs {
     cplx v[8];
     long base, obase;
@@ -84,19 +86,19 @@ struct StridedKernel {
       r.obase = a.out ? (long)o * a.os_out + (a.ts_out ? (long)tile * a.ts_out + r.t : (long)col) : r.base;
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        const int j = Line<N>::first_index(r.jt, q);
+        const int j = Ln::first_index(r.jt, q);
         r.v[q] = r.valid ? cload_stream(&a.data[r.base + (long)j * a.ls + (long)(j >> a.split_in) * a.jump_in], a.nt)
                          : cmake(0.0, 0.0);
       }
     }
-    Line<N>::template phase<DIR, PH>(r.v, r.jt, lds, L, r.t, a.tw);
+    Ln::template phase<DIR, PH>(r.v, r.jt, lds, L, r.t, a.tw);
     if (PH == NPHASE - 1 && r.valid) {
       cplx* const dst = a.out ? a.out : a.data;
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         cplx o = r.v[q];
         if (a.scale != 1.0) o = cscale(a.scale, o);
-        const int j = Line<N>::last_index(r.jt, q);
+        const int j = Ln::last_index(r.jt, q);
         cstore_stream(&dst[r.obase + (long)j * (a.ls_out ? a.ls_out : a.ls) + (long)(j >> a.split_out) * a.jump_out], o, a.nt);
       }
     }
@@ -112,18 +114,22 @@ struct ZArgs {
   const cplx* tw;   // pass twiddles of M
   const cplx* wz;   // e^{-2 pi i k/nz}, k = 0..M
   int nt;           // streaming stores
+  int images = 2;   // exchange planes of the kernel to launch (MIRROR kernels only), read by the host only
 };
 
 // MIRROR: the split X[k] from Z[k] and Z[M - k] takes the mirrored value from the lane that holds it (wave shuffle inside
 // the T lanes of the line) right after the last pass, instead of a round trip of the whole spectrum through LDS.
-template <int M, int LINES, bool MIRROR = false>
+// IMAGES = 1 (MIRROR only: the fall-back below parks the whole spectrum in both planes): Line<M, 1>, half the LDS.
+template <int M, int LINES, bool MIRROR = false, int IMAGES = 2>
 struct R2CKernel {
+  using Ln = Line<M, IMAGES>;
   static constexpr int T = M / 8;
   static constexpr int THREADS = T * LINES;
   static constexpr int LS = M + M / 8 + 2;       // line stride (doubles)
-  static constexpr int LDS_DOUBLES = 2 * LS * LINES;
+  static constexpr int LDS_DOUBLES = IMAGES * LS * LINES;
   static constexpr bool SHUFFLE = MIRROR && T <= 64 && T >= 2;
-  static constexpr int NPHASE = Line<M>::NPHASE + (SHUFFLE ? 0 : 1);
+  static_assert(IMAGES == 2 || SHUFFLE, "R2CKernel: one exchange plane with the shuffled split only");
+  static constexpr int NPHASE = Ln::NPHASE + (SHUFFLE ? 0 : 1);
   struct Regs {
     cplx v[8];
     double* row;
@@ -147,7 +153,7 @@ struct R2CKernel {
     }
 #if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (SHUFFLE) {
-      Line<M>::template phase<-1, PH>(r.v, r.jt, lds, L, r.l, a.tw);
+      Ln::template phase<-1, PH>(r.v, r.jt, lds, L, r.l, a.tw);
       if (PH == NPHASE - 1) {
         // slot q = (b, rr) of the last pass (radix RL) holds Z[jt + s T], s = b + rr (8 / RL); Z[M - k] is slot s' = 7 - s of
         // lane T - jt of this line (jt = 0: the own slot 8 - s, Z[M] := Z[0])
@@ -198,13 +204,15 @@ struct R2CKernel {
 // ------------------------------------------------------------------ z pass, c2r
 // MIRROR: the mirrored coefficient X[M - m] of the merge comes from the lane that loaded it as ITS X[m] (wave shuffle
 // inside the T lanes of the line) instead of a second global load: every coefficient is read once.
-template <int M, int LINES, bool MIRROR = false>
+template <int M, int LINES, bool MIRROR = false, int IMAGES = 2>
 struct C2RKernel {
+  using Ln = Line<M, IMAGES>;
   static constexpr int T = M / 8;
   static constexpr int THREADS = T * LINES;
   static constexpr int LS = M + M / 8 + 2;
-  static constexpr int LDS_DOUBLES = 2 * LS * LINES;
-  static constexpr int NPHASE = Line<M>::NPHASE;
+  static constexpr int LDS_DOUBLES = IMAGES * LS * LINES;
+  static_assert(IMAGES == 2 || MIRROR, "C2RKernel: one exchange plane for the MIRROR kernels only");
+  static constexpr int NPHASE = Ln::NPHASE;
   struct Regs {
     cplx v[8];
     double* row;
@@ -256,7 +264,7 @@ struct C2RKernel {
       }
       }
     }
-    Line<M>::template phase<+1, PH>(r.v, r.jt, lds, L, r.l, a.tw);
+    Ln::template phase<+1, PH>(r.v, r.jt, lds, L, r.l, a.tw);
     if (PH == NPHASE - 1 && r.valid) {
       cplx* out = reinterpret_cast<cplx*>(r.row);
 #pragma unroll
@@ -422,7 +430,8 @@ struct XFusedKernel {
     const cplx* tw = TW_LDS ? reinterpret_cast<const cplx*>(lds + TW_OFF) : a.tw;
     if (TW_LDS && PH == 0) {
       cplx* dst = reinterpret_cast<cplx*>(lds + TW_OFF);
-      for (int i = tid; i < tw_total(N); i += THREADS) dst[i] = a.tw[i];   // fenced by the barrier after phase 0
+      constexpr int NTW = tw_total(N);
+      for (int i = tid; i < NTW; i += THREADS) dst[i] = a.tw[i];   // fenced by the barrier after phase 0
     }
     if (PINGPONG) lds += ((LP / 2) % 2) * BUF_DOUBLES;
     if (PH == 0) {

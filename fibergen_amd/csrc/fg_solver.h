@@ -102,6 +102,8 @@ struct SolverOptions {
                                 // downloads of 8 MB and more, 1 always (both directions), 0 never (one strided copy)
   int joint_x = 1;              // tile kernels (lengths such as 100, 200, 300): the fused x pass of three components on ONE joint
                                 // image (1) or on one image per component (0); identical butterflies, the default is the faster form
+  int fft_images = -1;          // exchange planes in LDS of the power-of-two y / x / z transform passes (Fft3::set_images): -1 the measured
+                                // default per pass and length, 1 or 2 forced; bit-identical results, no effect on other lengths
   int bluestein = 1;            // lengths with a prime factor above 13 (67, 170, 190, 340 ..., from 64 points on): Bluestein's algorithm on the
                                 // tile kernels, O(n log n); 0: the O(n^2) sums (A/B runs).  Per solver (Solver::apply_bluestein)
   int tile_plans = 1;           // tile kernels (decimal sizes): the kernels built for one plan each where the plan is in their tables
@@ -141,6 +143,7 @@ class Solver {
 
   const Grid& grid() const { return g_; }
   SolverOptions& options() { return opt_; }
+  void apply_fft_images();  // hands opt_.fft_images to the transform this solver owns
   void apply_bluestein();   // hands opt_.bluestein to the transforms this solver owns
   void invalidate_moduli() { mod_dirty_ = mod5_dirty_ = smod_dirty_ = complement_dirty_ = true; }
   void invalidate_interface_lists() { mixed_dirty_ = true; }   // which lists exist depends on u_tile

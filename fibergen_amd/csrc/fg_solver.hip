@@ -123,6 +123,7 @@ Solver::Solver(int nx, int ny, int nz, double dx, double dy, double dz, int devi
   if (staged_copy(6 * comp, true)) (void)HostStager::of_device(device_);
 
   fft_.reset(new Fft3(g_, stream_));
+  fft_->set_images(opt_.fft_images);
   if (slab_layout_) {   // halo planes of the strain-state pipeline of the slab driver (tau going out, tau coming in)
     const size_t plane = (size_t)g_.nyzp * sizeof(double);
     for (int k = 0; k < 4; ++k) {
@@ -619,6 +620,9 @@ void Solver::enable_stage_timing(bool on) {
     event_bias_ms_ = bias;
   }
   timing_ = on;
+}
+void Solver::apply_fft_images() {   // (the slab passes of fft_ys_ keep two planes)
+  if (fft_) fft_->set_images(opt_.fft_images);
 }
 void Solver::apply_bluestein() {
   if (fft_) fft_->set_bluestein(opt_.bluestein != 0);

@@ -137,6 +137,8 @@ int fg_set_normals(fg_solver* s, const double* normals /* [3][nx][ny][nz] */);
  * error_estimator (0 epsilon = default, 1 residual, 2 sigma, 3 energy, 4 none: create_error_estimator F:14940-14972),
  * pair_chunk (0 = default; P: the z and y transform passes in runs of P x planes), staged_copy (-1 = default: field downloads of
  * 8 MB and more through the pinned-buffer pipeline; 1 both directions, 0 one strided copy), stage_chunk_kb (pipeline stage),
+ * fft_images (LDS exchange planes of the power-of-two y / x / z transform passes: -1 = default, the measured choice per pass and
+ * length; 2 = real and imaginary plane side by side; 1 = one plane crossed by the two parts in turn, half the LDS; bit-identical),
  * joint_x (tile kernels of the lengths that are not powers of two: 1 = default, fused x pass on one joint LDS image of the three
  * components; 0 = one image per component), tile_plans (1 = default: tile kernels built for one plan each where the plan is in
  * the tables of fg_fft_smooth_plans.h; 0 = the class kernels for every plan; a process-wide switch), bluestein (1 = default: an
