@@ -29,7 +29,7 @@ class SlabGroup {
   bool run(const double* E6, const double* S6);     // collective LSSolver::run (one load step); true = failed
   // runLoadsteppingSolver  F:21584-21685: steps first .. nparams-1 with params[i] * (E6, S6), each continuing from the one
   // before; basic scheme or CG (runCGElasticity F:23153-23247: displacement space where the fast path applies, strain
-  // space otherwise)
+  // space otherwise; the pipelined iteration itself is fg_cg_loop.h)
   bool run_load_steps(const double* E6, const double* S6, const double* params, int nparams, int first, LoadstepCallback step_cb,
                       void* user);
   void iterate(const double* E6, int n);            // n passes without the stop rule (bench, profiling)
@@ -59,6 +59,17 @@ class SlabGroup {
   template <class BcOk>
   bool converged(const StopRule& rule, long iter, bool voting, BcOk bc_ok, bool* failed, bool callbacks = true);
   void set_sumsq(int slot, int ncomp);
+  // the CG loops (the pipelined iteration itself: fg_cg_loop.h)
+  void cg_fetch(int slot);                                             // D2H of the seven reduced sums + flag and error words
+  void cg_wait() { wait_norms(); }
+  bool cg_may_run_ahead() const { return !cg_voting_; }                // no rank votes on what a callback saw in between
+  bool converged(const StopRule& rule, long iter, const std::function<bool()>& bc_ok, bool* failed) {
+    return converged(rule, iter, cg_voting_, bc_ok, failed, cg_callbacks_);
+  }
+  bool cg_voting_ = false, cg_callbacks_ = true;                       // of the pipelined CG run in progress
+  template <class Site>
+  friend CgResult cg_pipelined(Site&, const CgPipelinedOps&, StopRule&, const CgSlots&, double);
+  void set_state_u(const double* E);                                   // the iterate is (E, u_e) on every member
   void finish_cg_u(long iter, const double* E, double t_start);
   void vote(double* v2);                                               // sums of two host values over the ranks
   void pass_exact(const double* E6, bool mixed_bc);                    // strain-state pipeline, adopts

@@ -705,19 +705,38 @@ void SlabGroup::set_sumsq(int slot, int ncomp) {
   }
 }
 
-// end of a CG run in displacement / potential space: the state is (E, u_e), the strain field is materialised from it
-void SlabGroup::finish_cg_u(long iter, const double* E, double t_start) {
+// CG in displacement / potential space: what accessors called from a callback / bc_error see is eps = E + grad_s u_e
+void SlabGroup::set_state_u(const double* E) {
   for (Solver* s : m_) {
-    s->in_run_ = false;
-    s->iterations_ = iter;
     s->su_valid_ = true;
     s->eps_stale_ = true;
     for (int c = 0; c < 6; ++c) s->E_cur_[c] = E[c];
+  }
+}
+
+// end of a CG run in displacement / potential space: the state is (E, u_e), the strain field is materialised from it
+void SlabGroup::finish_cg_u(long iter, const double* E, double t_start) {
+  set_state_u(E);
+  for (Solver* s : m_) {
+    s->in_run_ = false;
+    s->iterations_ = iter;
     s->slab_materialise_eps();
   }
   synchronize();
   const double dt = now_seconds() - t_start;
   for (Solver* s : m_) s->solve_time_ += dt;
+}
+
+// The pipelined CG loops' fetch (fg_cg_loop.h): the seven reduced sums of dscal_[slot ..] with the flag and error words start
+// for every host; wait_norms() waits for them.
+void SlabGroup::cg_fetch(int slot) {
+  for (Solver* s : m_) {
+    FG_HIP_CHECK(hipMemcpyAsync(s->hscal_ + kSlotCg, s->dscal_ + slot, 7 * sizeof(double), hipMemcpyDeviceToHost, s->comm_stream_));
+    FG_HIP_CHECK(hipMemcpyAsync(s->hscal_ + kSlotFlag, s->dscal_ + kSlotFlag, 2 * sizeof(double), hipMemcpyDeviceToHost,
+                                s->comm_stream_));
+    FG_HIP_CHECK(hipMemcpyAsync(s->herr_, s->derr_, sizeof(int), hipMemcpyDeviceToHost, s->comm_stream_));
+    FG_HIP_CHECK(hipEventRecord(s->ev_norm_, s->comm_stream_));
+  }
 }
 
 // all members have left their local contribution in dscal_[slot..slot+n): reduce over ranks, bring to every host
@@ -1197,7 +1216,7 @@ bool SlabGroup::run_cg(const double* E6, const double* S6, bool fresh) {
   const bool voting = agree_on_voting();
   const double small = std::numeric_limits<double>::min();
   const double nglobal = (double)a.nglobal_;
-  const int blk[2] = {kSlotCg, kSlotCg + 8}, s0 = kSlotCg + 16;
+  const CgSlots slot = cg_slots(kSlotCg);
   Vec6 E, Z;
   for (int i = 0; i < 6; ++i) E.v[i] = E0[i], Z.v[i] = 0.0;
 
@@ -1205,6 +1224,7 @@ bool SlabGroup::run_cg(const double* E6, const double* S6, bool fresh) {
   auto u_w = [](Solver* s) { return s->su_[s->su_cur_ ^ 1]; };
   auto u_r = [](Solver* s) { return s->cgs_r_; };
   auto u_p = [](Solver* s) { return s->cgs_p_; };
+  auto v3 = [](Solver* s, double* b) { return strided3(b, s->ucs_); };
   // Fused form (option cg_fused, as Solver::run_cg_u): p:(p - w) and the update of eps, r with their norms as two tiled sweeps
   // (the own planes of the alternate buffers; their spare planes by a point-wise kernel), the direction update inside the
   // operator's sweep (Voigt mixing).
@@ -1215,23 +1235,6 @@ bool SlabGroup::run_cg(const double* E6, const double* S6, bool fresh) {
     for (Solver* s : m_) s->slab_front_laminate(false, false);
     pass_fast_chain();
   };
-  auto fetch7 = [&](int slot) {
-    for (Solver* s : m_) {
-      FG_HIP_CHECK(hipMemcpyAsync(s->hscal_ + kSlotCg, s->dscal_ + slot, 7 * sizeof(double), hipMemcpyDeviceToHost, s->comm_stream_));
-      FG_HIP_CHECK(hipMemcpyAsync(s->hscal_ + kSlotFlag, s->dscal_ + kSlotFlag, 2 * sizeof(double), hipMemcpyDeviceToHost,
-                                  s->comm_stream_));
-      FG_HIP_CHECK(hipMemcpyAsync(s->herr_, s->derr_, sizeof(int), hipMemcpyDeviceToHost, s->comm_stream_));
-      FG_HIP_CHECK(hipEventRecord(s->ev_norm_, s->comm_stream_));
-    }
-  };
-  auto direction_update = [&](int cur, int nxt) {   // p = r + beta p, beta = delta / gamma
-    for (Solver* s : m_) {
-      s->comm_wait(kXSums);
-      launch_cgu_axpy(1, s->gu_, strided3(u_e(s), s->ucs_), strided3(u_p(s), s->ucs_), strided3(u_r(s), s->ucs_),
-                      strided3(u_w(s), s->ucs_), s->dscal_, blk[nxt] + 6, blk[cur] + 6, nglobal, small, s->stream_, s->ucs_);
-    }
-  };
-
   for (Solver* s : m_) {
     s->slab_cg_alloc();
     s->cgs_r_ = s->scg_;
@@ -1256,101 +1259,83 @@ bool SlabGroup::run_cg(const double* E6, const double* S6, bool fresh) {
     }
     s->comm_wait(kXHaloU);
     FG_HIP_CHECK(hipMemsetAsync(u_e(s), 0, 3 * (size_t)s->ucs_ * sizeof(double), s->stream_));   // eps_0 = E
-    s->su_valid_ = true;
-    s->eps_stale_ = true;
     s->in_run_ = true;
-    for (int i = 0; i < 6; ++i) s->E_cur_[i] = E0[i];
   }
-  auto apply_dir = [&](int cur, int nxt) {   // fused: p = r + beta p inside the sweep; u_w = operator(u_p)
-    for (Solver* s : m_) {
-      s->comm_wait(kXSums);
-      s->slab_front_fast_cg(Z.v, blk[nxt] + 6, blk[cur] + 6, nglobal, small);
-    }
-    pass_fast_chain();
-  };
+  set_state_u(E.v);
   apply(false, E.v);   // r = -Gamma0 (C - C0) E  (+ E - eps_0 = 0, adjustResidual F:10012-10022)
   for (Solver* s : m_) {
     s->comm_wait(kXHaloU);
     const size_t f3 = 3 * (size_t)s->ucs_ * sizeof(double);
     FG_HIP_CHECK(hipMemcpyAsync(u_r(s), u_w(s), f3, hipMemcpyDeviceToDevice, s->stream_));
     FG_HIP_CHECK(hipMemcpyAsync(u_p(s), u_w(s), f3, hipMemcpyDeviceToDevice, s->stream_));   // p = r
-    launch_cgu_dot(1, s->gu_, strided3(u_e(s), s->ucs_), strided3(u_r(s), s->ucs_), E, s->partial_, s->dscal_ + blk[0], s->stream_);
-    s->slab_reduce(blk[0], 7, false);   // gamma_0 = r:r / N + tiny
+    launch_cgu_dot(1, s->gu_, v3(s, u_e(s)), v3(s, u_r(s)), E, s->partial_, s->dscal_ + slot.blk[0], s->stream_);
+    s->slab_reduce(slot.blk[0], 7, false);   // gamma_0 = r:r / N + tiny
   }
   double gamma_0 = 0.0;   // only the residual estimator reads it
   if (a.opt_.error_estimator == 1) {
-    fetch7(blk[0]);
+    cg_fetch(slot.blk[0]);
     wait_norms();
     gamma_0 = a.hscal_[kSlotCg + 6] / nglobal + small;
   }
   StopRule rule = a.stop_rule(prev0, gamma_0);
-  long iter = 0;
-  bool failed = false, applied = false;
-  int dir_cur = 0, dir_nxt = 1;   // fused: slots of the pending direction update
-  for (;;) {
-    const int cur = (int)(iter & 1), nxt = cur ^ 1;
-    if (!applied) {
-      if (fused_dir && iter > 0) apply_dir(dir_cur, dir_nxt);
-      else apply(true, Z.v);   // u_w = operator(u_p)
+  CgPipelinedOps ops;
+  ops.fused_dir = fused_dir;
+  ops.apply_p = [&] { apply(true, Z.v); };      // u_w = operator(u_p)
+  ops.apply_dir = [&](int num, int den) {       // fused: p = r + beta p inside the sweep; u_w = operator(u_p)
+    for (Solver* s : m_) {
+      s->comm_wait(kXSums);
+      s->slab_front_fast_cg(Z.v, num, den, nglobal, small);
     }
-    applied = false;
+    pass_fast_chain();
+  };
+  ops.direction = [&](int num, int den) {       // p = r + beta p, beta = delta / gamma
+    for (Solver* s : m_) {
+      s->comm_wait(kXSums);
+      launch_cgu_axpy(1, s->gu_, v3(s, u_e(s)), v3(s, u_p(s)), v3(s, u_r(s)), v3(s, u_w(s)), s->dscal_, num, den, nglobal, small,
+                      s->stream_, s->ucs_);
+    }
+  };
+  ops.dot_pw = [&](int out) {
     for (Solver* s : m_) {
       s->comm_wait(kXHaloU);
       s->comm_wait(kXSums);
       if (fused)
-        launch_cgu_tile(0, s->gu_, strided3(u_p(s), s->ucs_), strided3(u_w(s), s->ucs_), strided3(u_p(s), s->ucs_),
-                        strided3(u_w(s), s->ucs_), strided3(s->su_alt_, s->ucs_), strided3(s->cgs_ra_, s->ucs_), Z, s->dscal_, 0, 0,
-                        nglobal, small, s->partial_, s->dscal_ + s0, s->stream_);
+        launch_cgu_tile(0, s->gu_, v3(s, u_p(s)), v3(s, u_w(s)), v3(s, u_p(s)), v3(s, u_w(s)), v3(s, s->su_alt_), v3(s, s->cgs_ra_), Z,
+                        s->dscal_, 0, 0, nglobal, small, s->partial_, s->dscal_ + out, s->stream_);
       else
-        launch_cgu_dot(0, s->gu_, strided3(u_p(s), s->ucs_), strided3(u_w(s), s->ucs_), Z, s->partial_, s->dscal_ + s0, s->stream_);
-      s->slab_reduce(s0, 1, false);   // p : (p - w)
+        launch_cgu_dot(0, s->gu_, v3(s, u_p(s)), v3(s, u_w(s)), Z, s->partial_, s->dscal_ + out, s->stream_);
+      s->slab_reduce(out, 1, false);   // p : (p - w)
     }
+  };
+  ops.update = [&](int gamma, int pw, int out) {
     for (Solver* s : m_) {
       s->comm_wait(kXSums);
       // eps += alpha p ; r -= alpha (p - w),  alpha = gamma / (p:(p - w) / N + tiny); spare planes included
       if (fused) {
-        launch_cgu_tile(1, s->gu_, strided3(u_e(s), s->ucs_), strided3(u_r(s), s->ucs_), strided3(u_p(s), s->ucs_),
-                        strided3(u_w(s), s->ucs_), strided3(s->su_alt_, s->ucs_), strided3(s->cgs_ra_, s->ucs_), E, s->dscal_,
-                        blk[cur] + 6, s0, nglobal, small, s->partial_, s->dscal_ + blk[nxt], s->stream_);
-        launch_cgu_axpy_oop(0, strided3(u_e(s), s->ucs_), strided3(u_p(s), s->ucs_), strided3(u_r(s), s->ucs_),
-                            strided3(u_w(s), s->ucs_), strided3(s->su_alt_, s->ucs_), strided3(s->cgs_ra_, s->ucs_), s->dscal_,
-                            blk[cur] + 6, s0, nglobal, small, s->g_.n, s->ucs_ - s->g_.n, s->stream_);
+        launch_cgu_tile(1, s->gu_, v3(s, u_e(s)), v3(s, u_r(s)), v3(s, u_p(s)), v3(s, u_w(s)), v3(s, s->su_alt_), v3(s, s->cgs_ra_), E,
+                        s->dscal_, gamma, pw, nglobal, small, s->partial_, s->dscal_ + out, s->stream_);
+        launch_cgu_axpy_oop(0, v3(s, u_e(s)), v3(s, u_p(s)), v3(s, u_r(s)), v3(s, u_w(s)), v3(s, s->su_alt_), v3(s, s->cgs_ra_), s->dscal_,
+                            gamma, pw, nglobal, small, s->g_.n, s->ucs_ - s->g_.n, s->stream_);
         std::swap(s->su_[s->su_cur_], s->su_alt_);
         std::swap(s->cgs_r_, s->cgs_ra_);
       } else {
-        launch_cgu_axpy(0, s->gu_, strided3(u_e(s), s->ucs_), strided3(u_p(s), s->ucs_), strided3(u_r(s), s->ucs_),
-                        strided3(u_w(s), s->ucs_), s->dscal_, blk[cur] + 6, s0, nglobal, small, s->stream_, s->ucs_);
-        launch_cgu_dot(1, s->gu_, strided3(u_e(s), s->ucs_), strided3(u_r(s), s->ucs_), E, s->partial_, s->dscal_ + blk[nxt], s->stream_);
+        launch_cgu_axpy(0, s->gu_, v3(s, u_e(s)), v3(s, u_p(s)), v3(s, u_r(s)), v3(s, u_w(s)), s->dscal_, gamma, pw, nglobal, small,
+                        s->stream_, s->ucs_);
+        launch_cgu_dot(1, s->gu_, v3(s, u_e(s)), v3(s, u_r(s)), E, s->partial_, s->dscal_ + out, s->stream_);
       }
-      s->slab_reduce(blk[nxt], 7, false);   // norms of eps ; r : r
+      s->slab_reduce(out, 7, false);   // norms of eps ; r : r
     }
-    fetch7(blk[nxt]);
-    if (!voting && iter < a.opt_.maxiter) {   // the next direction and operator application, enqueued behind the copies
-      if (fused_dir) {
-        apply_dir(cur, nxt);
-      } else {
-        direction_update(cur, nxt);
-        apply(true, Z.v);
-      }
-      applied = true;
-    }
-    wait_norms();
-    for (Solver* s : m_) {   // state for accessors called from the callback / bc_error: eps = E + grad_s u_e
-      s->su_valid_ = true;
-      s->eps_stale_ = true;
-      for (int c = 0; c < 6; ++c) s->E_cur_[c] = E.v[c];
-    }
+  };
+  ops.sums = [&] {
+    set_state_u(E.v);   // eps = E + grad_s u_e
     set_sumsq(kSlotCg, 6);
-    rule.measure(norm9_of_sums(a.sumsq_, nglobal), a.hscal_[kSlotCg + 6] / nglobal + small);   // r:r after the update: the next gamma
-    if (converged(rule, iter, voting, [&] { return bc_error(E0, S0) <= a.opt_.bc_tol; }, &failed)) break;
-    iter++;
-    if (!applied) {
-      if (fused_dir) dir_cur = cur, dir_nxt = nxt;   // formed inside the next operator application
-      else direction_update(cur, nxt);
-    }
-  }
-  finish_cg_u(iter, E.v, t_start);
-  return failed;
+    return CgSums{norm9_of_sums(a.sumsq_, nglobal), a.hscal_[kSlotCg + 6]};
+  };
+  ops.bc_ok = [&] { return bc_error(E0, S0) <= a.opt_.bc_tol; };
+  cg_voting_ = voting, cg_callbacks_ = true;
+  const CgResult end = cg_pipelined(*this, ops, rule, slot, nglobal);
+  finish_cg_u(end.iter, E.v, t_start);
+  return end.failed;
 }
 
 // The same CG for the scalar modes, carried in potential space like Solver::run_cg_scalar (g = E + grad T_e; r, p, w = grad T_r,
@@ -1394,16 +1379,15 @@ bool SlabGroup::run_cg_scalar(const double* E0, double prev0) {
                        s->dscal_ + slot, s->stream_);
     }
     reduce_and_fetch(slot, n, false);
+    return a.hscal_[slot];
   };
   for (Solver* s : m_) {
     s->slab_cg_alloc();
     s->comm_wait(kXHaloU);
     FG_HIP_CHECK(hipMemsetAsync(T_e(s), 0, 3 * (size_t)s->ucs_ * sizeof(double), s->stream_));   // g_0 = E
-    s->su_valid_ = true;
-    s->eps_stale_ = true;
     s->in_run_ = true;
-    for (int i = 0; i < 6; ++i) s->E_cur_[i] = E.v[i];
   }
+  set_state_u(E.v);
   apply(false, E.v);
   for (Solver* s : m_) {
     s->comm_wait(kXHaloU);
@@ -1411,10 +1395,9 @@ bool SlabGroup::run_cg_scalar(const double* E0, double prev0) {
     FG_HIP_CHECK(hipMemcpyAsync(T_r(s), T_w(s), f1, hipMemcpyDeviceToDevice, s->stream_));
     FG_HIP_CHECK(hipMemcpyAsync(T_p(s), T_w(s), f1, hipMemcpyDeviceToDevice, s->stream_));   // p = r
   }
-  // Fused form (option cg_fused; see Solver::run_cg_scalar and SlabGroup::run_cg): two tiled sweeps for the vector work, the
-  // direction update inside the operator's sweep, the CG scalars on the device (all-reduced there), the next operator
-  // application enqueued before the hosts wait for the sums.  Alternates: T_e in component 1 of its buffer (copied back to
-  // component 0 at the end), T_r / T_p in components 2, 3 of scg_.  Not with convergence callbacks (accessors read component 0).
+  // Fused form (option cg_fused; see Solver::run_cg_scalar and SlabGroup::run_cg; the sums are all-reduced on the device).
+  // Alternates: T_e in component 1 of its buffer (copied back to component 0 at the end), T_r / T_p in components 2, 3 of
+  // scg_.  Not with convergence callbacks (accessors read component 0).
   bool fused = a.opt_.cg_fused != 0 && !voting;
   for (Solver* s : m_) fused = fused && sc_sweep_tiled(s->gu_);
   if (a.nranks_ > 1) {   // the two forms issue different reductions: every rank takes the form all of them can take
@@ -1423,16 +1406,7 @@ bool SlabGroup::run_cg_scalar(const double* E0, double prev0) {
     fused = v[0] == 0.0;
   }
   if (fused) {
-    const int blk[2] = {kSlotCg, kSlotCg + 8}, s0 = kSlotCg + 16;
-    auto fetch7 = [&](int slot) {
-      for (Solver* s : m_) {
-        FG_HIP_CHECK(hipMemcpyAsync(s->hscal_ + kSlotCg, s->dscal_ + slot, 7 * sizeof(double), hipMemcpyDeviceToHost, s->comm_stream_));
-        FG_HIP_CHECK(hipMemcpyAsync(s->hscal_ + kSlotFlag, s->dscal_ + kSlotFlag, 2 * sizeof(double), hipMemcpyDeviceToHost,
-                                    s->comm_stream_));
-        FG_HIP_CHECK(hipMemcpyAsync(s->herr_, s->derr_, sizeof(int), hipMemcpyDeviceToHost, s->comm_stream_));
-        FG_HIP_CHECK(hipEventRecord(s->ev_norm_, s->comm_stream_));
-      }
-    };
+    const CgSlots slot = cg_slots(kSlotCg);
     for (Solver* s : m_) {
       s->cgs_r_ = s->scg_;
       s->cgs_p_ = s->scg_ + s->ucs_;
@@ -1441,102 +1415,91 @@ bool SlabGroup::run_cg_scalar(const double* E0, double prev0) {
     }
     std::vector<double*> e_cur(m_.size()), e_alt(m_.size());
     for (size_t i = 0; i < m_.size(); ++i) e_cur[i] = T_e(m_[i]), e_alt[i] = T_e(m_[i]) + m_[i]->ucs_;
-    auto apply_dir = [&](int cur, int nxt) {
-      for (Solver* s : m_) {
-        s->comm_wait(kXSums);
-        s->slab_front_fast_sc_cg(blk[nxt] + 6, blk[cur] + 6, nglobal, small);
-      }
-      pass_fast_chain();
-    };
     for (size_t i = 0; i < m_.size(); ++i) {
       Solver* s = m_[i];
       s->comm_wait(kXHaloU);
       s->comm_wait(kXSums);
-      launch_sc_cg_dot(1, s->gu_, e_cur[i], s->cgs_r_, E, s->partial_, s->dscal_ + blk[0], s->stream_);
-      s->slab_reduce(blk[0], 7, false);   // gamma_0 = r.r / N + tiny
+      launch_sc_cg_dot(1, s->gu_, e_cur[i], s->cgs_r_, E, s->partial_, s->dscal_ + slot.blk[0], s->stream_);
+      s->slab_reduce(slot.blk[0], 7, false);   // gamma_0 = r.r / N + tiny
     }
-    fetch7(blk[0]);
+    cg_fetch(slot.blk[0]);
     wait_norms();
     StopRule rule = a.stop_rule(prev0, a.hscal_[kSlotCg + 6] / nglobal + small);
-    long iter = 0;
-    bool failed = false, applied = false;
-    for (;;) {
-      const int cur = (int)(iter & 1), nxt = cur ^ 1;
-      if (!applied) {   // the first iteration: p = r
-        for (Solver* s : m_) s->slab_front_fast(Z.v, false, s->cgs_p_, false);
-        pass_fast_chain();
+    CgPipelinedOps ops;
+    ops.fused_dir = true;
+    ops.apply_p = [&] {
+      for (Solver* s : m_) s->slab_front_fast(Z.v, false, s->cgs_p_, false);
+      pass_fast_chain();
+    };
+    ops.apply_dir = [&](int num, int den) {
+      for (Solver* s : m_) {
+        s->comm_wait(kXSums);
+        s->slab_front_fast_sc_cg(num, den, nglobal, small);
       }
-      applied = false;
+      pass_fast_chain();
+    };
+    ops.dot_pw = [&](int out) {
       for (size_t i = 0; i < m_.size(); ++i) {
         Solver* s = m_[i];
         s->comm_wait(kXHaloU);
         s->comm_wait(kXSums);
         launch_sc_cgu_tile(0, s->gu_, s->cgs_p_, T_w(s), s->cgs_p_, T_w(s), e_alt[i], s->cgs_ra_, Z, s->dscal_, 0, 0, nglobal, small,
-                           s->partial_, s->dscal_ + s0, s->stream_);
-        s->slab_reduce(s0, 1, false);   // p . (p - w)
+                           s->partial_, s->dscal_ + out, s->stream_);
+        s->slab_reduce(out, 1, false);   // p . (p - w)
       }
+    };
+    ops.update = [&](int gamma, int pw, int out) {
       for (size_t i = 0; i < m_.size(); ++i) {
         Solver* s = m_[i];
         s->comm_wait(kXSums);
-        launch_sc_cgu_tile(1, s->gu_, e_cur[i], s->cgs_r_, s->cgs_p_, T_w(s), e_alt[i], s->cgs_ra_, E, s->dscal_, blk[cur] + 6, s0, nglobal,
-                           small, s->partial_, s->dscal_ + blk[nxt], s->stream_);
-        launch_sc_cg_axpy_oop(0, e_cur[i], s->cgs_p_, s->cgs_r_, T_w(s), e_alt[i], s->cgs_ra_, s->dscal_, blk[cur] + 6, s0, nglobal,
-                              small, s->g_.n, s->ucs_ - s->g_.n, s->stream_);
+        launch_sc_cgu_tile(1, s->gu_, e_cur[i], s->cgs_r_, s->cgs_p_, T_w(s), e_alt[i], s->cgs_ra_, E, s->dscal_, gamma, pw, nglobal, small,
+                           s->partial_, s->dscal_ + out, s->stream_);
+        launch_sc_cg_axpy_oop(0, e_cur[i], s->cgs_p_, s->cgs_r_, T_w(s), e_alt[i], s->cgs_ra_, s->dscal_, gamma, pw, nglobal, small,
+                              s->g_.n, s->ucs_ - s->g_.n, s->stream_);
         std::swap(e_cur[i], e_alt[i]);
         std::swap(s->cgs_r_, s->cgs_ra_);
-        s->slab_reduce(blk[nxt], 7, false);   // norms of g ; r . r
+        s->slab_reduce(out, 7, false);   // norms of g ; r . r
       }
-      fetch7(blk[nxt]);
-      if (iter < a.opt_.maxiter) {   // the next direction and operator application, enqueued behind the copies
-        apply_dir(cur, nxt);
-        applied = true;
-      }
-      wait_norms();
+    };
+    ops.sums = [&] {
       set_sumsq(kSlotCg, 3);
-      rule.measure(norm_of_sums(a.sumsq_), a.hscal_[kSlotCg + 6] / nglobal + small);   // r.r after the update: the next gamma
-      auto bc_ok = [&] {
-        // bc_error reads the gradient of the current iterate: component 0 of the state buffer must be it
-        for (size_t i = 0; i < m_.size(); ++i) {
-          Solver* s = m_[i];
-          if (e_cur[i] != T_e(s)) {
-            FG_HIP_CHECK(hipMemcpyAsync(T_e(s), e_cur[i], (size_t)s->ucs_ * sizeof(double), hipMemcpyDeviceToDevice, s->stream_));
-            std::swap(e_cur[i], e_alt[i]);
-          }
-          s->su_valid_ = true;
-          s->eps_stale_ = true;
-          for (int c = 0; c < 6; ++c) s->E_cur_[c] = E.v[c];
+      return CgSums{norm_of_sums(a.sumsq_), a.hscal_[kSlotCg + 6]};
+    };
+    ops.bc_ok = [&] {
+      // bc_error reads the gradient of the current iterate: component 0 of the state buffer must be it
+      for (size_t i = 0; i < m_.size(); ++i) {
+        Solver* s = m_[i];
+        if (e_cur[i] != T_e(s)) {
+          FG_HIP_CHECK(hipMemcpyAsync(T_e(s), e_cur[i], (size_t)s->ucs_ * sizeof(double), hipMemcpyDeviceToDevice, s->stream_));
+          std::swap(e_cur[i], e_alt[i]);
         }
-        return bc_error(E.v, S_zero) <= a.opt_.bc_tol;
-      };
-      if (converged(rule, iter, voting, bc_ok, &failed, false)) break;
-      iter++;
-    }
+      }
+      set_state_u(E.v);
+      return bc_error(E.v, S_zero) <= a.opt_.bc_tol;
+    };
+    cg_voting_ = voting, cg_callbacks_ = false;   // (no rank votes in this form: every iteration runs ahead)
+    const CgResult end = cg_pipelined(*this, ops, rule, slot, nglobal);
     for (size_t i = 0; i < m_.size(); ++i) {
       Solver* s = m_[i];
       if (e_cur[i] != T_e(s))
         FG_HIP_CHECK(hipMemcpyAsync(T_e(s), e_cur[i], (size_t)s->ucs_ * sizeof(double), hipMemcpyDeviceToDevice, s->stream_));
     }
-    finish_cg_u(iter, E.v, t_start);
-    return failed;
+    finish_cg_u(end.iter, E.v, t_start);
+    return end.failed;
   }
   dot(1, false, false, kSlotCg, 7);
   StopRule rule = a.stop_rule(prev0, a.hscal_[kSlotCg + 6] / nglobal + small);
   double& gamma = rule.gamma_cur;
   long iter = 0;
   bool failed = false;
-  for (;;) {
+  for (;;) {   // alpha and beta on the host
     apply(true, Z.v);                       // T_w = operator(T_p)
-    dot(0, true, true, kSlotCg + 8, 1);     // p : (p - w)
-    const double alpha = gamma / (a.hscal_[kSlotCg + 8] / nglobal + small);
+    const double alpha = gamma / (dot(0, true, true, kSlotCg + 8, 1) / nglobal + small);   // p : (p - w)
     for (Solver* s : m_)   // g += alpha p ; r -= alpha (p - w), spare planes included
       launch_sc_cg_axpy(0, s->gu_, T_e(s), T_p(s), T_r(s), T_w(s), alpha, s->stream_, s->ucs_);
     dot(1, false, false, kSlotCg, 7);       // norms of g ; r : r
     const double rr = a.hscal_[kSlotCg + 6];
-    for (Solver* s : m_) {
-      s->su_valid_ = true;
-      s->eps_stale_ = true;
-      for (int c = 0; c < 6; ++c) s->E_cur_[c] = E.v[c];
-    }
+    set_state_u(E.v);
     set_sumsq(kSlotCg, 3);
     rule.measure(norm_of_sums(a.sumsq_));
     if (converged(rule, iter, voting, [&] { return bc_error(E.v, S_zero) <= a.opt_.bc_tol; }, &failed)) break;
@@ -1597,6 +1560,7 @@ bool SlabGroup::run_cg_strain(const double* E0, const double* S0, double prev0) 
     for (Solver* s : m_)
       launch_cg(mode, s->g_, s->ptrs6(s->*x), s->ptrs6(s->*y), s->ptrs6(s->*z), E, alpha, s->partial_, s->dscal_ + slot, s->stream_);
     if (n > 0) reduce_and_fetch(slot, n, false);
+    return a.hscal_[slot];   // (the reduced sum; n = 0: nothing was fetched)
   };
   for (Solver* s : m_) {
     s->comm_wait(kXHaloU);
@@ -1606,25 +1570,25 @@ bool SlabGroup::run_cg_strain(const double* E0, const double* S0, double prev0) 
     for (int i = 0; i < 6; ++i) s->E_cur_[i] = E.v[i];
   }
   apply(&Solver::eps_, &Solver::cg_r_);                                          // r = -Gamma0 (C - C0) eps
-  dot(0, &Solver::cg_r_, &Solver::eps_, &Solver::eps_, 0.0, kSlotMean, 1);       // r += E - eps ; r:r
-  StopRule rule = a.stop_rule(prev0, a.hscal_[kSlotMean] / nglobal + small);   // gamma_0 = r:r / N + tiny
-  double& gamma = rule.gamma_cur;
+  const double rr0 = dot(0, &Solver::cg_r_, &Solver::eps_, &Solver::eps_, 0.0, kSlotMean, 1);   // r += E - eps ; r:r
+  StopRule rule = a.stop_rule(prev0, rr0 / nglobal + small);                                     // gamma_0 = r:r / N + tiny
   for (Solver* s : m_)
     FG_HIP_CHECK(hipMemcpyAsync(s->cg_p_, s->cg_r_, 6 * (size_t)s->g_.n * sizeof(double), hipMemcpyDeviceToDevice, s->stream_));
+  double& gamma = rule.gamma_cur;
   long iter = 0;
   bool failed = false;
-  for (;;) {
+  for (;;) {   // alpha and beta on the host
     apply(&Solver::cg_p_, &Solver::cg_w_);                                       // w = -Gamma0 (C - C0) p
-    dot(1, &Solver::cg_p_, &Solver::cg_w_, &Solver::cg_w_, 0.0, kSlotMean, 1);   // p:(p - w)
-    const double alpha = gamma / (a.hscal_[kSlotMean] / nglobal + small);
+    const double pw = dot(1, &Solver::cg_p_, &Solver::cg_w_, &Solver::cg_w_, 0.0, kSlotMean, 1);   // p:(p - w)
+    const double alpha = gamma / (pw / nglobal + small);
     dot(2, &Solver::eps_, &Solver::cg_p_, &Solver::cg_p_, alpha, kSlotSumSq, 6);  // eps += alpha p ; norms
     set_sumsq(kSlotSumSq, 6);
     rule.measure(norm9_of_sums(a.sumsq_, nglobal));
     if (a.opt_.error_estimator >= 2) estimator_update(&rule.abs_err, &rule.rel_err);   // update_cg -> update  F:14465, F:14584
     if (converged(rule, iter, voting, [&] { return bc_error(E0, S0) <= a.opt_.bc_tol; }, &failed)) break;
     iter++;
-    dot(3, &Solver::cg_r_, &Solver::cg_p_, &Solver::cg_w_, -alpha, kSlotMean, 1);   // r -= alpha (p - w) ; r:r
-    const double delta = a.hscal_[kSlotMean] / nglobal + small;
+    const double rr = dot(3, &Solver::cg_r_, &Solver::cg_p_, &Solver::cg_w_, -alpha, kSlotMean, 1);   // r -= alpha (p - w) ; r:r
+    const double delta = rr / nglobal + small;
     const double beta = delta / gamma;
     gamma = delta;
     dot(4, &Solver::cg_p_, &Solver::cg_r_, &Solver::cg_r_, beta, kSlotMean, 0);      // p = r + beta p

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "fg_cg_loop.h"
 #include "fg_comm.h"
 #include "fg_fft.h"
 #include "fg_hostmath.h"
@@ -246,6 +247,17 @@ class Solver {
   // _converged on the rule's measurement with this solver's hooks (fg_stop_rule.h); true: the loop ends, *failed says how
   template <class BcOk>
   bool converged(const StopRule& rule, long iter, BcOk bc_ok, bool* failed);
+  // the CG loops (the pipelined iteration itself: fg_cg_loop.h)
+  void cg_fetch(int slot);              // D2H of the seven sums of the stop rule + error word, event for the host
+  void cg_wait();                       // waits for those copies only; throws on a device error
+  bool cg_may_run_ahead() const { return !cb_; }   // no callback looks at the state between two iterations
+  template <class Site>
+  friend CgResult cg_pipelined(Site&, const CgPipelinedOps&, StopRule&, const CgSlots&, double);
+  const double* cg_sumsq(int ncomp);    // those sums of squares as sumsq_ (zero beyond ncomp)
+  double cg_fetch_now(int slot, int n); // D2H of n sums, waited for; returns the first
+  void cg_apply(double* u_in, const double* Eadd, double* xscratch);   // fu_alt_ = operator(u_in), displacement / potential space
+  void cg_set_state(const Vec6& E);     // the iterate is (E, fu_)
+  void cg_finish(long iter, double t_start, const Vec6* E);   // E: materialise the strain from (E, fu_); nullptr: strain space
   bool run_cg(const double* E0, const double* S0, double prev0);
   bool run_cg_scalar(const double* E0, double prev0);  // heat / porous: CG in potential space
   bool run_cg_u(const double* E0, double prev0);      // the same CG carried in displacement space (Voigt, prescribed mean strains)

@@ -1664,6 +1664,62 @@ bool Solver::converged(const StopRule& rule, long iter, BcOk bc_ok, bool* failed
   return d != StopDecision::kContinue;
 }
 
+// The CG loops' fetch (fg_cg_loop.h): the seven sums of dscal_[slot ..] and the error word start for the host; what is enqueued
+// between cg_fetch and cg_wait runs while the host waits for them.
+void Solver::cg_fetch(int slot) {
+  FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotCg, dscal_ + slot, 7 * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  FG_HIP_CHECK(hipMemcpyAsync(herr_, derr_, sizeof(int), hipMemcpyDeviceToHost, stream_));
+  FG_HIP_CHECK(hipEventRecord(ev_copy_, stream_));
+}
+
+void Solver::cg_wait() {
+  FG_HIP_CHECK(hipEventSynchronize(ev_copy_));
+  if (*herr_ != 0) check_device_error("cg");
+}
+
+// one sum (or n) fetched at once; returns the first
+double Solver::cg_fetch_now(int slot, int n) {
+  FG_HIP_CHECK(hipMemcpyAsync(hscal_ + slot, dscal_ + slot, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  check_device_error("cg");
+  return hscal_[slot];
+}
+
+// the fetched sums of squares as sumsq_ (ncomp of them: 3 in the scalar modes)
+const double* Solver::cg_sumsq(int ncomp) {
+  for (int c = 0; c < 6; ++c) sumsq_[c] = c < ncomp ? hscal_[kSlotCg + c] : 0.0;
+  return sumsq_;
+}
+
+// CG in displacement / potential space: w = operator(u_in) with prescribed mean Eadd, i.e. u -> f = div((C - C0)(Eadd + grad_s u))
+// -> FFT chain (alpha = -1) -> fu_alt_
+void Solver::cg_apply(double* u_in, const double* Eadd, double* xscratch) {
+  double* keep = fu_;
+  fu_ = u_in;
+  for (int c = 0; c < 6; ++c) E_cur_[c] = Eadd[c];
+  u_pass_front(Eadd);   // sweeps fu_ (with E_cur_) into fu_alt_; its norm sums are not used here
+  fu_ = keep;
+  fft_g0_chain(fu_alt_, -1.0, nullptr, xscratch);
+}
+
+// CG in displacement / potential space: what accessors called from a callback / bc_error see is eps = E + grad_s fu_
+void Solver::cg_set_state(const Vec6& E) {
+  u_valid_ = true;
+  eps_stale_ = true;
+  for (int c = 0; c < 6; ++c) E_cur_[c] = E.v[c];
+}
+
+// end of a CG run; E: the run was carried in displacement / potential space, the strain field is materialised from (E, fu_)
+void Solver::cg_finish(long iter, double t_start, const Vec6* E) {
+  iterations_ = iter;
+  if (E) {
+    cg_u_active_ = false;
+    cg_set_state(*E);
+    ensure_eps();
+  }
+  FG_HIP_CHECK(hipStreamSynchronize(stream_));
+  solve_time_ += now_seconds() - t_start;
+}
+
 // run F:21247-21398 -> runLoadsteppingSolver (single load step, t = 1) F:21584-21685
 // -> runSolver -> runBasic F:21716-21805 with the stop rule of _converged F:21177-21244.
 bool Solver::run(const double* E6, const double* S6) {
@@ -1904,9 +1960,7 @@ bool Solver::run_one_step(const double* E0, const double* S0) {
 // F:20583-20587 = one basicScheme pass with E = 0), l2 inner product, epsilon error estimator.
 // The same iteration carried in displacement space (see k_cgu_dot): eps = E + grad_s u_e, r / p / w = grad_s u_r / u_p / u_w.
 //   u_e = fu_ (so the strain is materialised from it afterwards), u_w = fu_alt_ (output of the FFT chain),
-//   u_r, u_p = the two halves of the 6-component buffer cg_r_.
-// Per iteration: one displacement sweep (the K1 of the basic scheme with E = 0) + FFT chain, one gradient dot product,
-// one point-wise update of u_e and u_r, one gradient norm sweep, one point-wise update of u_p.
+//   u_r, u_p = the two halves of the 6-component buffer cg_r_.  The iteration itself: cg_pipelined (fg_cg_loop.h).
 bool Solver::run_cg_u(const double* E0, double prev0) {
   const double t_start = now_seconds();
   const size_t f3 = 3 * (size_t)g_.n * sizeof(double);
@@ -1942,15 +1996,7 @@ bool Solver::run_cg_u(const double* E0, double prev0) {
   if (opt_.update_ref) calc_ref_material();
   Vec6 E, Z;
   for (int i = 0; i < 6; ++i) E.v[i] = E0[i], Z.v[i] = 0.0;   // Q = 0: calcBCMean leaves E0
-  // the operator on a displacement: u -> f = div((C - C0)(Eadd + grad_s u)) -> FFT chain (alpha = -1) -> fu_alt_
-  auto apply = [&](double* u_in, const double* Eadd) {
-    double* keep = fu_;
-    fu_ = u_in;
-    for (int c = 0; c < 6; ++c) E_cur_[c] = Eadd[c];
-    u_pass_front(Eadd);   // sweeps fu_ (with E_cur_) into fu_alt_; its norm sums are not used here
-    fu_ = keep;
-    fft_g0_chain(fu_alt_, -1.0, nullptr, tau_);
-  };
+  auto apply = [&](double* u_in, const double* Eadd) { cg_apply(u_in, Eadd, tau_); };
   // fused form: u_p := u_r + beta u_p (beta from the sums at dscal_[i_num] / dscal_[i_den]) inside the sweep of the operator
   auto apply_dir = [&](int i_num, int i_den) {
     if (dfg()) {
@@ -1989,94 +2035,56 @@ bool Solver::run_cg_u(const double* E0, double prev0) {
     fft_g0_chain(fu_alt_, -1.0, nullptr, tau_);
     std::swap(u_p, p_alt);
   };
-  int beta_num = 0, beta_den = 0;   // fused form: slots of the pending direction update
   // eps_0 = E (u_e = 0);  r = -Gamma0 (C - C0) E  (+ E - eps_0 = 0, adjustResidual F:10012-10022)
-  // The CG scalars stay on the device (k_cgu_axpy forms alpha and beta from the sums the dot sweeps leave in
-  // dscal_): the host fetches only the seven sums of the stop rule, and -- when no callback can look at the state
-  // in between -- has already enqueued the next direction update and operator application when it waits for them.
-  const int blk[2] = {kSlotCg, kSlotCg + 8}, s0 = kSlotCg + 16;
+  // The CG scalars stay on the device: k_cgu_axpy forms alpha and beta from the sums the dot sweeps leave in dscal_ (cg_pipelined).
+  const CgSlots slot = cg_slots(kSlotCg);
   const double nvox = (double)nglobal_;
   FG_HIP_CHECK(hipMemsetAsync(fu_, 0, f3, stream_));
   apply(fu_, E.v);
   FG_HIP_CHECK(hipMemcpyAsync(u_r, fu_alt_, f3, hipMemcpyDeviceToDevice, stream_));
   FG_HIP_CHECK(hipMemcpyAsync(u_p, fu_alt_, f3, hipMemcpyDeviceToDevice, stream_));   // p = r
-  launch_cgu_dot(1, g_, ptrs3(fu_), ptrs3(u_r), E, partial_, dscal_ + blk[0], stream_);   // gamma_0 = r:r / N + tiny
+  launch_cgu_dot(1, g_, ptrs3(fu_), ptrs3(u_r), E, partial_, dscal_ + slot.blk[0], stream_);   // gamma_0 = r:r / N + tiny
   double gamma_0 = 0.0;   // r:r / N + tiny at the start: only the residual estimator reads it
   if (opt_.error_estimator == 1) {
-    FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotCg + 6, dscal_ + blk[0] + 6, sizeof(double), hipMemcpyDeviceToHost, stream_));
+    FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotCg + 6, dscal_ + slot.rr(0), sizeof(double), hipMemcpyDeviceToHost, stream_));
     FG_HIP_CHECK(hipStreamSynchronize(stream_));
     gamma_0 = hscal_[kSlotCg + 6] / (double)nglobal_ + small;
   }
   StopRule rule = stop_rule(prev0, gamma_0);
   const double S_zero[6] = {0, 0, 0, 0, 0, 0};
-  long iter = 0;
-  bool failed = false;
-  bool applied = false;   // u_w = operator(u_p) of the coming iteration is already enqueued
-  for (;;) {
-    const int cur = (int)(iter & 1), nxt = cur ^ 1;
-    if (!applied) {
-      if (fused_dir && iter > 0) apply_dir(beta_num, beta_den);                        // p = r + beta p ; u_w = operator(u_p)
-      else apply(u_p, Z.v);                                                           // u_w = operator(u_p)
-    }
-    applied = false;
-    if (fused) {
+  CgPipelinedOps ops;
+  ops.fused_dir = fused_dir;
+  ops.apply_p = [&] { apply(u_p, Z.v); };   // u_w = operator(u_p)
+  ops.apply_dir = apply_dir;
+  ops.direction = [&](int num, int den) {   // p = r + beta p (beta = delta / gamma)
+    launch_cgu_axpy(1, g_, ptrs3(fu_), ptrs3(u_p), ptrs3(u_r), ptrs3(fu_alt_), dscal_, num, den, nvox, small, stream_);
+  };
+  ops.dot_pw = [&](int out) {   // p : (p - w)
+    if (fused)
       launch_cgu_tile(0, g_, ptrs3(u_p), ptrs3(fu_alt_), ptrs3(u_p), ptrs3(fu_alt_), ptrs3(fu_cg_), ptrs3(r_alt), Z, dscal_, 0, 0, nvox,
-                      small, partial_, dscal_ + s0, stream_);                                         // p : (p - w)
-      // eps += alpha p ; r -= alpha (p - w) into the alternate buffers, with the norms of the new eps and r : r
-      launch_cgu_tile(1, g_, ptrs3(fu_), ptrs3(u_r), ptrs3(u_p), ptrs3(fu_alt_), ptrs3(fu_cg_), ptrs3(r_alt), E, dscal_, blk[cur] + 6, s0,
-                      nvox, small, partial_, dscal_ + blk[nxt], stream_);
+                      small, partial_, dscal_ + out, stream_);
+    else
+      launch_cgu_dot(0, g_, ptrs3(u_p), ptrs3(fu_alt_), Z, partial_, dscal_ + out, stream_);
+  };
+  ops.update = [&](int gamma, int pw, int out) {   // eps += alpha p ; r -= alpha (p - w), with the norms of the new eps and r : r
+    if (fused) {   // into the alternate buffers
+      launch_cgu_tile(1, g_, ptrs3(fu_), ptrs3(u_r), ptrs3(u_p), ptrs3(fu_alt_), ptrs3(fu_cg_), ptrs3(r_alt), E, dscal_, gamma, pw, nvox,
+                      small, partial_, dscal_ + out, stream_);
       std::swap(fu_, fu_cg_);
       std::swap(u_r, r_alt);
     } else {
-    launch_cgu_dot(0, g_, ptrs3(u_p), ptrs3(fu_alt_), Z, partial_, dscal_ + s0, stream_);   // p : (p - w)
-    // eps += alpha p ; r -= alpha (p - w),  alpha = gamma / (p:(p - w) / N + tiny)
-    launch_cgu_axpy(0, g_, ptrs3(fu_), ptrs3(u_p), ptrs3(u_r), ptrs3(fu_alt_), dscal_, blk[cur] + 6, s0, nvox, small, stream_);
-    launch_cgu_dot(1, g_, ptrs3(fu_), ptrs3(u_r), E, partial_, dscal_ + blk[nxt], stream_);   // norms of eps ; r : r
+      launch_cgu_axpy(0, g_, ptrs3(fu_), ptrs3(u_p), ptrs3(u_r), ptrs3(fu_alt_), dscal_, gamma, pw, nvox, small, stream_);
+      launch_cgu_dot(1, g_, ptrs3(fu_), ptrs3(u_r), E, partial_, dscal_ + out, stream_);
     }
-    FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotCg, dscal_ + blk[nxt], 7 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    FG_HIP_CHECK(hipMemcpyAsync(herr_, derr_, sizeof(int), hipMemcpyDeviceToHost, stream_));
-    FG_HIP_CHECK(hipEventRecord(ev_copy_, stream_));
-    if (!cb_ && iter < opt_.maxiter) {
-      // p = r + beta p (beta = delta / gamma) and the next operator application, enqueued behind the copies
-      if (fused_dir) {
-        apply_dir(blk[nxt] + 6, blk[cur] + 6);
-      } else {
-        launch_cgu_axpy(1, g_, ptrs3(fu_), ptrs3(u_p), ptrs3(u_r), ptrs3(fu_alt_), dscal_, blk[nxt] + 6, blk[cur] + 6, nvox, small,
-                        stream_);
-        apply(u_p, Z.v);
-      }
-      applied = true;
-    }
-    FG_HIP_CHECK(hipEventSynchronize(ev_copy_));
-    if (*herr_ != 0) check_device_error("cg");
-    // state for accessors called from the callback / bc_error: eps = E + grad_s fu_
-    u_valid_ = true;
-    eps_stale_ = true;
-    for (int c = 0; c < 6; ++c) E_cur_[c] = E.v[c];
-    for (int c = 0; c < 6; ++c) sumsq_[c] = hscal_[kSlotCg + c];
-    // delta = r:r after the update is the next gamma
-    rule.measure(norm9_of_sums(sumsq_, (double)nglobal_), hscal_[kSlotCg + 6] / (double)nglobal_ + small);
-    if (converged(rule, iter, [&] { return bc_error(E0, S_zero) <= opt_.bc_tol; }, &failed)) break;
-    iter++;
-    if (!applied) {   // p = r + beta p
-      if (fused_dir) {
-        beta_num = blk[nxt] + 6;   // formed inside the next operator application
-        beta_den = blk[cur] + 6;
-      } else {
-        launch_cgu_axpy(1, g_, ptrs3(fu_), ptrs3(u_p), ptrs3(u_r), ptrs3(fu_alt_), dscal_, blk[nxt] + 6, blk[cur] + 6, nvox, small,
-                        stream_);
-      }
-    }
-  }
-  cg_u_active_ = false;
-  iterations_ = iter;
-  u_valid_ = true;
-  eps_stale_ = true;
-  for (int c = 0; c < 6; ++c) E_cur_[c] = E.v[c];
-  ensure_eps();
-  FG_HIP_CHECK(hipStreamSynchronize(stream_));
-  solve_time_ += now_seconds() - t_start;
-  return failed;
+  };
+  ops.sums = [&] {
+    cg_set_state(E);   // eps = E + grad_s fu_
+    return CgSums{norm9_of_sums(cg_sumsq(6), nvox), hscal_[kSlotCg + 6]};
+  };
+  ops.bc_ok = [&] { return bc_error(E0, S_zero) <= opt_.bc_tol; };
+  const CgResult end = cg_pipelined(*this, ops, rule, slot, nvox);
+  cg_finish(end.iter, t_start, &E);
+  return end.failed;
 }
 
 // Scalar modes: the same CG in potential space (g = E + grad T_e; r, p, w = grad T_r, T_p, T_w): runCG dispatches every
@@ -2095,125 +2103,88 @@ bool Solver::run_cg_scalar(const double* E0, double prev0) {
   Vec6 E, Z;
   for (int i = 0; i < 6; ++i) E.v[i] = i < 3 ? E0[i] : 0.0, Z.v[i] = 0.0;
   const double S_zero[6] = {0, 0, 0, 0, 0, 0};
-  auto set_state = [&] {   // for accessors called from the callback / bc_error: g = E + grad T_e, T_e = fu_'s first component
-    u_valid_ = true;
-    eps_stale_ = true;
-    for (int c = 0; c < 6; ++c) E_cur_[c] = E.v[c];
-  };
-  auto finish = [&](long iter) {
-    in_run_ = false;
-    cg_u_active_ = false;
-    iterations_ = iter;
-    set_state();
-    ensure_eps();
-    FG_HIP_CHECK(hipStreamSynchronize(stream_));
-    solve_time_ += now_seconds() - t_start;
-  };
-  auto fetch = [&](int slot, int n) {
-    FG_HIP_CHECK(hipMemcpyAsync(hscal_ + slot, dscal_ + slot, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    check_device_error("cg");
-  };
-  auto apply = [&](double* T_in, const double* Eadd) {   // T -> f = div((C - C0)(Eadd + grad T)) -> FFT chain -> fu_alt_
-    double* keep = fu_;
-    fu_ = T_in;
-    for (int c = 0; c < 6; ++c) E_cur_[c] = Eadd[c];
-    u_pass_front(Eadd);
-    fu_ = keep;
-    fft_g0_chain(fu_alt_);
-  };
+  auto apply = [&](double* T_in, const double* Eadd) { cg_apply(T_in, Eadd, nullptr); };
   FG_HIP_CHECK(hipMemsetAsync(fu_, 0, f1, stream_));
   apply(fu_, E.v);
   FG_HIP_CHECK(hipMemcpyAsync(T_r, fu_alt_, f1, hipMemcpyDeviceToDevice, stream_));
   FG_HIP_CHECK(hipMemcpyAsync(T_p, fu_alt_, f1, hipMemcpyDeviceToDevice, stream_));
-  // Fused form (option cg_fused; as in run_cg_u): p.(p - w) and the update of T_e, T_r with their norms as two tiled sweeps,
-  // the direction update inside the operator's sweep, the CG scalars on the device, the next operator application enqueued
-  // before the host waits for the sums.  Out of place: T_e, T_r, T_p alternate between two components each (the spare
-  // components of fu_ and cg_r_).  Not with a convergence callback (accessors read fu_'s first component in between).
+  // Fused form (option cg_fused; as in run_cg_u, cg_pipelined with the direction inside the operator's sweep).  Out of place:
+  // T_e, T_r, T_p alternate between two components each (the spare components of fu_ and cg_r_).  Not with a convergence
+  // callback (accessors read fu_'s first component in between).
   const int fused_opt = opt_.cg_fused;
+  const double nvox = (double)nglobal_;
   if (fused_opt != 0 && !cb_ && opt_.u_loop >= 2 && sc_sweep_tiled(g_) && !slab_layout_) {
-    const int blk[2] = {kSlotCg, kSlotCg + 8}, s0 = kSlotCg + 16;
-    const double nvox = (double)nglobal_;
+    const CgSlots slot = cg_slots(kSlotCg);
     double *e_cur = fu_, *e_alt = fu_ + g_.n, *r_cur = T_r, *r_alt = cg_r_ + 2 * g_.n, *p_cur = T_p, *p_alt = cg_r_ + 3 * g_.n;
     const double* cond = effective_moduli().p[0];
-    auto apply_dir = [&](int i_num, int i_den) {   // T_p := T_r + beta T_p inside the sweep; T_w = operator(T_p)
+    launch_sc_cg_dot(1, g_, e_cur, r_cur, E, partial_, dscal_ + slot.blk[0], stream_);   // gamma_0 = r.r / N + tiny
+    FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotCg + 6, dscal_ + slot.rr(0), sizeof(double), hipMemcpyDeviceToHost, stream_));
+    FG_HIP_CHECK(hipStreamSynchronize(stream_));
+    check_device_error("cg");
+    StopRule rule = stop_rule(prev0, hscal_[kSlotCg + 6] / nvox + small);
+    CgPipelinedOps ops;
+    ops.fused_dir = true;
+    ops.apply_p = [&] { apply(p_cur, Z.v); };
+    ops.apply_dir = [&](int num, int den) {   // T_p := T_r + beta T_p inside the sweep; T_w = operator(T_p)
       time_begin(0);
-      launch_sc_sweep_cg(g_, opt_.mu_0, p_cur, r_cur, p_alt, cond, fu_alt_, Z, dscal_, i_num, i_den, nvox, small, partial_,
+      launch_sc_sweep_cg(g_, opt_.mu_0, p_cur, r_cur, p_alt, cond, fu_alt_, Z, dscal_, num, den, nvox, small, partial_,
                          dscal_ + kSlotSumSq, stream_);
       time_end(0);
       fft_g0_chain(fu_alt_);
       std::swap(p_cur, p_alt);
     };
-    launch_sc_cg_dot(1, g_, e_cur, r_cur, E, partial_, dscal_ + blk[0], stream_);   // gamma_0 = r.r / N + tiny
-    FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotCg + 6, dscal_ + blk[0] + 6, sizeof(double), hipMemcpyDeviceToHost, stream_));
-    FG_HIP_CHECK(hipStreamSynchronize(stream_));
-    check_device_error("cg");
-    StopRule rule = stop_rule(prev0, hscal_[kSlotCg + 6] / nvox + small);
-    long iter = 0;
-    bool failed = false, applied = false;
-    for (;;) {
-      const int cur = (int)(iter & 1), nxt = cur ^ 1;
-      if (!applied) apply(p_cur, Z.v);   // the first iteration: p = r (every later application is enqueued ahead, see below)
-      applied = false;
-      launch_sc_cgu_tile(0, g_, p_cur, fu_alt_, p_cur, fu_alt_, e_alt, r_alt, Z, dscal_, 0, 0, nvox, small, partial_, dscal_ + s0, stream_);
-      launch_sc_cgu_tile(1, g_, e_cur, r_cur, p_cur, fu_alt_, e_alt, r_alt, E, dscal_, blk[cur] + 6, s0, nvox, small, partial_,
-                         dscal_ + blk[nxt], stream_);
+    ops.dot_pw = [&](int out) {
+      launch_sc_cgu_tile(0, g_, p_cur, fu_alt_, p_cur, fu_alt_, e_alt, r_alt, Z, dscal_, 0, 0, nvox, small, partial_, dscal_ + out,
+                         stream_);
+    };
+    ops.update = [&](int gamma, int pw, int out) {
+      launch_sc_cgu_tile(1, g_, e_cur, r_cur, p_cur, fu_alt_, e_alt, r_alt, E, dscal_, gamma, pw, nvox, small, partial_, dscal_ + out,
+                         stream_);
       std::swap(e_cur, e_alt);
       std::swap(r_cur, r_alt);
-      FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotCg, dscal_ + blk[nxt], 7 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-      FG_HIP_CHECK(hipMemcpyAsync(herr_, derr_, sizeof(int), hipMemcpyDeviceToHost, stream_));
-      FG_HIP_CHECK(hipEventRecord(ev_copy_, stream_));
-      if (iter < opt_.maxiter) {   // the next direction and operator application, enqueued behind the copies
-        apply_dir(blk[nxt] + 6, blk[cur] + 6);
-        applied = true;
+    };
+    ops.sums = [&] { return CgSums{norm3_of_sums(cg_sumsq(3), nvox), hscal_[kSlotCg + 6]}; };
+    ops.bc_ok = [&] {
+      // bc_error reads the strain of the current iterate: fu_'s first component must be it
+      if (e_cur != fu_) {
+        FG_HIP_CHECK(hipMemcpyAsync(fu_, e_cur, f1, hipMemcpyDeviceToDevice, stream_));
+        std::swap(e_cur, e_alt);
       }
-      FG_HIP_CHECK(hipEventSynchronize(ev_copy_));
-      if (*herr_ != 0) check_device_error("cg");
-      for (int c = 0; c < 6; ++c) sumsq_[c] = c < 3 ? hscal_[kSlotCg + c] : 0.0;
-      // delta = r.r after the update is the next gamma
-      rule.measure(norm3_of_sums(sumsq_, nvox), hscal_[kSlotCg + 6] / nvox + small);
-      auto bc_ok = [&] {
-        // bc_error reads the strain of the current iterate: fu_'s first component must be it
-        if (e_cur != fu_) {
-          FG_HIP_CHECK(hipMemcpyAsync(fu_, e_cur, f1, hipMemcpyDeviceToDevice, stream_));
-          std::swap(e_cur, e_alt);
-        }
-        set_state();
-        return bc_error(E.v, S_zero) <= opt_.bc_tol;
-      };
-      if (converged(rule, iter, bc_ok, &failed)) break;
-      iter++;
-    }
+      cg_set_state(E);
+      return bc_error(E.v, S_zero) <= opt_.bc_tol;
+    };
+    const CgResult end = cg_pipelined(*this, ops, rule, slot, nvox);   // (cb_ is not set in this form: every iteration runs ahead)
     if (e_cur != fu_) FG_HIP_CHECK(hipMemcpyAsync(fu_, e_cur, f1, hipMemcpyDeviceToDevice, stream_));
-    finish(iter);
-    return failed;
+    in_run_ = false;
+    cg_finish(end.iter, t_start, &E);
+    return end.failed;
   }
   launch_sc_cg_dot(1, g_, fu_, T_r, E, partial_, dscal_ + kSlotSumSq, stream_);
-  fetch(kSlotSumSq, 7);
-  StopRule rule = stop_rule(prev0, hscal_[kSlotSumSq + 6] / (double)nglobal_ + small);
+  cg_fetch_now(kSlotSumSq, 7);
+  StopRule rule = stop_rule(prev0, hscal_[kSlotSumSq + 6] / nvox + small);
   double& gamma = rule.gamma_cur;
   long iter = 0;
   bool failed = false;
-  for (;;) {
+  for (;;) {   // alpha and beta on the host
     apply(T_p, Z.v);
     launch_sc_cg_dot(0, g_, T_p, fu_alt_, Z, partial_, dscal_ + kSlotMean, stream_);
-    fetch(kSlotMean, 1);
-    double alpha = hscal_[kSlotMean] / (double)nglobal_ + small;
-    alpha = gamma / alpha;
+    const double alpha = gamma / (cg_fetch_now(kSlotMean, 1) / nvox + small);
     launch_sc_cg_axpy(0, g_, fu_, T_p, T_r, fu_alt_, alpha, stream_);
     launch_sc_cg_dot(1, g_, fu_, T_r, E, partial_, dscal_ + kSlotSumSq, stream_);
-    fetch(kSlotSumSq, 7);
+    cg_fetch_now(kSlotSumSq, 7);
     const double rr = hscal_[kSlotSumSq + 6];
-    set_state();
+    cg_set_state(E);
     for (int c = 0; c < 6; ++c) sumsq_[c] = c < 3 ? hscal_[kSlotSumSq + c] : 0.0;
-    rule.measure(norm3_of_sums(sumsq_, (double)nglobal_));
+    rule.measure(norm3_of_sums(sumsq_, nvox));
     if (converged(rule, iter, [&] { return bc_error(E.v, S_zero) <= opt_.bc_tol; }, &failed)) break;
     iter++;
-    const double delta = rr / (double)nglobal_ + small;
+    const double delta = rr / nvox + small;
     const double beta = delta / gamma;
     gamma = delta;
     launch_sc_cg_axpy(1, g_, fu_, T_p, T_r, fu_alt_, beta, stream_);
   }
-  finish(iter);
+  in_run_ = false;
+  cg_finish(iter, t_start, &E);
   return failed;
 }
 
@@ -2234,84 +2205,57 @@ bool Solver::run_cg(const double* E0, const double* S0, double prev0) {
   Vec6 E, Z;
   bc_mean(BC_QC0_, BC_M_, opt_.bc_relax, E0, S0, E.v);
   for (int i = 0; i < 6; ++i) Z.v[i] = 0.0;
-  auto bc_ok = [&] { return bc_error(E0, S0) <= opt_.bc_tol; };
-  auto finish = [&](long iter) {
-    in_run_ = false;
-    iterations_ = iter;
-    FG_HIP_CHECK(hipStreamSynchronize(stream_));
-    solve_time_ += now_seconds() - t_start;
-  };
-  auto fetch = [&](int slot, int n) {
-    FG_HIP_CHECK(hipMemcpyAsync(hscal_ + slot, dscal_ + slot, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    check_device_error("cg");
-  };
   const FieldPtrs<6> e = ptrs6(eps_), r = ptrs6(cg_r_), p = ptrs6(cg_p_), w = ptrs6(cg_w_);
   launch_set_const6(g_, e, E, stream_);
   basic_scheme(Z.v, eps_, cg_r_);                                                  // r = -Gamma0 (C - C0) eps
   launch_cg(0, g_, r, e, e, E, 0.0, partial_, dscal_ + kSlotMean, stream_);        // r += E - eps ; r:r
-  fetch(kSlotMean, 1);
-  StopRule rule = stop_rule(prev0, hscal_[kSlotMean] / (double)nglobal_ + small);   // gamma_0 = r:r / N + tiny
-  double& gamma = rule.gamma_cur;
+  StopRule rule = stop_rule(prev0, cg_fetch_now(kSlotMean, 1) / (double)nglobal_ + small);   // gamma_0 = r:r / N + tiny
   FG_HIP_CHECK(hipMemcpyAsync(cg_p_, cg_r_, f6, hipMemcpyDeviceToDevice, stream_));  // p = r
-  // Round 4 (option cg_fused): the CG scalars on the device, the updates of eps and r as ONE sweep with their norms, the next
-  // direction and operator application enqueued before the host waits for the seven sums of the stop rule -- one host
-  // synchronisation per iteration instead of three, 528 instead of 576 bytes per voxel of vector work.
+  // option cg_fused (cg_pipelined): the updates of eps and r as ONE sweep with their norms -- one host synchronisation per
+  // iteration instead of three, 528 instead of 576 bytes per voxel of vector work; otherwise cg_host_scalars
+  const double nvox = (double)nglobal_;
+  auto bc_ok = [&] { return bc_error(E0, S0) <= opt_.bc_tol; };
   if (opt_.cg_fused != 0) {
-    const int blk[2] = {kSlotCg, kSlotCg + 8}, s0 = kSlotCg + 16;
-    const double nvox = (double)nglobal_;
-    FG_HIP_CHECK(hipMemcpyAsync(dscal_ + blk[0] + 6, dscal_ + kSlotMean, sizeof(double), hipMemcpyDeviceToDevice, stream_));   // gamma_0
-    long iter = 0;
-    bool failed = false, applied = false;
-    for (;;) {
-      const int cur = (int)(iter & 1), nxt = cur ^ 1;
-      if (!applied) basic_scheme(Z.v, cg_p_, cg_w_);                                 // w = -Gamma0 (C - C0) p
-      applied = false;
-      launch_cg(1, g_, p, w, w, E, 0.0, partial_, dscal_ + s0, stream_);             // p:(p - w)
-      // eps += alpha p ; r -= alpha (p - w) ; norms of eps ; r:r
-      launch_cg_dev(5, g_, e, r, p, w, dscal_, blk[cur] + 6, s0, nvox, small, partial_, dscal_ + blk[nxt], stream_);
-      FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotCg, dscal_ + blk[nxt], 7 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-      FG_HIP_CHECK(hipMemcpyAsync(herr_, derr_, sizeof(int), hipMemcpyDeviceToHost, stream_));
-      FG_HIP_CHECK(hipEventRecord(ev_copy_, stream_));
-      if (!cb_ && iter < opt_.maxiter) {   // p = r + beta p and the next operator application, enqueued behind the copies
-        launch_cg_dev(6, g_, e, r, p, w, dscal_, blk[nxt] + 6, blk[cur] + 6, nvox, small, partial_, nullptr, stream_);
-        basic_scheme(Z.v, cg_p_, cg_w_);
-        applied = true;
-      }
-      FG_HIP_CHECK(hipEventSynchronize(ev_copy_));
-      if (*herr_ != 0) check_device_error("cg");
-      for (int c = 0; c < 6; ++c) sumsq_[c] = hscal_[kSlotCg + c];
-      rule.measure(norm9_of_sums(sumsq_, nvox), hscal_[kSlotCg + 6] / nvox + small);   // r:r after the update: the next gamma
-      if (opt_.error_estimator >= 2) estimator_update(&rule.abs_err, &rule.rel_err);   // update_cg -> update  F:14465, F:14584
-      if (converged(rule, iter, bc_ok, &failed)) break;
-      iter++;
-      if (!applied) launch_cg_dev(6, g_, e, r, p, w, dscal_, blk[nxt] + 6, blk[cur] + 6, nvox, small, partial_, nullptr, stream_);
-    }
-    finish(iter);
-    return failed;
+    const CgSlots slot = cg_slots(kSlotCg);
+    FG_HIP_CHECK(hipMemcpyAsync(dscal_ + slot.rr(0), dscal_ + kSlotMean, sizeof(double), hipMemcpyDeviceToDevice, stream_));   // gamma_0
+    CgPipelinedOps ops;
+    ops.apply_p = [&] { basic_scheme(Z.v, cg_p_, cg_w_); };   // w = -Gamma0 (C - C0) p
+    ops.direction = [&](int num, int den) { launch_cg_dev(6, g_, e, r, p, w, dscal_, num, den, nvox, small, partial_, nullptr, stream_); };
+    ops.dot_pw = [&](int out) { launch_cg(1, g_, p, w, w, E, 0.0, partial_, dscal_ + out, stream_); };   // p:(p - w)
+    ops.update = [&](int gamma_slot, int pw, int out) {   // eps += alpha p ; r -= alpha (p - w) ; norms of eps ; r:r
+      launch_cg_dev(5, g_, e, r, p, w, dscal_, gamma_slot, pw, nvox, small, partial_, dscal_ + out, stream_);
+    };
+    ops.sums = [&] { return CgSums{norm9_of_sums(cg_sumsq(6), nvox), hscal_[kSlotCg + 6]}; };
+    if (opt_.error_estimator >= 2)   // update_cg -> update  F:14465, F:14584
+      ops.estimator = [&](StopRule& r) { estimator_update(&r.abs_err, &r.rel_err); };
+    ops.bc_ok = bc_ok;
+    const CgResult end = cg_pipelined(*this, ops, rule, slot, nvox);
+    in_run_ = false;
+    cg_finish(end.iter, t_start, nullptr);
+    return end.failed;
   }
+  double& gamma = rule.gamma_cur;
   long iter = 0;
   bool failed = false;
-  for (;;) {
+  for (;;) {   // alpha and beta on the host
     basic_scheme(Z.v, cg_p_, cg_w_);                                               // w = -Gamma0 (C - C0) p
     launch_cg(1, g_, p, w, w, E, 0.0, partial_, dscal_ + kSlotMean, stream_);      // p:(p - w)
-    fetch(kSlotMean, 1);
-    double alpha = hscal_[kSlotMean] / (double)nglobal_ + small;
-    alpha = gamma / alpha;
+    const double alpha = gamma / (cg_fetch_now(kSlotMean, 1) / nvox + small);
     launch_cg(2, g_, e, p, p, E, alpha, partial_, dscal_ + kSlotSumSq, stream_);   // eps += alpha p ; norms
-    fetch(kSlotSumSq, 6);
+    cg_fetch_now(kSlotSumSq, 6);
     for (int c = 0; c < 6; ++c) sumsq_[c] = hscal_[kSlotSumSq + c];
-    rule.measure(norm9_of_sums(sumsq_, (double)nglobal_));
+    rule.measure(norm9_of_sums(sumsq_, nvox));
     if (opt_.error_estimator >= 2) estimator_update(&rule.abs_err, &rule.rel_err);   // update_cg -> update  F:14465, F:14584
     if (converged(rule, iter, bc_ok, &failed)) break;
     iter++;
     launch_cg(3, g_, r, p, w, E, -alpha, partial_, dscal_ + kSlotMean, stream_);   // r -= alpha (p - w) ; r:r
-    fetch(kSlotMean, 1);
-    const double delta = hscal_[kSlotMean] / (double)nglobal_ + small;
+    const double delta = cg_fetch_now(kSlotMean, 1) / nvox + small;
     const double beta = delta / gamma;
     gamma = delta;
     launch_cg(4, g_, p, r, r, E, beta, partial_, dscal_ + kSlotMean, stream_);     // p = r + beta p
   }
-  finish(iter);
+  in_run_ = false;
+  cg_finish(iter, t_start, nullptr);
   return failed;
 }
 

@@ -57,6 +57,33 @@ def test_fused_cg_with_callback_and_maxiter():
     assert rel_err(out[1][3], out[0][3]) < 1e-11
 
 
+@pytest.mark.parametrize("kw,with_cb", [(dict(tol=1e-8), False), (dict(tol=1e-12, maxiter=7), True)])
+def test_strain_space_cg_host_scalars_equals_device_scalars(kw, with_cb):
+    """The sigma estimator re-measures a mean of the strain field, so CG runs in strain space (Solver::run_cg): cg_fused=0 keeps
+    alpha and beta on the host, the default forms them on the device and enqueues ahead -- unless a convergence callback reads
+    the iterate in between.  Both against the oracle; maxiter ends both on the same iterate."""
+    grid = (8, 16, 128)
+    o = make_oracle(grid, (1.0, 2.0, 1.5), "voigt", error_estimator="sigma", **kw)
+    assert o.run_cg(E_LOAD) is False
+    res = []
+    for fused in (0, 1):
+        s = make_gpu_solver(grid, (1.0, 2.0, 1.5), "voigt", method="cg", error_estimator="sigma", cg_fused=fused, **kw)
+        seen = []
+        if with_cb:
+            s.set_convergence_callback(lambda: seen.append(s.mean_stress().copy()) and False)
+        assert s.run(E_LOAD) is False
+        assert s.iterations == o.iterations and (not with_cb or (s.iterations == 7 and len(seen) == 8))
+        assert np.abs(np.array(s.residuals) - np.array(o.residuals)).max() < 1e-10
+        assert rel_err(s.get_field("epsilon"), o.eps) < 1e-8
+        assert rel_err(s.mean_stress(), o.mean_stress()) < 1e-9
+        res.append((np.array(s.residuals), s.get_field("epsilon"), np.array(seen)))
+        s.close()
+    assert res[0][0].shape == res[1][0].shape and np.abs(res[0][0] - res[1][0]).max() < 1e-12
+    assert rel_err(res[1][1], res[0][1]) < 1e-10
+    if with_cb:
+        assert np.abs(res[0][2] - res[1][2]).max() < 1e-11
+
+
 @pytest.mark.parametrize("grid,dims,estimator", [((8, 14, 128), (1, 1, 1), "epsilon"), ((6, 16, 256), (2.0, 1.0, 0.5), "epsilon"),
                                                  ((10, 18, 124), (1, 1, 1), "residual"), ((9, 16, 100), (1, 1, 1), "epsilon")])
 def test_fused_scalar_cg_matches_oracle_and_unfused(grid, dims, estimator):
