@@ -49,6 +49,7 @@ SIGNATURES = {
     "fg_set_num_phases": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "fg_set_phase": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, c_double_p]),
     "fg_set_phase_stiffness": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p]),   # LinearGeneralMaterialLaw F:11233
+    "fg_set_phase_conductivity": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p]),   # MatrixLinearAnisotropicMaterialLaw F:11089
     "fg_set_phase_field_fine": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p]),
     "fg_set_normals": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
     "fg_set_option_d": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_double]),

@@ -205,6 +205,10 @@ int fg_set_phase_stiffness(fg_solver* s, int p, const double* C) {
   return guarded(s, [&](fg::Solver& v) { v.set_phase_stiffness(p, C); });
 }
 
+int fg_set_phase_conductivity(fg_solver* s, int p, const double* c6) {
+  return guarded(s, [&](fg::Solver& v) { v.set_phase_conductivity(p, c6); });
+}
+
 int fg_set_phase_field_fine(fg_solver* s, int p, const double* phi) {
   return guarded(s, [&](fg::Solver& v) {
     if (!phi) throw std::runtime_error("phi pointer is NULL");
@@ -271,6 +275,7 @@ int fg_set_option_i(fg_solver* s, const char* key, long value) {
     else if (k == "fuse_x") o.fuse_x = value != 0;
     else if (k == "phi_sweep") o.phi_sweep = value != 0;
     else if (k == "aniso_tile") o.aniso_tile = value != 0;
+    else if (k == "aniso_sc_tile") o.aniso_sc_tile = value != 0;
     else if (k == "laminate_overlap") o.laminate_overlap = value != 0;
     else if (k == "slab_loopback") o.slab_loopback = value != 0;
     else if (k == "slab_split") o.slab_split = value < 0 ? -1 : (value != 0);

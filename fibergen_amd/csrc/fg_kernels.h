@@ -49,12 +49,25 @@ struct G0Layout {
   int nyl, jj0;
 };
 
-// Scalar modes (heat / porous): conductivities of the phases, calcStress factors (beta = -alpha 2 mu0)
+// Scalar modes (heat / porous): conductivities of the phases, calcStress factors (beta = -alpha 2 mu0).
+// law[p] = kScLawIso: the constant mu[p] (ScalarLinearIsotropicMaterialLaw  F:11158-11215).  law[p] = kScLawAniso: the constant
+// symmetric 3 x 3 matrix K[p] in the order 11, 22, 33, 23, 13, 12 (MatrixLinearAnisotropicMaterialLaw  F:11087-11156); such a
+// phase carries mu = NaN, so a path that still reads mu poisons its result.
+enum ScalarLaw { kScLawIso = 0, kScLawAniso = 1 };
+
 struct ScalarParams {
   int n;
   double mu[kMaxPhases];
   double alpha, beta;
+  int law[kMaxPhases];
+  double K[kMaxPhases][6];
 };
+
+inline bool any_aniso_phase(const ScalarParams& sp) {
+  bool a = false;
+  for (int p = 0; p < kMaxPhases; ++p) a = a || (p < sp.n && sp.law[p] != kScLawIso);
+  return a;
+}
 
 constexpr int kMaxReduceBlocks = 4096;  // partial-sum rows of the two-stage reductions
 
@@ -219,6 +232,12 @@ void launch_sc_sweep(const Grid& g, const ScalarParams& sp, const double* T, con
 // fast variant: a = per-voxel effective conductivity (launch_effective_moduli with 2 mu_p := mu_p, first array)
 // sumtau3 != nullptr: also the three sums of the flux polarisation (mixed boundary conditions); returns whether they were
 // produced (the LDS-tiled form does, the untiled one does not)
+// k_sc_tile_aniso: two complementary phases, at least one of law aniso (K0, K1: six constants each, an isotropic phase as mu on
+// the diagonal); reads phi_1.  cg_r != nullptr: the direction update T := r + b T of launch_sc_sweep_cg inside the sweep.
+void launch_sc_tile_aniso(const Grid& g, double mu_0, const double* K0, const double* K1, const double* T, const double* phi1,
+                          double* f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s, const double* cg_r = nullptr,
+                          double* cg_p_new = nullptr, const double* sc = nullptr, int i_num = 0, int i_den = 0, double nvox = 1.0,
+                          double small = 0.0);
 bool sc_sweep_tiled(const Grid& g);   // launch_sc_sweep_fast takes the tiled kernel (the one that can carry the sums of tau)
 bool launch_sc_sweep_fast(const Grid& g, double mu_0, const double* T, const double* a, double* f, const Vec6& E,
                           double* partial, double* sumsq6, hipStream_t s, double* sumtau3 = nullptr);

@@ -1481,6 +1481,240 @@ void launch_sc_tile_t(const Grid& g, double mu_0, const double* T, const double*
   FG_HIP_CHECK(hipGetLastError());
 }
 
+// k_sc_tile for two complementary phases of which at least one has law aniso (MatrixLinearAnisotropicMaterialLaw  F:11087-11156):
+// the sweep reads phi_1 instead of the effective conductivity (the same bytes per voxel) and forms
+//   K(v) = K_0 + phi_1(v) (K_1 - K_0) - 2 mu0 I = d0 + phi_1(v) d1      (six constants each: 11 22 33 23 13 12).
+// calcStress F:18134-18184 evaluates the law per voxel index, so the flux q(v) = K(v) g(v) takes the whole gradient at v and
+// div- q at v needs q_x(v - x), q_y(v - y), q_z(v - z): every thread, halo rows and lanes included, forms the full gradient
+// and the full flux at its own two voxels (T_yf from the image, T_zf from the next lane).  q_x(v - x) is carried in registers,
+// q_z(v - z) comes from the previous lane (DPP; across the waves of a whole row through Zb), q_y(v - y) of row r - 1 through the
+// image Qb that carried the conductivity: it is written after the plane's barrier, so it is read behind the NEXT plane's
+// barrier -- f of plane q - 1 is completed and stored at step q, one more step drains the last plane.  One barrier per plane,
+// two images, every T and phi value loaded once per tile.  The last row and (ZS = 0) the last lane have no forward neighbour:
+// their flux is never read.  The plane x0 - 1 takes one warm-up exchange for q_x entering plane x0.
+struct ScAnisoLin {
+  double d0[6], d1[6];
+};
+
+template <int TYR, int ZS, bool CGP = false>
+__global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_sc_tile_aniso(Grid g, ScAnisoLin K, const double* T, const double* phi1,
+                                                                             double* fo, Vec6 E, double* partial, int nty, int ntz,
+                                                                             int LX, int nt, ScCgDirection cg) {
+  constexpr bool FULLROW = ZS > 0;
+  constexpr int NZS = ZS ? ZS : 1;
+  constexpr int TYU = TYR - 2;
+  constexpr int TZU = FULLROW ? 64 * NZS : 62;
+  constexpr int RW = NZS * 64;
+  __shared__ double2 Tb[2][TYR][RW];
+  __shared__ double2 Qb[2][TYR][RW];    // q_y of the plane
+  __shared__ double Zb[2][TYR][NZS];    // q_z of the last voxel of every wave (whole rows: the z neighbour across waves)
+  constexpr int NA = 3;
+  __shared__ double red[TYR * NZS * NA];
+
+  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
+  const int r = wv / NZS, zs = wv % NZS;
+  const int li = zs * 64 + l;
+  const int zprev = (zs + NZS - 1) % NZS, znext = (zs + 1) % NZS;
+  const int nzh = g.nz / 2;
+  int b = blockIdx.x;
+  {
+    const int nb = gridDim.x;
+    if (nb % 8 == 0) b = (b % 8) * (nb / 8) + b / 8;   // one XCD takes a contiguous run of tiles
+  }
+  const int tz = b % ntz;
+  b /= ntz;
+  const int ty = b % nty;
+  const int tx = b / nty;
+  const bool surplus = tx * LX >= g.nx;
+  const int j0 = min(ty * TYU, g.ny - TYU), kp0 = min(tz * TZU, nzh - TZU), x0 = surplus ? 0 : tx * LX;
+  const int jr = j0 - 1 + r;
+  const int j = jr < 0 ? jr + g.ny : (jr >= g.ny ? jr - g.ny : jr);
+  const int kr = FULLROW ? li : kp0 - 1 + l;
+  const int kp = kr < 0 ? kr + nzh : (kr >= nzh ? kr - nzh : kr);
+  const bool own = r >= 1 && r <= TYU && jr >= ty * TYU && (FULLROW || (l >= 1 && l <= TZU && kr >= tz * TZU));
+  const long rowoff = (long)j * g.nzp + 2 * kp;
+  const int rm = r > 0 ? r - 1 : 0, rp = r + 1 < TYR ? r + 1 : TYR - 1;
+  const double hx = g.hx, hy = g.hy, hz = g.hz;
+  const int nsteps = surplus ? 0 : (x0 + LX <= g.nx ? LX : g.nx - x0);
+
+  auto plane = [&](int q) {
+    const int x = q < 0 ? q + g.xw_lo : (q >= g.nx ? q - g.xw_hi : q);
+    return (long)x * g.nyzp + rowoff;
+  };
+  auto store_f = [&](long off, double2 v) {
+    if (nt) {
+      typedef double fg_v2d __attribute__((ext_vector_type(2)));
+      fg_v2d t;
+      t.x = v.x;
+      t.y = v.y;
+      __builtin_nontemporal_store(t, reinterpret_cast<fg_v2d*>(fo + off));
+    } else {
+      st2(fo, off, v);
+    }
+  };
+  const double cgb = CGP ? (cg.sc[cg.i_num] / cg.nvox + cg.small) / (cg.sc[cg.i_den] / cg.nvox + cg.small) : 0.0;
+  auto load_T = [&](long o, bool keep) {
+    double2 v = ld2(T, o);
+    if (CGP) {
+      const double2 rv = ld2(cg.r, o);
+      v.x = rv.x + cgb * v.x;
+      v.y = rv.y + cgb * v.y;
+      if (keep && own) st2(cg.po, o, v);
+    }
+    return v;
+  };
+  // the flux K(v) g(v) at one voxel
+  auto flux = [&](double ph, double gx, double gy, double gz, double& qx, double& qy, double& qz) {
+    const double k11 = K.d0[0] + ph * K.d1[0], k22 = K.d0[1] + ph * K.d1[1], k33 = K.d0[2] + ph * K.d1[2];
+    const double k23 = K.d0[3] + ph * K.d1[3], k13 = K.d0[4] + ph * K.d1[4], k12 = K.d0[5] + ph * K.d1[5];
+    qx = k11 * gx + k12 * gy + k13 * gz;
+    qy = k12 * gx + k22 * gy + k23 * gz;
+    qz = k13 * gx + k23 * gy + k33 * gz;
+  };
+  // the forward neighbours in y (image) and z (next lane / next wave's first lane) of the plane held in image `img`
+  auto forward = [&](int img, double2 Tc, double2& Tyf, double& Tzf) {
+    Tyf = Tb[img][rp][li];
+    Tzf = dpp_move<0x130>(Tc.x);
+    if (FULLROW) {
+      if (l == 63) Tzf = Tb[img][r][znext * 64].x;
+    }
+  };
+
+  double2 Tc = load_T(plane(x0 - 1), false), Tn = load_T(plane(x0), nsteps > 0), T2 = load_T(plane(x0 + 1), nsteps > 1);
+  double2 pc = ld2(phi1, plane(x0 - 1)), pn = ld2(phi1, plane(x0));
+  double2 q0m;   // x flux of the previous plane: plane x0 - 1 needs its whole gradient, one warm-up exchange (image 1)
+  {
+    Tb[1][r][li] = Tc;
+    __syncthreads();
+    double2 Tyf;
+    double Tzf;
+    forward(1, Tc, Tyf, Tzf);
+    double qy, qz;
+    flux(pc.x, E.v[0] + (Tn.x - Tc.x) * hx, E.v[1] + (Tyf.x - Tc.x) * hy, E.v[2] + (Tc.y - Tc.x) * hz, q0m.x, qy, qz);
+    flux(pc.y, E.v[0] + (Tn.y - Tc.y) * hx, E.v[1] + (Tyf.y - Tc.y) * hy, E.v[2] + (Tzf - Tc.y) * hz, q0m.y, qy, qz);
+  }
+  Tc = Tn; Tn = T2; pc = pn;
+  double acc[NA] = {};
+  // what the previous step left for its plane: the x part of f, q_y, q_z and q_z of the voxel below the pair
+  double2 fx = make_double2(0.0, 0.0), qyp = fx, qzp = fx;
+  double qzbp = 0.0;
+  long op = 0;
+
+  for (int st = 0; st <= nsteps; ++st) {
+    const int q = x0 + st;
+    const int img = st & 1;
+    const bool live = st < nsteps;
+    if (live) {
+      T2 = load_T(plane(q + 2), st + 2 < nsteps);
+      pn = ld2(phi1, plane(q + 1));
+      Tb[img][r][li] = Tc;
+    }
+    __syncthreads();
+    if (st > 0) {   // complete plane q - 1: q_y of row r - 1 is in the previous image by now
+      const double2 qyb = Qb[img ^ 1][rm][li];
+      double qzb = qzbp;
+      if (FULLROW) {
+        if (l == 0) qzb = Zb[img ^ 1][r][zprev];
+      }
+      double2 f;
+      f.x = fx.x + (qyp.x - qyb.x) * hy + (qzp.x - qzb) * hz;
+      f.y = fx.y + (qyp.y - qyb.y) * hy + (qzp.y - qzp.x) * hz;
+      if (own) store_f(op, f);
+    }
+    if (live) {
+      double2 Tyf;
+      double Tzf;
+      forward(img, Tc, Tyf, Tzf);
+      const double g0x = E.v[0] + (Tn.x - Tc.x) * hx, g0y = E.v[0] + (Tn.y - Tc.y) * hx;
+      const double g1x = E.v[1] + (Tyf.x - Tc.x) * hy, g1y = E.v[1] + (Tyf.y - Tc.y) * hy;
+      const double g2x = E.v[2] + (Tc.y - Tc.x) * hz, g2y = E.v[2] + (Tzf - Tc.y) * hz;
+      double2 qx, qy, qz;
+      flux(pc.x, g0x, g1x, g2x, qx.x, qy.x, qz.x);
+      flux(pc.y, g0y, g1y, g2y, qx.y, qy.y, qz.y);
+      Qb[img][r][li] = qy;
+      if (FULLROW) {
+        if (l == 63) Zb[img][r][zs] = qz.y;
+      }
+      qzbp = dpp_move<0x138>(qz.y);
+      if (own) {
+        acc[0] += g0x * g0x + g0y * g0y;
+        acc[1] += g1x * g1x + g1y * g1y;
+        acc[2] += g2x * g2x + g2y * g2y;
+      }
+      fx.x = (qx.x - q0m.x) * hx;
+      fx.y = (qx.y - q0m.y) * hx;
+      qyp = qy;
+      qzp = qz;
+      op = plane(q);
+      q0m = qx;
+      Tc = Tn; Tn = T2; pc = pn;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NA; ++c) {
+    double v = acc[c];
+    v += dpp_move<0x128>(v);
+    v += dpp_move<0x124>(v);
+    v += dpp_move<0x122>(v);
+    v += dpp_move<0x121>(v);
+    acc[c] = (read_lane(v, 0) + read_lane(v, 16)) + (read_lane(v, 32) + read_lane(v, 48));
+  }
+  if (l == 0) {
+#pragma unroll
+    for (int c = 0; c < NA; ++c) red[wv * NA + c] = acc[c];
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    double v = 0.0;
+    if (threadIdx.x < NA)
+      for (int w = 0; w < TYR * NZS; ++w) v += red[w * NA + threadIdx.x];
+    partial[(long)blockIdx.x * 6 + threadIdx.x] = v;
+  }
+}
+
+template <int TYR, int ZS>
+void launch_sc_tile_aniso_t(const Grid& g, const ScAnisoLin& K, const double* T, const double* phi1, double* f, const Vec6& E,
+                            double* partial, double* sumsq6, hipStream_t s, const ScCgDirection* cgd) {
+  constexpr int NZS = ZS ? ZS : 1;
+  constexpr int TYU = TYR - 2, TZU = ZS ? 64 * ZS : 62;
+  const int nzh = g.nz / 2;
+  const int nty = (g.ny + TYU - 1) / TYU, ntz = (nzh + TZU - 1) / TZU;
+  const int cus = device_cu_count();
+  int LX = march_length(g.nx, (long)nty * ntz, 2 * cus);
+  if (LX > g.nx) LX = g.nx;
+  const int ntx = (g.nx + LX - 1) / LX;
+  int nb = nty * ntz * ntx;
+  if (nb >= 8) nb = ((nb + 7) / 8) * 8;
+  const int nt = (double)g.n * sizeof(double) > 128.0 * 1024 * 1024 ? 1 : 0;
+  if (cgd)
+    hipLaunchKernelGGL((k_sc_tile_aniso<TYR, ZS, true>), dim3(nb), dim3(TYR * NZS * 64), 0, s, g, K, T, phi1, f, E, partial, nty, ntz,
+                       LX, nt, *cgd);
+  else
+    hipLaunchKernelGGL((k_sc_tile_aniso<TYR, ZS>), dim3(nb), dim3(TYR * NZS * 64), 0, s, g, K, T, phi1, f, E, partial, nty, ntz, LX,
+                       nt, ScCgDirection{});
+  FG_HIP_CHECK(hipGetLastError());
+  fold_sum(partial, nb, 6, sumsq6, s);
+  FG_HIP_CHECK(hipGetLastError());
+}
+
+// K0, K1: the six constants of the two phases (an isotropic phase as mu on the diagonal); cg: the direction update of the
+// conjugate gradients (launch_sc_sweep_cg) or none.  The grid must pass sc_sweep_tiled.
+void launch_sc_tile_aniso(const Grid& g, double mu_0, const double* K0, const double* K1, const double* T, const double* phi1,
+                          double* f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s, const double* cg_r,
+                          double* cg_p_new, const double* sc, int i_num, int i_den, double nvox, double small) {
+  ScAnisoLin K;
+  for (int c = 0; c < 6; ++c) {
+    K.d0[c] = K0[c] - (c < 3 ? 2 * mu_0 : 0.0);
+    K.d1[c] = K1[c] - K0[c];
+  }
+  const ScCgDirection cg = {cg_r, cg_p_new, sc, i_num, i_den, nvox, small};
+  const ScCgDirection* cgd = cg_r ? &cg : nullptr;
+  const int nzh = g.nz / 2;
+  if (nzh == 64) launch_sc_tile_aniso_t<8, 1>(g, K, T, phi1, f, E, partial, sumsq6, s, cgd);
+  else if (nzh == 128) launch_sc_tile_aniso_t<6, 2>(g, K, T, phi1, f, E, partial, sumsq6, s, cgd);
+  else launch_sc_tile_aniso_t<8, 0>(g, K, T, phi1, f, E, partial, sumsq6, s, cgd);
+}
+
 // Scalar sibling of k_cgu_tile (conjugate gradients in potential space, k_sc_cg_dot / k_sc_cg_axpy of fg_kernels_scalar.hip):
 // gradients are forward differences, so a tile needs the NEXT plane (registers), the next row (LDS) and the next lane (DPP).
 //   MODE 0:  partial[0] = sum grad A . (grad A - grad B),  A = a, B = b

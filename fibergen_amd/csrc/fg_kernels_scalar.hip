@@ -32,9 +32,105 @@ __device__ __forceinline__ double sc_flux(const ScalarParams& sp, const double* 
   return P;
 }
 
+// The same mixing over phases of either law, for component c of the flux: an aniso phase contributes
+// MatrixLinearAnisotropicMaterialLaw::PK1  F:11114-11128,  S[c] (+)= alpha * (K_c0 E_0 + K_c1 E_1 + K_c2 E_2)  with
+// alpha = phi * alpha, an iso phase the term of sc_flux.  All three gradient components of the voxel enter.
+__device__ __forceinline__ double sc_flux_row(const ScalarParams& sp, const double* ph, const double* g, int c) {
+  // K is stored 11, 22, 33, 23, 13, 12: the entries of row c
+  const int i0 = c == 0 ? 0 : (c == 1 ? 5 : 4), i1 = c == 0 ? 5 : (c == 1 ? 1 : 3), i2 = c == 0 ? 4 : (c == 1 ? 3 : 2);
+  double P = 0.0;
+  bool first = true;
+  for (int p = 0; p < sp.n; ++p) {
+    if (ph[p] <= kVoigtThreshold) continue;
+    const double alpha = ph[p] * sp.alpha;
+    double t;
+    if (sp.law[p] == kScLawAniso) t = alpha * (sp.K[p][i0] * g[0] + sp.K[p][i1] * g[1] + sp.K[p][i2] * g[2]);
+    else t = g[c] * (alpha * sp.mu[p]);
+    if (first) P = t;
+    else P += t;
+    first = false;
+  }
+  if (sp.beta != 0) P += sp.beta * g[c];
+  return P;
+}
+
 struct PhiPair {
   double v[kMaxPhases][2];
 };
+
+// T_k -> sums of squares of g_k = E + grad+ T_k (epsOperatorStaggeredHeat  F:18697-18760, component_norm
+// F:10127) and f = div-( (C - C0) g_k )  (calcStress  F:18134, divOperatorStaggeredHeat  F:18914-18975) with an aniso phase
+// present.  calcStress evaluates the law per voxel index on the three stored gradient components, so q_x(v) mixes g_y(v) and
+// g_z(v) although they sit on other faces: div- q at v needs the whole gradient at v - x, v - y and v - z, a 13-point stencil
+// on T (the six diagonal neighbours v-x+y, v-x+z, v-y+x, v-y+z, v-z+x, v-z+y enter).  Order of the reference: gradient at a
+// voxel, full flux at that voxel, backward divergence of the three flux components.
+__global__ __launch_bounds__(kBlock) void k_sc_sweep_aniso(Grid g, ScalarParams sp, const double* T, FieldPtrs<kMaxPhases> phi,
+                                                           double* f, Vec6 E, double* partial, Sweep sw) {
+  __shared__ double smem[4 * 6];
+  const double hx = g.hx, hy = g.hy, hz = g.hz;
+  const long npairs = (long)g.nx * g.ny * g.nzc;
+  double acc[6] = {0, 0, 0, 0, 0, 0};
+  const BlockRun run = block_run((npairs + kBlock - 1) / kBlock);
+  for (long it = 0; it < run.count; ++it) {
+    const long pidx = (run.first + it * run.stride) * kBlock + threadIdx.x;
+    if (pidx >= npairs) continue;
+    const PairPos p = pair_pos_tiled(pidx, g, sw);
+    if (p.k >= g.nz) continue;
+    const bool second = p.k + 1 < g.nz;
+    const long xf = (p.i + 1 == g.nx ? -(long)(g.nx - 1) : 1L) * g.nyzp;
+    const long xb = (p.i == 0 ? (long)(g.nx - 1) : -1L) * g.nyzp;
+    const long yf = (p.j + 1 == g.ny ? -(long)(g.ny - 1) : 1L) * g.nzp;
+    const long yb = (p.j == 0 ? (long)(g.ny - 1) : -1L) * g.nzp;
+    const long ro = p.off - p.k;
+    const int k = p.k;
+    const int kb = k == 0 ? g.nz - 1 : k - 1;
+    const int kf2 = (k + 2 >= g.nz) ? k + 2 - g.nz : k + 2;
+    const Row4 Tc = load_row(T, ro, k, kb, kf2, second, true, true);
+    const Row4 Txf = load_row(T, ro + xf, k, kb, kf2, second, true, false);
+    const Row4 Tyf = load_row(T, ro + yf, k, kb, kf2, second, true, false);
+    const Row4 Txb = load_row(T, ro + xb, k, kb, kf2, second, false, true);
+    const Row4 Tyb = load_row(T, ro + yb, k, kb, kf2, second, false, true);
+    const Row4 Txbyf = load_row(T, ro + xb + yf, k, kb, kf2, second, false, false);   // rows of the diagonal neighbours
+    const Row4 Tybxf = load_row(T, ro + yb + xf, k, kb, kf2, second, false, false);
+    double fo[2] = {0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      if (s == 1 && !second) break;
+      const int i0 = s + 1;
+      double pc[kMaxPhases], pxb[kMaxPhases], pyb[kMaxPhases], pzb[kMaxPhases];
+      const int kz = k + s;
+      const int kzb = kz == 0 ? g.nz - 1 : kz - 1;
+      for (int q = 0; q < sp.n; ++q) {
+        pc[q] = phi.p[q][ro + kz];
+        pxb[q] = phi.p[q][ro + xb + kz];
+        pyb[q] = phi.p[q][ro + yb + kz];
+        pzb[q] = phi.p[q][ro + kzb];
+      }
+      // the gradient at v = (i, j, k) and at its three backward neighbours
+      const double gc[3] = {E.v[0] + (Txf.v[i0] - Tc.v[i0]) * hx, E.v[1] + (Tyf.v[i0] - Tc.v[i0]) * hy,
+                            E.v[2] + (Tc.v[i0 + 1] - Tc.v[i0]) * hz};
+      const double gxb[3] = {E.v[0] + (Tc.v[i0] - Txb.v[i0]) * hx, E.v[1] + (Txbyf.v[i0] - Txb.v[i0]) * hy,
+                             E.v[2] + (Txb.v[i0 + 1] - Txb.v[i0]) * hz};
+      const double gyb[3] = {E.v[0] + (Tybxf.v[i0] - Tyb.v[i0]) * hx, E.v[1] + (Tc.v[i0] - Tyb.v[i0]) * hy,
+                             E.v[2] + (Tyb.v[i0 + 1] - Tyb.v[i0]) * hz};
+      const double gzb[3] = {E.v[0] + (Txf.v[i0 - 1] - Tc.v[i0 - 1]) * hx, E.v[1] + (Tyf.v[i0 - 1] - Tc.v[i0 - 1]) * hy,
+                             E.v[2] + (Tc.v[i0] - Tc.v[i0 - 1]) * hz};
+      acc[0] += gc[0] * gc[0];
+      acc[1] += gc[1] * gc[1];
+      acc[2] += gc[2] * gc[2];
+      double y = (sc_flux_row(sp, pc, gc, 0) - sc_flux_row(sp, pxb, gxb, 0)) * hx;
+      y += (sc_flux_row(sp, pc, gc, 1) - sc_flux_row(sp, pyb, gyb, 1)) * hy;
+      y += (sc_flux_row(sp, pc, gc, 2) - sc_flux_row(sp, pzb, gzb, 2)) * hz;
+      fo[s] = y;
+    }
+    st2(f, p.off, make_double2(fo[0], fo[1]));
+  }
+  block_reduce<6>(acc, smem, OpSum());
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) partial[(long)blockIdx.x * 6 + c] = acc[c];
+  }
+}
 
 // T_k -> sums of squares of g_k = E + grad+ T_k (epsOperatorStaggeredHeat  F:18697-18760, component_norm
 // F:10127) and f = div-( (C - C0) g_k )  (calcStress  F:18134, divOperatorStaggeredHeat  F:18914-18975).
@@ -146,7 +242,8 @@ __global__ __launch_bounds__(kBlock) void k_sc_grad(Grid g, const double* T, Fie
 }
 
 // g -> flux P(g) * alpha + beta g (3 components), stored or (REDUCE: meanPK1  F:12312-12351) summed
-template <bool REDUCE>
+// ANISO: a phase of law aniso is present, every flux component takes the three gradient components (sc_flux_row)
+template <bool REDUCE, bool ANISO = false>
 __global__ __launch_bounds__(kBlock) void k_sc_flux(Grid g, ScalarParams sp, FieldPtrs<3> gr, FieldPtrs<kMaxPhases> phi,
                                                     FieldPtrs<3> out, double* partial) {
   __shared__ double smem[4 * 6];
@@ -160,9 +257,14 @@ __global__ __launch_bounds__(kBlock) void k_sc_flux(Grid g, ScalarParams sp, Fie
       if (p.k + s >= g.nz) break;
       double ph[kMaxPhases];
       for (int q = 0; q < sp.n; ++q) ph[q] = phi.p[q][p.off + s];
+      double gv[3] = {0, 0, 0};
+      if (ANISO) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gv[c] = gr.p[c][p.off + s];
+      }
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        o[c][s] = sc_flux(sp, ph, gr.p[c][p.off + s]);
+        o[c][s] = ANISO ? sc_flux_row(sp, ph, gv, c) : sc_flux(sp, ph, gr.p[c][p.off + s]);
         acc[c] += o[c][s];
       }
     }
@@ -242,6 +344,85 @@ __global__ __launch_bounds__(kBlock) void k_sc_minmax(Grid g, ScalarParams sp, F
       const double t = sc_flux(sp, ph, 1.0);  // dPK1 with W = 1: (phi * 1) * mu accumulated
       acc[0] = acc[0] < t ? acc[0] : t;
       acc[1] = acc[1] < -t ? acc[1] : -t;
+    }
+  }
+  block_reduce<2>(acc, smem, OpMin());
+  if (threadIdx.x == 0) {
+    partial[(long)blockIdx.x * 2 + 0] = acc[0];
+    partial[(long)blockIdx.x * 2 + 1] = acc[1];
+  }
+}
+
+// One Jacobi rotation in the plane (p, q) of a symmetric 3 x 3 matrix: a_pq -> 0; r is the third index
+__device__ __forceinline__ void jacobi_rotate3(double& app, double& aqq, double& apq, double& arp, double& arq) {
+  if (apq == 0.0) return;
+  const double theta = (aqq - app) / (2 * apq);
+  const double t = (theta < 0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1));
+  const double c = 1 / sqrt(t * t + 1), sn = t * c;
+  app -= t * apq;
+  aqq += t * apq;
+  apq = 0.0;
+  const double rp = c * arp - sn * arq, rq = sn * arp + c * arq;
+  arp = rp;
+  arq = rq;
+}
+
+// Eigenvalues of a symmetric 3 x 3 matrix (a00, a11, a22, a12, a02, a01) by cyclic Jacobi rotations: what dsyev returns for
+// the matrix eig() hands it (F:12518-12522) to a few ulp of its norm, also for the repeated eigenvalues of a transversely
+// isotropic K, where the closed trigonometric form loses half the digits.  An off-diagonal of size off moves an eigenvalue
+// by at most off (second order in it where the eigenvalues are apart): the sweeps stop at eps^2 of the diagonal.
+__device__ __forceinline__ void sym3_eigenvalues(double a00, double a11, double a22, double a12, double a02, double a01, double* w) {
+  for (int sweep = 0; sweep < 12; ++sweep) {
+    const double off = fabs(a01) + fabs(a02) + fabs(a12);
+    if (off <= 4.9e-32 * (fabs(a00) + fabs(a11) + fabs(a22))) break;
+    jacobi_rotate3(a00, a11, a01, a02, a12);
+    jacobi_rotate3(a00, a22, a02, a01, a12);
+    jacobi_rotate3(a11, a22, a12, a01, a02);
+  }
+  w[0] = a00;
+  w[1] = a11;
+  w[2] = a22;
+}
+
+// The same scan with an aniso phase present: the Voigt tangent sum_p phi_p K_p (VoigtMixedMaterialLaw::dPK1  F:12763-12771
+// over MatrixLinearAnisotropicMaterialLaw::dPK1  F:11130-11150 and the scalar law's, on the rows of the identity: row m is
+// alpha * K(:, m), the phases above the threshold accumulated in their order) is a full symmetric 3 x 3 per voxel, and its
+// extreme eigenvalues are not monotone in phi: every voxel is diagonalised.
+__global__ __launch_bounds__(kBlock) void k_sc_minmax_aniso(Grid g, ScalarParams sp, FieldPtrs<kMaxPhases> phi, double* partial) {
+  __shared__ double smem[4 * 2];
+  const long npairs = (long)g.nx * g.ny * g.nzc;
+  double acc[2] = {1.0 / 0.0, 1.0 / 0.0};  // (min, -max)
+  for (long pidx = (long)blockIdx.x * blockDim.x + threadIdx.x; pidx < npairs; pidx += (long)gridDim.x * blockDim.x) {
+    const PairPos p = pair_pos(pidx, g);
+    for (int s = 0; s < 2; ++s) {
+      if (p.k + s >= g.nz) continue;
+      double A[6] = {0, 0, 0, 0, 0, 0};
+      bool first = true;
+      for (int q = 0; q < sp.n; ++q) {
+        const double f = phi.p[q][p.off + s];
+        if (f <= kVoigtThreshold) continue;
+        const double alpha = f * sp.alpha;
+        double t[6];
+        if (sp.law[q] == kScLawAniso) {
+#pragma unroll
+          for (int c = 0; c < 6; ++c) t[c] = alpha * sp.K[q][c];
+        } else {
+          const double am = alpha * sp.mu[q];   // dS[s] = W[s] * alpha_mu on the identity rows
+          t[0] = t[1] = t[2] = am;
+          t[3] = t[4] = t[5] = 0.0;
+        }
+#pragma unroll
+        for (int c = 0; c < 6; ++c) A[c] = first ? t[c] : A[c] + t[c];
+        first = false;
+      }
+      if (first) continue;   // no phase above the threshold: dPK1 leaves the matrix unset; nothing to scan
+      double w[3];
+      sym3_eigenvalues(A[0], A[1], A[2], A[3], A[4], A[5], w);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        acc[0] = acc[0] < w[c] ? acc[0] : w[c];
+        acc[1] = acc[1] < -w[c] ? acc[1] : -w[c];
+      }
     }
   }
   block_reduce<2>(acc, smem, OpMin());
@@ -335,7 +516,8 @@ int grid_cap(long nwork, int max_blocks) {
 void launch_sc_sweep(const Grid& g, const ScalarParams& sp, const double* T, const FieldPtrs<kMaxPhases>& phi, double* f,
                      const Vec6& E, double* partial, double* sumsq6, hipStream_t s) {
   const int nb = sweep_blocks((long)g.nx * g.ny * g.nzc);
-  hipLaunchKernelGGL(k_sc_sweep, dim3(nb), dim3(kBlock), 0, s, g, sp, T, phi, f, E, partial, chunk_rows(g));
+  if (any_aniso_phase(sp)) hipLaunchKernelGGL(k_sc_sweep_aniso, dim3(nb), dim3(kBlock), 0, s, g, sp, T, phi, f, E, partial, chunk_rows(g));
+  else hipLaunchKernelGGL(k_sc_sweep, dim3(nb), dim3(kBlock), 0, s, g, sp, T, phi, f, E, partial, chunk_rows(g));
   FG_HIP_CHECK(hipGetLastError());
   fold_sum(partial, nb, 6, sumsq6, s);
   FG_HIP_CHECK(hipGetLastError());
@@ -353,14 +535,16 @@ void launch_sc_grad(const Grid& g, const double* T, const FieldPtrs<3>& out, con
 void launch_sc_flux(const Grid& g, const ScalarParams& sp, const FieldPtrs<3>& gr, const FieldPtrs<kMaxPhases>& phi,
                     const FieldPtrs<3>& out, hipStream_t s) {
   const long npairs = (long)g.nx * g.ny * g.nzc;
-  hipLaunchKernelGGL(k_sc_flux<false>, dim3(grid_cap(npairs, 1 << 20)), dim3(kBlock), 0, s, g, sp, gr, phi, out, nullptr);
+  if (any_aniso_phase(sp)) hipLaunchKernelGGL((k_sc_flux<false, true>), dim3(grid_cap(npairs, 1 << 20)), dim3(kBlock), 0, s, g, sp, gr, phi, out, nullptr);
+  else hipLaunchKernelGGL(k_sc_flux<false>, dim3(grid_cap(npairs, 1 << 20)), dim3(kBlock), 0, s, g, sp, gr, phi, out, nullptr);
   FG_HIP_CHECK(hipGetLastError());
 }
 
 void launch_sc_flux_mean(const Grid& g, const ScalarParams& sp, const FieldPtrs<3>& gr, const FieldPtrs<kMaxPhases>& phi,
                          double* partial, double* out6, hipStream_t s) {
   const int nb = reduce_blocks(g);
-  hipLaunchKernelGGL(k_sc_flux<true>, dim3(nb), dim3(kBlock), 0, s, g, sp, gr, phi, gr, partial);
+  if (any_aniso_phase(sp)) hipLaunchKernelGGL((k_sc_flux<true, true>), dim3(nb), dim3(kBlock), 0, s, g, sp, gr, phi, gr, partial);
+  else hipLaunchKernelGGL(k_sc_flux<true>, dim3(nb), dim3(kBlock), 0, s, g, sp, gr, phi, gr, partial);
   FG_HIP_CHECK(hipGetLastError());
   fold_sum(partial, nb, 6, out6, s);
   FG_HIP_CHECK(hipGetLastError());
@@ -432,7 +616,8 @@ void launch_sc_cg_axpy(int mode, const Grid& g, double* x, double* y, double* r,
 void launch_sc_minmax(const Grid& g, const ScalarParams& sp, const FieldPtrs<kMaxPhases>& phi, double* partial,
                       double* out2, hipStream_t s) {
   const int nb = reduce_blocks(g);
-  hipLaunchKernelGGL(k_sc_minmax, dim3(nb), dim3(kBlock), 0, s, g, sp, phi, partial);
+  if (any_aniso_phase(sp)) hipLaunchKernelGGL(k_sc_minmax_aniso, dim3(nb), dim3(kBlock), 0, s, g, sp, phi, partial);
+  else hipLaunchKernelGGL(k_sc_minmax, dim3(nb), dim3(kBlock), 0, s, g, sp, phi, partial);
   FG_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_fold<OpMin>, dim3(1), dim3(kBlock), 0, s, partial, nb, 2, 1.0 / 0.0, out2);
   FG_HIP_CHECK(hipGetLastError());

@@ -615,6 +615,7 @@ void SlabGroup::check_members() const {
   if (a.pt_.n < 1) throw std::runtime_error("No materials specified");
   for (Solver* s : m_) {
     if (s->general_phase()) throw std::runtime_error("general (anisotropic) phases are not available on slab-decomposed solvers");
+    if (s->aniso_phase()) throw std::runtime_error("aniso (3 x 3 conductivity) phases are not available on slab-decomposed solvers");
     if (s->nranks_ > 1 && !s->comm_) throw std::runtime_error("slab solver is not connected to a transport (fg_slab_connect_*)");
     if (s->opt_.mixing != a.opt_.mixing || s->pt_.n != a.pt_.n || s->opt_.u_loop != a.opt_.u_loop || s->opt_.u_tile != a.opt_.u_tile ||
         s->opt_.slab_split != a.opt_.slab_split || s->opt_.slab_interleave != a.opt_.slab_interleave || s->opt_.method != a.opt_.method ||

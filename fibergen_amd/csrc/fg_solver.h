@@ -89,6 +89,8 @@ struct SolverOptions {
   int phi_sweep = 1;            // two complementary phases: the tiled sweep reads phi_1 instead of the two moduli arrays
   int aniso_tile = 1;           // general (6 x 6 stiffness) phases, two complementary phases: the displacement loop on the tiled sweep's
                                 // anisotropic form (1) or the strain-state pass everywhere (0; also what every other case runs)
+  int aniso_sc_tile = 1;        // heat / porous, two complementary phases with an aniso (3 x 3) phase: the potential loop on the tiled
+                                // sweep's aniso form (1) or the exact-order 13-point sweep everywhere (0; also what every other case runs)
   int laminate_overlap = 1;     // displacement loop with laminate mixing: interface kernels on a second stream beside the sweep
   int slab_loopback = 0;        // test mode: a lone slab sends to itself through its transport (see Solver::slab_loopback)
   int slab_split = -1;          // slab driver: all-to-all per component, overlapping the next component's transforms (1), one
@@ -159,6 +161,8 @@ class Solver {
   // of the tensor shear strains sits in the product -- general6, fg_stage_math.h) and becomes a general phase until
   // set_phase_material makes it isotropic again.  Throws unless |C_ij - C_ji| <= 1e-12 max|C|.
   void set_phase_stiffness(int p, const double* C36);
+  void set_phase_conductivity(int p, const double* c6);   // heat / porous: law "aniso", c11 c22 c33 c23 c13 c12
+  bool aniso_phase() const;                               // a phase of law "aniso" is set
   bool general_phase() const { return any_general_phase(pt_); }
   void set_phase_field(int p, const double* phi_host);  // [nx][ny][nz], copied
   // gamma_scheme 2: phase p's image on the doubly fine grid [2nx][2ny][2nz] (initPhi under select_dfg F:17152-17230), reduced on
@@ -227,7 +231,7 @@ class Solver {
   void reset_stage_times();
   double event_bias_ms() const { return event_bias_ms_; }
   // fg_get_counter: "interface_voxels" / "affected_voxels" = lengths of the laminate correction's lists (0 before they are
-  // built); "phase_uploads" = host arrays received by set_phase_field / set_phase_field_fine / set_normals; "u_tile_aniso" =
+  // built); "sc_tile_aniso" = launches of k_sc_tile_aniso; "phase_uploads" = host arrays received by set_phase_field / set_phase_field_fine / set_normals; "u_tile_aniso" =
   // launches of the tiled sweep's anisotropic form; -1 = unknown name
   long counter(const std::string& name) const;
 
@@ -262,7 +266,9 @@ class Solver {
   bool run_cg_scalar(const double* E0, double prev0);  // heat / porous: CG in potential space
   bool run_cg_u(const double* E0, double prev0);      // the same CG carried in displacement space (Voigt, prescribed mean strains)
   bool u_loop_eligible(bool allow_mixed_bc = false);   // (may run the complement check on the device)
-  bool two_phase_complementary();       // phi_0 == 1 - phi_1 everywhere (checked once per geometry)
+  bool sc_tile_aniso_ok(bool mixed_bc); // aniso phases: the tiled sweep has a form for this problem (k_sc_tile_aniso)
+  void sc_aniso_constants(double* K0, double* K1) const;   // the six constants of phases 0 and 1 (isotropic: mu on the diagonal)
+  bool two_phase_complementary(bool scalar = false);       // phi_0 == 1 - phi_1 everywhere (checked once per geometry)
   void general_check() const;           // throws for the combinations general phases do not cover
   bool aniso_tile_ok();                 // general phases: the displacement loop has a sweep for this problem (k_u_tile ANISO)
   FieldPtrs<2> effective_moduli();      // per-voxel sums of the phase moduli for the fast kernels (allocated on first use)
@@ -406,6 +412,9 @@ class Solver {
   double* mod5_ = nullptr;     // gamma_scheme 2: the five moduli
   bool mod5_dirty_ = true;
   bool complement_dirty_ = true, complementary_ = false;
+  int sc_law_[kMaxPhases];         // scalar modes: ScalarLaw per phase (ScalarParams::law)
+  double sc_K_[kMaxPhases][6];     // and the six constants of an aniso phase
+  long sc_tile_aniso_ = 0;  // launches of the tiled scalar sweep's aniso form (fg_get_counter "sc_tile_aniso")
   long u_tile_aniso_ = 0;   // launches of the tiled sweep's anisotropic form (fg_get_counter "u_tile_aniso")
   double* fu_alt_ = nullptr;   // 3: second f/u buffer of the displacement-based loop (swapped with fu_)
   double* phi_ = nullptr;      // nphase

@@ -93,6 +93,8 @@ Solver::Solver(int nx, int ny, int nz, double dx, double dy, double dz, int devi
   for (int i = 0; i < kMaxPhases; ++i) {
     pt_.mu[i] = pt_.lambda[i] = 0.0;
     pt_.law[i] = kLawIso;
+    sc_law_[i] = kScLawIso;
+    for (int c = 0; c < 6; ++c) sc_K_[i][c] = 0.0;
     for (int k = 0; k < 36; ++k) pt_.C[i][k] = 0.0;
   }
   opt_.mu_0 = std::numeric_limits<double>::quiet_NaN();  // F:15340
@@ -243,6 +245,11 @@ void Solver::set_num_phases(int n) {
   phis_ = nullptr;
   fine_set_ = 0;
   pt_.n = n;
+  for (int p = 0; p < kMaxPhases; ++p) {   // a fresh set of phases: no general / aniso phase outlives it (their mu = NaN goes too)
+    if (pt_.law[p] != kLawIso || sc_law_[p] != kScLawIso) pt_.mu[p] = pt_.lambda[p] = 0.0;
+    pt_.law[p] = kLawIso;
+    sc_law_[p] = kScLawIso;
+  }
   mod_dirty_ = mod5_dirty_ = true;
   smod_dirty_ = mod5_dirty_ = true;
   complement_dirty_ = true;
@@ -258,6 +265,7 @@ void Solver::set_phase_material(int p, double mu, double lambda) {
   pt_.mu[p] = mu;
   pt_.lambda[p] = lambda;
   pt_.law[p] = kLawIso;
+  sc_law_[p] = kScLawIso;
 }
 
 void Solver::set_phase_stiffness(int p, const double* C36) {
@@ -276,8 +284,31 @@ void Solver::set_phase_stiffness(int p, const double* C36) {
   mixed_dirty_ = true;
   for (int i = 0; i < 36; ++i) pt_.C[p][i] = C36[i];
   pt_.law[p] = kLawGeneral;
+  sc_law_[p] = kScLawIso;
   // the safety net: whatever still reads (mu, lambda) of a general phase computes NaN, not an isotropic answer
   pt_.mu[p] = pt_.lambda[p] = std::numeric_limits<double>::quiet_NaN();
+}
+
+// law "aniso" of the scalar modes (MatrixLinearAnisotropicMaterialLaw  F:11087-11156): c11 c22 c33 c23 c13 c12
+void Solver::set_phase_conductivity(int p, const double* c6) {
+  if (p < 0 || p >= pt_.n) throw std::runtime_error("phase index out of range");
+  if (!c6) throw std::runtime_error("conductivity pointer is NULL");
+  if (opt_.mode != 1) throw std::runtime_error("aniso (3 x 3 conductivity) phases are available in heat / porous mode only");
+  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("aniso (3 x 3 conductivity) phases are not available on slab-decomposed solvers");
+  for (int i = 0; i < 6; ++i)
+    if (!std::isfinite(c6[i])) throw std::runtime_error("phase conductivity is not finite");
+  invalidate_moduli();
+  for (int i = 0; i < 6; ++i) sc_K_[p][i] = c6[i];
+  sc_law_[p] = kScLawAniso;
+  pt_.law[p] = kLawIso;
+  // the convention of general phases: whatever still reads mu of an aniso phase computes NaN, not an isotropic answer
+  pt_.mu[p] = pt_.lambda[p] = std::numeric_limits<double>::quiet_NaN();
+}
+
+bool Solver::aniso_phase() const {
+  bool a = false;
+  for (int p = 0; p < pt_.n; ++p) a = a || sc_law_[p] != kScLawIso;
+  return a;
 }
 
 void Solver::set_phase_field(int p, const double* phi_host) {
@@ -642,6 +673,7 @@ long Solver::counter(const std::string& name) const {
   if (name == "affected_voxels") return (long)aff_n_;
   if (name == "phase_uploads") return phase_uploads_;
   if (name == "u_tile_aniso") return u_tile_aniso_;
+  if (name == "sc_tile_aniso") return sc_tile_aniso_;
   if (name == "pair_chunk_planes") return (long)pair_chunk_planes(opt_.mode == 1 ? 1 : 3);
   return -1;
 }
@@ -1202,7 +1234,11 @@ int Solver::pair_chunk_planes(int) const {
 ScalarParams Solver::scalar_params(double mu_0, double alpha) const {
   ScalarParams sp;
   sp.n = pt_.n;
-  for (int q = 0; q < kMaxPhases; ++q) sp.mu[q] = q < pt_.n ? pt_.mu[q] : 0.0;
+  for (int q = 0; q < kMaxPhases; ++q) {
+    sp.mu[q] = q < pt_.n ? pt_.mu[q] : 0.0;
+    sp.law[q] = q < pt_.n ? sc_law_[q] : kScLawIso;
+    for (int c = 0; c < 6; ++c) sp.K[q][c] = q < pt_.n ? sc_K_[q][c] : 0.0;
+  }
   sp.alpha = alpha;
   sp.beta = -alpha * 2 * mu_0;  // calcStress  F:18138
   return sp;
@@ -1241,8 +1277,9 @@ bool Solver::u_loop_eligible(bool allow_mixed_bc) {
 
 // Two phases whose fractions are complementary bit for bit (phi_0 == 1 - phi_1: what normalizePhi leaves for two
 // materials), checked once per geometry on the device.  Option phi_sweep = 0 switches the shortcut off (A/B runs).
-bool Solver::two_phase_complementary() {
-  if (pt_.n != 2 || opt_.mode != 0 || !opt_.phi_sweep) return false;
+bool Solver::two_phase_complementary(bool scalar) {
+  if (pt_.n != 2 || !opt_.phi_sweep) return false;
+  if (opt_.mode != 0 && !(scalar && opt_.mode == 1)) return false;   // (scalar: the aniso form of the tiled scalar sweep asks)
   if (complement_dirty_) {
     int one = 1;
     FG_HIP_CHECK(hipMemcpyAsync(derr_ + 1, &one, sizeof(int), hipMemcpyHostToDevice, stream_));
@@ -1258,7 +1295,8 @@ bool Solver::two_phase_complementary() {
 
 // A = sum_p phi_p 2 mu_p, B = sum_p phi_p lambda_p per voxel (k_effective_moduli), computed once per geometry
 FieldPtrs<2> Solver::effective_moduli() {
-  if (general_phase()) throw std::logic_error("effective moduli (sum phi 2 mu, sum phi lambda) do not exist with a general phase");
+  if (general_phase() || aniso_phase())
+    throw std::logic_error("effective moduli (sum phi 2 mu, sum phi lambda) do not exist with a general or an aniso phase");
   if (!mod_) {
     FG_HIP_CHECK(hipMalloc(&mod_, 2 * (size_t)g_.n * sizeof(double)));
     mod_dirty_ = mod5_dirty_ = true;
@@ -1278,6 +1316,11 @@ FieldPtrs<2> Solver::effective_moduli() {
 
 // law "general" (constant 6 x 6 stiffness per phase): elasticity, Voigt mixing, staggered / collocated / willot, one GPU
 void Solver::general_check() const {
+  // law "aniso" (constant 3 x 3 conductivity per phase): heat / porous, one GPU (Voigt mixing is all these modes have)
+  if (aniso_phase()) {
+    if (opt_.mode != 1) throw std::runtime_error("aniso (3 x 3 conductivity) phases are available in heat / porous mode only");
+    if (nranks_ != 1 || slab_layout_) throw std::runtime_error("aniso (3 x 3 conductivity) phases are not available on slab-decomposed solvers");
+  }
   if (!general_phase()) return;
   if (opt_.mode != 0) throw std::runtime_error("general (anisotropic) phases are available in elasticity mode only");
   if (opt_.mixing != kMixVoigt)
@@ -1289,6 +1332,20 @@ void Solver::general_check() const {
 bool Solver::aniso_tile_ok() {
   return opt_.aniso_tile && opt_.mode == 0 && opt_.gamma_scheme == 0 && opt_.mixing == kMixVoigt && opt_.u_loop >= 2 && opt_.u_tile &&
          nranks_ == 1 && !slab_layout_ && u_tile_supported(g_) && two_phase_complementary();
+}
+
+// aniso phases of the scalar modes: k_sc_tile_aniso serves two complementary phases on the grids the tiled sweep takes; mixed
+// boundary conditions (no form with the sums of tau) and everything else run the exact-order sweep
+bool Solver::sc_tile_aniso_ok(bool mixed_bc) {
+  return opt_.aniso_sc_tile && opt_.mode == 1 && aniso_phase() && opt_.u_loop >= 2 && opt_.u_tile && !mixed_bc && nranks_ == 1 &&
+         !slab_layout_ && sc_sweep_tiled(g_) && two_phase_complementary(true);
+}
+
+void Solver::sc_aniso_constants(double* K0, double* K1) const {
+  for (int p = 0; p < 2; ++p) {
+    double* K = p ? K1 : K0;
+    for (int c = 0; c < 6; ++c) K[c] = sc_law_[p] == kScLawAniso ? sc_K_[p][c] : (c < 3 ? pt_.mu[p] : 0.0);
+  }
 }
 
 void Solver::willot_check() const {
@@ -1379,11 +1436,18 @@ void Solver::u_pass_front(const double* E6) {
   }
   time_begin(0);
   if (opt_.mode == 1) {
-    if (opt_.u_loop >= 2) {
-      // fast variant: effective conductivity a = sum_p phi_p mu_p precomputed (first moduli array)
+    if (opt_.u_loop >= 2 && !aniso_phase()) {
+      // fast variant: effective conductivity a = sum_p phi_p mu_p precomputed (first moduli array); an aniso phase has no
+      // such array and takes the exact-order sweep's 13-point form
       const bool mixed = !(frobenius(BC_MQ_) < kEps) && in_run_;
       sc_tau_sums_ = launch_sc_sweep_fast(g_, opt_.mu_0, fu_, effective_moduli().p[0], fu_alt_, E, partial_, dscal_ + kSlotSumSq,
                                           stream_, mixed ? dscal_ + kSlotMean : nullptr);
+    } else if (sc_tile_aniso_ok(!(frobenius(BC_MQ_) < kEps) && in_run_)) {
+      double K0[6], K1[6];
+      sc_aniso_constants(K0, K1);
+      sc_tau_sums_ = false;
+      launch_sc_tile_aniso(g_, opt_.mu_0, K0, K1, fu_, phi_ + g_.n, fu_alt_, E, partial_, dscal_ + kSlotSumSq, stream_);
+      ++sc_tile_aniso_;
     } else {
       sc_tau_sums_ = false;
       launch_sc_sweep(g_, scalar_params(opt_.mu_0, 1.0), fu_, phase_ptrs(), fu_alt_, E, partial_, dscal_ + kSlotSumSq, stream_);
@@ -2113,10 +2177,13 @@ bool Solver::run_cg_scalar(const double* E0, double prev0) {
   // callback (accessors read fu_'s first component in between).
   const int fused_opt = opt_.cg_fused;
   const double nvox = (double)nglobal_;
-  if (fused_opt != 0 && !cb_ && opt_.u_loop >= 2 && sc_sweep_tiled(g_) && !slab_layout_) {
+  const bool aniso = aniso_phase();   // the fused form needs the tiled sweep: for aniso phases its two-phase form
+  if (fused_opt != 0 && !cb_ && opt_.u_loop >= 2 && sc_sweep_tiled(g_) && !slab_layout_ && (!aniso || sc_tile_aniso_ok(false))) {
     const CgSlots slot = cg_slots(kSlotCg);
     double *e_cur = fu_, *e_alt = fu_ + g_.n, *r_cur = T_r, *r_alt = cg_r_ + 2 * g_.n, *p_cur = T_p, *p_alt = cg_r_ + 3 * g_.n;
-    const double* cond = effective_moduli().p[0];
+    const double* cond = aniso ? nullptr : effective_moduli().p[0];
+    double K0[6], K1[6];
+    if (aniso) sc_aniso_constants(K0, K1);
     launch_sc_cg_dot(1, g_, e_cur, r_cur, E, partial_, dscal_ + slot.blk[0], stream_);   // gamma_0 = r.r / N + tiny
     FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotCg + 6, dscal_ + slot.rr(0), sizeof(double), hipMemcpyDeviceToHost, stream_));
     FG_HIP_CHECK(hipStreamSynchronize(stream_));
@@ -2127,8 +2194,14 @@ bool Solver::run_cg_scalar(const double* E0, double prev0) {
     ops.apply_p = [&] { apply(p_cur, Z.v); };
     ops.apply_dir = [&](int num, int den) {   // T_p := T_r + beta T_p inside the sweep; T_w = operator(T_p)
       time_begin(0);
-      launch_sc_sweep_cg(g_, opt_.mu_0, p_cur, r_cur, p_alt, cond, fu_alt_, Z, dscal_, num, den, nvox, small, partial_,
-                         dscal_ + kSlotSumSq, stream_);
+      if (aniso) {
+        launch_sc_tile_aniso(g_, opt_.mu_0, K0, K1, p_cur, phi_ + g_.n, fu_alt_, Z, partial_, dscal_ + kSlotSumSq, stream_, r_cur, p_alt,
+                             dscal_, num, den, nvox, small);
+        ++sc_tile_aniso_;
+      } else {
+        launch_sc_sweep_cg(g_, opt_.mu_0, p_cur, r_cur, p_alt, cond, fu_alt_, Z, dscal_, num, den, nvox, small, partial_,
+                           dscal_ + kSlotSumSq, stream_);
+      }
       time_end(0);
       fft_g0_chain(fu_alt_);
       std::swap(p_cur, p_alt);

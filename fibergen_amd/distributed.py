@@ -68,6 +68,11 @@ class SlabMember(LSSolver):
     def transport(self):
         return self._lib.fg_slab_transport(self._h).decode()
 
+    def set_phase_conductivity(self, p, K, phi=None):
+        """law="aniso": the slab sweeps are isotropic (refused before anything reaches the library)"""
+        from .materials import ANISO_SLAB_ERROR
+        raise RuntimeError(ANISO_SLAB_ERROR)
+
     def slab(self, array):
         """This rank's x-slab of a global array [..., nx, ny, nz]."""
         a = np.asarray(array)
@@ -286,6 +291,10 @@ class SlabGroup:
     def set_phase_stiffness(self, p, C):
         from .materials import GENERAL_SLAB_ERROR
         raise RuntimeError(GENERAL_SLAB_ERROR)
+
+    def set_phase_conductivity(self, p, K, phi=None):
+        from .materials import ANISO_SLAB_ERROR
+        raise RuntimeError(ANISO_SLAB_ERROR)
 
     def set_normals(self, normals):
         for m in self.members:

@@ -317,6 +317,12 @@ class FG:
                 raise RuntimeError(_materials.GENERAL_DFG_ERROR)
             if getattr(self, "_slabs", False):
                 raise RuntimeError(_materials.GENERAL_SLAB_ERROR)
+        # law="aniso" exists in heat / porous only (F:15229-15233); elsewhere it stays an unknown law (below).  The slab
+        # sweeps are isotropic: refused before a solver exists
+        heat = mode in ("heat", "porous")
+        if heat and getattr(self, "_slabs", False) and mats_el is not None and any(
+                isinstance(m.tag, str) and m.tag != "ref" and m.attrib.get("law", "iso") == "aniso" for m in mats_el):
+            raise RuntimeError(_materials.ANISO_SLAB_ERROR)
 
         if getattr(self, "_slabs", False):
             from .distributed import GlobalViewSolver
@@ -382,10 +388,13 @@ class FG:
                     matrix_set = True
                     matrix_mat = len(names)
                 law = attrs.get("law", "iso")
-                if law not in ("iso", "general"):
+                if law not in ("iso", "general") and not (law == "aniso" and heat):
                     raise RuntimeError("Unknown material law '%s'" % law)
                 names.append(m.tag)
-                if law == "general":
+                if law == "aniso":
+                    # MatrixLinearAnisotropicMaterialLaw  F:11087-11156, read at F:15229-15233: a constant symmetric 3x3
+                    consts.append({"cond": _materials.aniso_conductivity(attrs, self._eval)})
+                elif law == "general":
                     # LinearGeneralMaterialLaw  F:11233-11349, read at F:15215-15218: a constant 6x6 stiffness
                     consts.append({"C": _materials.general_stiffness(attrs, self._eval)})
                 elif scalar:
@@ -397,6 +406,7 @@ class FG:
             raise RuntimeError("No materials specified")
         lss.set_num_phases(len(names))
         self._phase_materials = consts
+        lss.set_options(mode=mode)   # before the phases: which laws a phase may take depends on the mode
         for p in range(len(consts)):
             self._set_phase(lss, p)
         lss.set_options(**opts)
@@ -409,11 +419,14 @@ class FG:
         self._solver_valid = True
 
     def _set_phase(self, lss, p, phi=None):
-        """phase p's constants (and field) into the solver: (mu, lambda), or the stiffness of a law="general" material"""
+        """phase p's constants (and field) into the solver: (mu, lambda), the stiffness of a law="general" material, or the
+        conductivity of a law="aniso" material"""
         c = self._phase_materials[p]
         if "C" in c:
             lss.set_phase(p, 0.0, 0.0, phi)
             lss.set_phase_stiffness(p, c["C"])
+        elif "cond" in c:
+            lss.set_phase_conductivity(p, c["cond"], phi)
         else:
             lss.set_phase(p, c["mu"], c["lambda"], phi)
 

@@ -88,6 +88,18 @@ GENERAL_DFG_ERROR = "general (anisotropic) phases are not available with gamma_s
 GENERAL_SLAB_ERROR = "general (anisotropic) phases are not available on slab-decomposed solvers"
 
 
+# law="aniso" (heat / porous): in the wording of the solver library (Solver::set_phase_conductivity)
+ANISO_SLAB_ERROR = "aniso (3 x 3 conductivity) phases are not available on slab-decomposed solvers"
+
+
+def aniso_conductivity(attrs, evaluate=float):
+    """MatrixLinearAnisotropicMaterialLaw::readSettings  F:11097-11105: the six attributes c11 c22 c33 c23 c13 c12 of the
+    symmetric 3x3 matrix, defaults 1, 1, 1, 0, 0, 0 (F:11094).  Only these six names are read (c21, c31, c32 are not).
+    Returns the six numbers in that order."""
+    defaults = (("c11", 1.0), ("c22", 1.0), ("c33", 1.0), ("c23", 0.0), ("c13", 0.0), ("c12", 0.0))
+    return [evaluate(attrs[k]) if k in attrs else d for k, d in defaults]
+
+
 def general_stiffness(attrs, evaluate=float):
     """LinearGeneralMaterialLaw::readSettings  F:11240-11245 = read_matrix(attr, C, "c", true)  F:1101-1119 on Voigt::Id4(6)
     F:501-512 (diag 1, 1, 1, 0.5, 0.5, 0.5 -- not the plain identity): i, j row-major, every attribute c<i><j> found sets (i, j)

@@ -33,6 +33,18 @@ def _dp(a):
     return a.ctypes.data_as(_lib.c_double_p)
 
 
+def conductivity6(K):
+    """six numbers (11, 22, 33, 23, 13, 12) or a symmetric 3x3 -> the six doubles fg_set_phase_conductivity takes"""
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape == (3, 3):
+        if not np.array_equal(K, K.T):
+            raise ValueError("the conductivity must be symmetric")
+        K = np.array([K[0, 0], K[1, 1], K[2, 2], K[1, 2], K[0, 2], K[0, 1]])
+    if K.shape != (6,):
+        raise ValueError("the conductivity must be six numbers (11, 22, 33, 23, 13, 12) or a symmetric 3x3")
+    return np.ascontiguousarray(K)
+
+
 class LSSolver:
     def __init__(self, nx, ny, nz, dx=1.0, dy=1.0, dz=1.0, device=0):
         self._lib = _lib.load()
@@ -88,6 +100,15 @@ class LSSolver:
             raise ValueError("the stiffness must be 6x6")
         self._check(self._lib.fg_set_phase_stiffness(self._h, int(p), _dp(C)))
 
+    def set_phase_conductivity(self, p, K, phi=None):
+        """fg_set_phase_conductivity (MatrixLinearAnisotropicMaterialLaw F:11089-11156), heat / porous mode: phase p gets the
+        constant symmetric conductivity / permeability K -- six numbers c11 c22 c33 c23 c13 c12, or a symmetric 3x3 -- and,
+        with phi, its field.  Set the mode first.  A later set_phase(p, mu, lam) makes the phase isotropic again."""
+        c6 = conductivity6(K)
+        if phi is not None:
+            self.set_phase(p, 0.0, 0.0, phi)
+        self._check(self._lib.fg_set_phase_conductivity(self._h, int(p), _dp(c6)))
+
     def set_phase_fine(self, p, phi):
         """gamma_scheme full_staggered: phase p's fractions on the doubly fine grid, shape (2nx, 2ny, 2nz)."""
         phi = np.ascontiguousarray(phi, dtype=np.float64)
@@ -142,7 +163,7 @@ class LSSolver:
                 if v not in kinds:
                     raise RuntimeError("Unknown error estimator '%s'" % v)
                 self._check(self._lib.fg_set_option_i(self._h, b"error_estimator", kinds[v]))
-            elif k in ("u_loop", "fuse_x", "cg_fused", "fuse_stress_div", "u_tile", "x_layout", "plane_fft", "slab_split", "slab_interleave", "slab_loopback", "laminate_overlap", "phi_sweep", "aniso_tile", "pair_chunk", "joint_x", "fft_images", "bluestein", "tile_plans", "staged_copy", "stage_chunk_kb"):
+            elif k in ("u_loop", "fuse_x", "cg_fused", "fuse_stress_div", "u_tile", "x_layout", "plane_fft", "slab_split", "slab_interleave", "slab_loopback", "laminate_overlap", "phi_sweep", "aniso_tile", "aniso_sc_tile", "pair_chunk", "joint_x", "fft_images", "bluestein", "tile_plans", "staged_copy", "stage_chunk_kb"):
                 self._check(self._lib.fg_set_option_i(self._h, k.encode(), int(v)))
             elif k in ("maxiter", "loadstep_extrapolation_order"):
                 self._check(self._lib.fg_set_option_i(self._h, k.encode(), int(v)))
@@ -213,7 +234,7 @@ class LSSolver:
         is transformed: 0 length 1, 1 power of two, 2 sub-lines p * 2^k, 3 tile kernels, 4 Bluestein, 5 O(n^2)),
         "fft_bluestein_m_x|y|z" (padded length of the axis' Bluestein pass, 0 = not on Bluestein), "phase_uploads" (host
         arrays received by set_phase / set_phase_fine / set_normals), "u_tile_aniso" (launches of the tiled sweep's anisotropic
-        form); -1 = unknown name."""
+        form), "sc_tile_aniso" (launches of the tiled scalar sweep's aniso form); -1 = unknown name."""
         return int(self._lib.fg_get_counter(self._h, name.encode()))
 
     def iterate(self, E, n):

@@ -76,6 +76,20 @@ int fg_set_phase(fg_solver* s, int p, double mu, double lambda, const double* ph
  * Voigt tangent ("General phases").  Two complementary phases run the displacement loop on the tiled sweep's
  * anisotropic form (option aniso_tile); everything else runs the strain-state pass and the strain-space CG. */
 int fg_set_phase_stiffness(fg_solver* s, int p, const double* C /* [6][6] */);
+/* Law "aniso" of the modes heat / porous, MatrixLinearAnisotropicMaterialLaw F:11089-11156: phase p gets the constant symmetric
+ * 3 x 3 conductivity / permeability K, six doubles in the order 11, 22, 33, 23, 13, 12 (the reference's attributes c11 c22 c33
+ * c23 c13 c12), and is an aniso phase until a later fg_set_phase(p, mu, ...) makes it isotropic again.  PK1 F:11114-11128:
+ * q_c = alpha (K_c0 g_0 + K_c1 g_1 + K_c2 g_2), evaluated per voxel index on the three stored gradient components, so the
+ * divergence of the flux is a 13-point stencil on the potential ("Aniso phases of the scalar modes").  Iso and
+ * aniso phases mix (Voigt).  FG_ERROR with "phase conductivity is not finite" for a NaN / Inf entry, "aniso (3 x 3
+ * conductivity) phases are available in heat / porous mode only" on a solver whose mode is not 1 (set the mode first), "...
+ * are not available on slab-decomposed solvers" on a slab, "phase index out of range" for a bad p.  Methods basic and cg,
+ * estimators epsilon and residual, mixed boundary conditions with method basic, load steps, one GPU.  Two complementary
+ * phases run the potential loop (basic, and cg with the direction inside the sweep) on the tiled sweep's aniso form (option
+ * aniso_sc_tile, counter "sc_tile_aniso"); everything else -- three or more phases, other fractions, mixed boundary conditions,
+ * grids the tiles do not fit, u_loop < 2 -- runs the exact-order 13-point sweep.  The reference-material scan diagonalises every
+ * voxel's 3 x 3 Voigt tangent. */
+int fg_set_phase_conductivity(fg_solver* s, int p, const double* c6 /* 11 22 33 23 13 12 */);
 /* gamma_scheme 2: phase p's fractions on the doubly fine grid, [2nx][2ny][2nz] over the same box (initPhi after
  * select_dfg(true) F:17152-17230, normalised there).  The image is reduced on the device to the coarse field (the 8-cell
  * means of F:17180-17228, what "phi" returns) and to the three shear-group fractions, and is not kept.  A phase given through
@@ -125,7 +139,9 @@ int fg_set_normals(fg_solver* s, const double* normals /* [3][nx][ny][nz] */);
  * phi_sweep (1 = default: with two phases whose fractions are complementary bit for bit the tiled sweep reads phi_1 and
  * forms the effective moduli itself; 0 = always the two precomputed moduli arrays), aniso_tile (1 = default: two complementary
  * phases with a general phase -- fg_set_phase_stiffness -- run the displacement loop on the tiled sweep's 6 x 6 form where
- * u_tile, phi_sweep and the grid allow; 0 = the strain-state pass), laminate_overlap (1 = default: the interface kernels of the laminate correction run on a second stream beside the
+ * u_tile, phi_sweep and the grid allow; 0 = the strain-state pass), aniso_sc_tile (1 = default: heat / porous with two complementary
+ * phases of which one has law aniso -- fg_set_phase_conductivity -- run the tiled sweep's aniso form where u_loop, u_tile, phi_sweep
+ * and the grid allow; 0 = the exact-order 13-point sweep), laminate_overlap (1 = default: the interface kernels of the laminate correction run on a second stream beside the
  * displacement sweep; 0 = one stream), slab_split (slab driver: 1 = one all-to-all per component, overlapping the transforms of the next component; 0 = one
  * exchange for the three components; -1 = by slab size, default), slab_interleave (-1 = default: in the one-exchange mode a
  * peer's three components travel as ONE message where the sizes allow; 0 = one message per peer and component),
@@ -227,7 +243,8 @@ int fg_get_stage_timing_bias(const fg_solver* s, double* ms);
  * "fft_bluestein_m_x" / "_y" / "_z" = the padded length of the axis' Bluestein pass (0: the axis is not on Bluestein);
  * "phase_uploads" = host arrays this solver has received through fg_set_phase (with a field), fg_set_phase_field_fine and
  * fg_set_normals (fg_voxelize_into adds none); "u_tile_aniso" = launches of the tiled sweep's anisotropic form (general
- * phases, option aniso_tile).  Unknown names give -1. */
+ * phases, option aniso_tile); "sc_tile_aniso" = launches of the tiled scalar sweep's aniso form (heat / porous, option
+ * aniso_sc_tile).  Unknown names give -1. */
 long fg_get_counter(const fg_solver* s, const char* name);
 
 /* Measurement helper (no counterpart in the reference): achieved HBM bandwidth of a streaming copy a = b and of the
