@@ -6,6 +6,7 @@ strains, the factor 2 in the product.
 
   general6            PK1 F:11254-11272 in its operation order
   pk1_voigt_general   VoigtMixedMaterialLaw::PK1 F:12752-12761 over mixed isotropic / general phases
+  energy_general      W F:11247-11252; energy_voigt_general: VoigtMixedMaterialLaw::W F:12739-12750 over mixed phases
   scan_matrix         the matrix eig() hands dsyev (F:12518-12522): dPK1 of the identity rows, read through its upper triangle
   GeneralLSOracle     LSOracle with these two; the scan takes numpy.linalg.eigvalsh per voxel
 """
@@ -15,7 +16,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from oracle.ls_oracle import VOIGT_THRESHOLD, LSOracle, hooke
+from oracle.ls_oracle import VOIGT_THRESHOLD, LSOracle, energy_hooke, hooke
 
 
 def is_general(mat):
@@ -73,6 +74,24 @@ def voigt_tangent_matrices(phis, mats):
     return A
 
 
+def energy_general(E, C):
+    """LinearGeneralMaterialLaw::W  F:11247-11252: 0.5 * S.dot(E) with S = PK1(E, 1) and SymTensor3x3::dot F:9414-9417 (shear
+    products doubled)"""
+    S = general6(E, C, 1.0)
+    return 0.5 * (S[0] * E[0] + S[1] * E[1] + S[2] * E[2] + 2 * (S[3] * E[3] + S[4] * E[4] + S[5] * E[5]))
+
+
+def energy_voigt_general(eps, phis, mats):
+    """oracle.ls_oracle.energy_voigt with a per-phase law (VoigtMixedMaterialLaw::W F:12739-12750: W += phi_p * W_p from zero,
+    phases with phi <= 10 eps skipped)"""
+    W = np.zeros(eps.shape[1:])
+    for phi, mat in zip(phis, mats):
+        use = phi > VOIGT_THRESHOLD
+        Wp = energy_general(eps, np.asarray(mat)) if is_general(mat) else energy_hooke(eps, mat[0], mat[1])
+        W = np.where(use, W + phi * Wp, W)
+    return W
+
+
 @dataclass
 class GeneralLSOracle(LSOracle):
     """LSOracle whose materials may be 6x6 stiffnesses (Voigt mixing)"""
@@ -81,6 +100,13 @@ class GeneralLSOracle(LSOracle):
         if self.mixing_rule != "voigt":
             raise RuntimeError("general phases support Voigt mixing only")
         return pk1_voigt_general(eps, self.phis, self.mats, alpha)
+
+    def mean_energy(self, eps=None):
+        """meanW  F:12239-12262 over the Voigt rule's W with a per-phase law"""
+        if self.mixing_rule != "voigt":
+            raise RuntimeError("general phases support Voigt mixing only")
+        eps = self.eps if eps is None else eps
+        return float(energy_voigt_general(eps, self.phis, self.mats).sum()) / self.N
 
     def tangent_eig_minmax(self):
         if not any(is_general(m) for m in self.mats):

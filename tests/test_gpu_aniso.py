@@ -9,6 +9,7 @@ import pytest
 
 from aniso_reference import AnisoScalarOracle, FixedRefOracle, check_laminate, k6, layer_problem, random_spd3, voigt_tangent3
 from helpers import rel_err, sphere_phi
+from test_gpu_fuzz import smooth_field
 
 pytestmark = pytest.mark.gpu
 
@@ -74,6 +75,56 @@ def test_aniso_run_matches_reference(grid, dims, u_loop):
     s.iterate(E3, 2)
     g2 = o.basic_scheme(E3, o.basic_scheme(E3, o.eps))
     assert rel_err(s.get_field("epsilon"), g2) < 1e-10
+    s.close()
+
+
+SHORT_GRIDS = [(1, 7, 5), (2, 7, 5), (6, 1, 5), (6, 2, 5), (6, 5, 1), (6, 5, 2), (2, 2, 2), (1, 1, 8), (1, 16, 1)]
+_short_oracles = {}
+
+
+def short_axis_phi(grid):
+    """the sphere, or a smooth random field where the sphere's fraction is the same in every voxel of the grid"""
+    phi1 = sphere_phi(grid, 0.3)
+    if phi1.min() == phi1.max():
+        phi1 = smooth_field(np.random.default_rng(5), grid)
+    assert 0.0 <= phi1.min() < phi1.max() <= 1.0
+    return phi1
+
+
+@pytest.mark.parametrize("grid", SHORT_GRIDS)
+@pytest.mark.parametrize("u_loop", [1, 2])
+@pytest.mark.parametrize("method", ["basic", "cg"])
+def test_aniso_short_axes(grid, u_loop, method):
+    """axes of length 1 and 2: the 13-point stencil (k_sc_sweep_aniso, u_loop 1 and 2 alike for aniso phases off the tiled grids)
+    wraps +-1 in two directions at once, and both neighbours along such an axis are the voxel itself (length 1) or one and the
+    same voxel (length 2).  Against the restatement at the bars of test_aniso_run_matches_reference, for method basic and cg."""
+    dims = (2.0, 1.0, 0.5)
+    phi1 = short_axis_phi(grid)
+    mats, phis = two_K(), [1 - phi1, phi1]
+    s = _solver(grid, mats, phis, dims, tol=1e-9, u_loop=u_loop, method=method)
+    assert s.run(E3) is False
+    assert s.counter("sc_tile_aniso") == 0
+    mu_0 = s.ref_material[0]
+    assert abs(mu_0 - eig_mu0(phis, mats)) <= 1e-13 * mu_0
+    key = (grid, method, mu_0)
+    if key not in _short_oracles:     # one restatement run for both u_loop values (left unchanged)
+        o = _oracle(FixedRefOracle, grid, mats, phis, dims, tol=1e-9, mu_0=mu_0)
+        assert (o.run_cg(E3) if method == "cg" else o.run(E3)) is False
+        _short_oracles[key] = o
+    o = _short_oracles[key]
+    g, T, To = s.get_field("epsilon"), s.get_field("u"), o.potential()
+    print("short axes", grid, u_loop, method, "iterations", s.iterations, o.iterations, "residuals",
+          np.abs(np.array(s.residuals) - np.array(o.residuals)).max() if s.iterations == o.iterations else None,
+          "gradient", rel_err(g, o.eps), "flux", rel_err(s.get_field("sigma"), o.pk1(o.eps)),
+          "mean flux", rel_err(s.mean_stress(), o.mean_stress()), "potential", np.abs(T[0] - To).max())
+    assert s.iterations == o.iterations and o.iterations < 10000
+    np.testing.assert_allclose(s.residuals, o.residuals, rtol=0, atol=1e-11)
+    assert g.shape == (3,) + grid
+    assert rel_err(g, o.eps) < 1e-10
+    assert rel_err(s.get_field("sigma"), o.pk1(o.eps)) < 1e-10
+    assert rel_err(s.mean_stress(), o.mean_stress()) < 1e-11
+    np.testing.assert_allclose(s.mean_strain(), E3, atol=1e-12)
+    assert T.shape == (1,) + grid and np.abs(T[0] - To).max() < 1e-10 * max(1.0, np.abs(To).max())
     s.close()
 
 
