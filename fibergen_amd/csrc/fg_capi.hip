@@ -304,7 +304,8 @@ int fg_set_option_i(fg_solver* s, const char* key, long value) {
     }
     else if (k == "u_loop") o.u_loop = (int)value;
     else if (k == "method") {
-      if (value != 0 && value != 1) throw std::runtime_error("Unknown solver method");
+      if (value != 0 && value != 1 && value != 2) throw std::runtime_error("Unknown solver method");
+      if (value == 2 && v.is_slab()) throw std::runtime_error("method polarization is not available on slab-decomposed solvers");
       o.method = (int)value;
     }
     else if (k == "fuse_stress_div") o.fuse_stress_div = value != 0;

@@ -166,12 +166,21 @@ void launch_add_small(double* out, const double* in, int n, hipStream_t s);
 void launch_div(const Grid& g, const FieldPtrs<6>& tau, const FieldPtrs<3>& f, const XHalo& h, hipStream_t s);
 void launch_g0(const Grid& g, const FieldPtrs<3>& fh, const G0Tables& tb, double c10, double c20, const G0Layout& lay,
                hipStream_t s);
+// mean6 != nullptr (method polarization): the zero frequency becomes E + mcoef * mean6[c] for a device-resident mean6, as in
+// launch_gamma_willot; a kernel instantiation of its own, the one every other call takes is unchanged
 void launch_gamma_collocated(const Grid& g, const FieldPtrs<6>& th, const XiTables& xt, double c10, double c20, double beta,
-                             const Vec6& E, hipStream_t s);
+                             const Vec6& E, hipStream_t s, const double* mean6 = nullptr, double mcoef = 0.0);
 // gamma_scheme willot (fg_kernels_willot.hip): eta_hat = alpha Gamma_hat : tau_hat + beta tau_hat in place, lambda_0 = infinity
 // selects the Stokes form; zero frequency = E (+ mcoef * mean6[c] for a device-resident mean6, else mean6 = nullptr)
 void launch_gamma_willot(const Grid& g, const FieldPtrs<6>& th, const WillotTables& wt, double mu_0, double lambda_0,
                          double alpha, double beta, const Vec6& E, const double* mean6, double mcoef, hipStream_t s);
+// method polarization (fg_kernels_polar.hip).  launch_polarize: calcPolarization F:18044-18131 per voxel (polarize_voxel),
+// out = Q(in), or with inv the strain (C + C0)^-1 in (out may be in); !inv: out7 = the six sums of Q and the number of voxels
+// that took the 6 x 6 solve.  launch_polar_back (staggered): P = Q + (P0 + sym grad_h u), sumsq6 = sums of squares of P.
+void launch_polarize(const Grid& g, const PhaseTable& pt, double mu_0, bool inv, const FieldPtrs<6>& in,
+                     const FieldPtrs<kMaxPhases>& phi, const FieldPtrs<6>& out, double* partial, double* out7, hipStream_t s);
+void launch_polar_back(const Grid& g, const FieldPtrs<3>& u, const FieldPtrs<6>& Q, const FieldPtrs<6>& P, const Vec6& P0,
+                       double* partial, double* sumsq6, hipStream_t s);
 void launch_eps_norm(const Grid& g, const FieldPtrs<3>& u, const FieldPtrs<6>& eps, const Vec6& E, const Vec6& R,
                      bool add_R, double* partial, double* sumsq6, const XHalo& h, hipStream_t s);
 // viscosity: eta = (E - coef tau_sum / nvox) + sym grad u + coef tau, sums of squares (tau_sum on the device)

@@ -454,8 +454,10 @@ __global__ __launch_bounds__(kBlock) void k_g0(Grid g, FieldPtrs<3> fh, G0Tables
 // GammaOperatorFourierCollocated  F:19381-19608 (freq_hack off): per frequency the real symmetric 6x6
 // Gamma0_hat built from xi = m/d (F:19434-19456), eta_hat_i = sum_j g_ij tau_hat_j (x2 for the shear columns)
 // + beta tau_hat_i, in place on the six complex components; the zero frequency is set to E (F:19605-19607).
+// MEAN (method polarization, F:20553): the zero frequency is E + mcoef * mean6[c] with mean6 on the device.
+template <bool MEAN>
 __global__ __launch_bounds__(kBlock) void k_gamma_collocated(Grid g, FieldPtrs<6> th, XiTables xt, double c10, double c20,
-                                                             double beta, Vec6 E) {
+                                                             double beta, Vec6 E, const double* mean6, double mcoef) {
   const long nfreq = (long)g.nx * g.ny * g.nzc;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < nfreq; idx += (long)gridDim.x * blockDim.x) {
     const long row = idx / g.nzc;
@@ -469,7 +471,7 @@ __global__ __launch_bounds__(kBlock) void k_gamma_collocated(Grid g, FieldPtrs<6
     cplx ey[6];
     if (ii == 0 && jj == 0 && kk == 0) {
 #pragma unroll
-      for (int c = 0; c < 6; ++c) ey[c] = cmake(E.v[c], 0.0);
+      for (int c = 0; c < 6; ++c) ey[c] = cmake(MEAN ? E.v[c] + mcoef * mean6[c] : E.v[c], 0.0);
     } else {
       const double xi0 = xt.xi[0][ii], xi1 = xt.xi[1][jj], xi2 = xt.xi[2][kk];
       const double xi00 = xi0 * xi0, xi01 = xi0 * xi1, xi11 = xi1 * xi1;
@@ -1724,9 +1726,11 @@ void launch_g0(const Grid& g, const FieldPtrs<3>& fh, const G0Tables& tb, double
 }
 
 void launch_gamma_collocated(const Grid& g, const FieldPtrs<6>& th, const XiTables& xt, double c10, double c20, double beta,
-                             const Vec6& E, hipStream_t s) {
+                             const Vec6& E, hipStream_t s, const double* mean6, double mcoef) {
   const long nfreq = (long)g.nx * g.ny * g.nzc;
-  hipLaunchKernelGGL(k_gamma_collocated, dim3(grid_for(nfreq, 1 << 20)), dim3(kBlock), 0, s, g, th, xt, c10, c20, beta, E);
+  const dim3 nb(grid_for(nfreq, 1 << 20));
+  if (mean6) hipLaunchKernelGGL(k_gamma_collocated<true>, nb, dim3(kBlock), 0, s, g, th, xt, c10, c20, beta, E, mean6, mcoef);
+  else hipLaunchKernelGGL(k_gamma_collocated<false>, nb, dim3(kBlock), 0, s, g, th, xt, c10, c20, beta, E, mean6, mcoef);
   FG_HIP_CHECK(hipGetLastError());
 }
 

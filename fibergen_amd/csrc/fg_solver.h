@@ -41,7 +41,8 @@ constexpr int kSlotScratch = 16; // 6: sums nobody reads (strain materialisation
 constexpr int kSlotFlag = 22;    // 2: slab driver, summed over the ranks with every reduction: [0] ranks whose device error flag
                                  // is raised, [1] ranks that were asked to stop (fg_cancel)
 constexpr int kSlotCg = 24;      // displacement CG: two blocks of 8 (norms of eps [6] + r:r, alternating per iteration), then p:(p-w) [8]
-constexpr int kNumSlots = 48;
+constexpr int kSlotPolar = 48;   // method polarization: sums of Q [6], voxels that took the 6 x 6 solve [1] (24..47 are the CG loops')
+constexpr int kNumSlots = 56;
 }  // namespace slots
 
 inline double now_seconds() {
@@ -78,7 +79,15 @@ struct SolverOptions {
   int error_estimator = 0;      // 0 = epsilon (EpsilonErrorEstimator F:14591-14637), 1 = residual (ResidualErrorEstimator
                                 // F:14382-14405: abs = sqrt(gamma), rel = sqrt(gamma / gamma_0); method cg only),
                                 // 2 = sigma (F:14514-14587), 3 = energy (F:14410-14468), 4 = none (F:14370-14378)
-  int method = 0;               // 0 = basic scheme (runBasic F:21716), 1 = conjugate gradients (runCGElasticity F:23153)
+  int method = 0;               // 0 = basic scheme (runBasic F:21716), 1 = conjugate gradients (runCGElasticity F:23153),
+                                // 2 = polarization: the Eyre-Milton scheme (runPolarization F:21808-21851, polarizationScheme
+                                // F:20536-20554, calcPolarization F:18044-18131); elasticity, Voigt mixing, iso / general phases,
+                                // pure-strain boundary conditions, estimators epsilon / none, one GPU; gamma_scheme collocated and
+                                // willot follow the reference to the operation.  gamma_scheme staggered is a STATED DEVIATION: the
+                                // reference's GammaOperatorStaggered F:20288-20300 takes beta and drops it (P <- mean - 4 mu_0
+                                // grad_s G0 div Q without the + Q, which is not Eyre-Milton's iteration and does not converge to the
+                                // cell problem's solution); here P <- Q - 4 mu_0 grad_s_h G0 div_h Q with its mean set to P00 + P0
+                                // 
   int u_loop = 2;               // pure strain BC: displacement-based pass (0 off, 1 exact operation order: bit-identical
                                 // to 0, 2 precomputed effective moduli + FMA, agrees with 1 to rounding; with laminate
                                 // mixing 2 = the Voigt sweep + divergence of (tau_laminate - tau_voigt) at the interface)
@@ -232,7 +241,8 @@ class Solver {
   double event_bias_ms() const { return event_bias_ms_; }
   // fg_get_counter: "interface_voxels" / "affected_voxels" = lengths of the laminate correction's lists (0 before they are
   // built); "sc_tile_aniso" = launches of k_sc_tile_aniso; "phase_uploads" = host arrays received by set_phase_field / set_phase_field_fine / set_normals; "u_tile_aniso" =
-  // launches of the tiled sweep's anisotropic form; -1 = unknown name
+  // launches of the tiled sweep's anisotropic form; "polarization_generic_voxels" = voxels that took the 6 x 6 solve in the last
+  // forward launch of the polarisation kernel (waits for the stream); -1 = unknown name
   long counter(const std::string& name) const;
 
  private:
@@ -270,6 +280,13 @@ class Solver {
   void sc_aniso_constants(double* K0, double* K1) const;   // the six constants of phases 0 and 1 (isotropic: mu on the diagonal)
   bool two_phase_complementary(bool scalar = false);       // phi_0 == 1 - phi_1 everywhere (checked once per geometry)
   void general_check() const;           // throws for the combinations general phases do not cover
+  // method polarization (fg_solver.hip, "the polarisation loop")
+  void polar_check() const;             // throws for the combinations the method does not cover, each naming the option
+  void polar_start(const double* E6);   // P = 4 mu_0 E, the constant field the loop starts from  F:21828
+  void polar_pass(const double* E6);    // one polarizationScheme call on the state P held in eps_
+  void polar_to_strain();               // calcPolarization(..., inv = true)  F:21850: eps_ <- (C + C0)^-1 P
+  void polar_settle();                  // before the phases change: a held polarisation state becomes the strain of the phases it was built with
+  bool run_polarization(const double* E0, const double* S0, double prev0);
   bool aniso_tile_ok();                 // general phases: the displacement loop has a sweep for this problem (k_u_tile ANISO)
   FieldPtrs<2> effective_moduli();      // per-voxel sums of the phase moduli for the fast kernels (allocated on first use)
   bool dfg() const { return opt_.gamma_scheme == 2; }
@@ -445,6 +462,8 @@ class Solver {
 
   bool u_valid_ = false;    // fu_ holds the displacement belonging to the current strain state
   bool eps_stale_ = false;  // eps_ has not been written since fu_ changed
+  bool pol_state_ = false;  // method polarization: eps_ holds the polarisation P, not the strain (ensure_eps converts it)
+  double pol_mu0_ = 0.0;    // the mu_0 that state was built with: the conversion uses it, a pass on another one starts afresh
   bool in_run_ = false;
   bool fresh_step_ = true;   // the load step being run starts from the zeroed field (not from a previous step)
   bool cg_u_active_ = false;  // displacement-space CG is iterating: fu_ is the iterate u_e, fu_alt_ is free between steps

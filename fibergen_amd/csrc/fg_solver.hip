@@ -236,6 +236,7 @@ void Solver::release() {
 // ------------------------------------------------------------------ configuration
 void Solver::set_num_phases(int n) {
   if (n < 1 || n > kMaxPhases) throw std::runtime_error("number of phases must be in [1, 8]");
+  polar_settle();
   FG_HIP_CHECK(hipSetDevice(device_));
   if (phi_) FG_HIP_CHECK(hipFree(phi_));
   phi_ = nullptr;
@@ -258,6 +259,7 @@ void Solver::set_num_phases(int n) {
 
 void Solver::set_phase_material(int p, double mu, double lambda) {
   if (p < 0 || p >= pt_.n) throw std::runtime_error("phase index out of range");
+  polar_settle();
   mod_dirty_ = mod5_dirty_ = true;
   smod_dirty_ = mod5_dirty_ = true;
   complement_dirty_ = true;
@@ -280,6 +282,7 @@ void Solver::set_phase_stiffness(int p, const double* C36) {
   for (int i = 0; i < 6; ++i)
     for (int j = i + 1; j < 6; ++j)
       if (std::fabs(C36[6 * i + j] - C36[6 * j + i]) > 1e-12 * cmax) throw std::runtime_error("phase stiffness is not symmetric");
+  polar_settle();
   invalidate_moduli();
   mixed_dirty_ = true;
   for (int i = 0; i < 36; ++i) pt_.C[p][i] = C36[i];
@@ -313,6 +316,7 @@ bool Solver::aniso_phase() const {
 
 void Solver::set_phase_field(int p, const double* phi_host) {
   if (p < 0 || p >= pt_.n) throw std::runtime_error("phase index out of range");
+  polar_settle();
   mod_dirty_ = mod5_dirty_ = true;
   smod_dirty_ = mod5_dirty_ = true;
   complement_dirty_ = true;
@@ -674,6 +678,13 @@ long Solver::counter(const std::string& name) const {
   if (name == "phase_uploads") return phase_uploads_;
   if (name == "u_tile_aniso") return u_tile_aniso_;
   if (name == "sc_tile_aniso") return sc_tile_aniso_;
+  if (name == "polarization_generic_voxels") {   // left on the device by the last forward launch of k_polarize
+    double v = 0.0;
+    FG_HIP_CHECK(hipSetDevice(device_));
+    FG_HIP_CHECK(hipStreamSynchronize(stream_));
+    FG_HIP_CHECK(hipMemcpy(&v, dscal_ + kSlotPolar + 6, sizeof(double), hipMemcpyDeviceToHost));
+    return (long)v;
+  }
   if (name == "pair_chunk_planes") return (long)pair_chunk_planes(opt_.mode == 1 ? 1 : 3);
   return -1;
 }
@@ -1540,6 +1551,7 @@ void Solver::u_pass_back() {
 }
 
 void Solver::ensure_eps() {
+  if (pol_state_) polar_to_strain();   // method polarization left P in eps_
   if (slab_layout_ && su_valid_ && eps_stale_) {   // slab driver: the state is su_[cur] with its halo planes
     slab_materialise_eps();
     return;
@@ -1563,6 +1575,14 @@ void Solver::iterate(const double* E6, int n) {
   if (willot()) willot_check();
   general_check();
   int i = 0;
+  if (opt_.method == 2) {   // the polarisation loop: from P = 4 mu_0 E unless a polarisation state is there already
+    polar_check();
+    if (pol_state_ && opt_.mu_0 != pol_mu0_) ensure_eps();   // the reference material changed: that state is of another operator
+    if (!pol_state_) polar_start(E6);
+    for (; i < n; ++i) polar_pass(E6);
+    return;
+  }
+  ensure_eps();   // a polarisation state left by method polarization becomes the strain before another method iterates on it
   if (u_loop_eligible()) {
     if (!u_valid_ && n > 0 && opt_.mode == 1) {
       // no potential yet: the zero gradient field is E = 0, T = 0
@@ -1689,7 +1709,8 @@ void Solver::calc_ref_material() {
   check_device_error("reference material");
   double lambda_min = hscal_[kSlotMinMax], lambda_max = -hscal_[kSlotMinMax + 1];
   if (lambda_min < 0) lambda_min = 0;  // F:12183-12223
-  double mu_0 = 0.5 * (lambda_min + lambda_max);
+  double mu_0 = opt_.method == 2 ? std::sqrt(lambda_min * lambda_max)   // getRefMaterial(..., polarization)  F:12227-12229
+                                 : 0.5 * (lambda_min + lambda_max);
   mu_0 *= 0.5 * opt_.ref_scale;
   opt_.mu_0 = mu_0;
   recompute_bc();  // F:22312
@@ -1837,6 +1858,7 @@ bool Solver::run_load_steps(const double* E6, const double* S6, const double* pa
     if (norm2(t, 6) > se * norm2(Emax, 6)) throw std::runtime_error("Incompatible strain boundary condition specified");
   }
   FG_HIP_CHECK(hipMemsetAsync(eps_, 0, 6 * (size_t)g_.n * sizeof(double), stream_));  // F:21379
+  pol_state_ = false;
   u_valid_ = false;
   eps_stale_ = false;
   // converged strain fields of the last steps (device copies, oldest first)  F:21586
@@ -1911,6 +1933,7 @@ bool Solver::run_one_step(const double* E0, const double* S0) {
   if (dfg()) dfg_check();
   if (willot()) willot_check();
   general_check();
+  if (opt_.method == 2) polar_check();
   // EpsilonErrorEstimator  F:14591-14637: constructed on the field the step starts from (zero for the first step)
   const double prev0 = fresh_step_ ? 0.0 : current_norm9();
   if (opt_.error_estimator >= 2) {
@@ -1922,6 +1945,7 @@ bool Solver::run_one_step(const double* E0, const double* S0) {
     return run_cg_scalar(E0, prev0);
   }
   if (opt_.method == 1) return run_cg(E0, S0, prev0);
+  if (opt_.method == 2) return run_polarization(E0, S0, prev0);
   if (opt_.error_estimator == 1)   // ErrorEstimator::update  F:14359
     throw std::runtime_error("Selected error estimator is not compatible with the selected solution method");
   const double t_start = now_seconds();
@@ -2014,6 +2038,127 @@ bool Solver::run_one_step(const double* E0, const double* S0) {
   in_run_ = false;
   iterations_ = iter;
   ensure_eps();
+  FG_HIP_CHECK(hipStreamSynchronize(stream_));
+  solve_time_ += now_seconds() - t_start;
+  return failed;
+}
+
+// ------------------------------------------------------------------ the polarisation loop
+// method "polarization": Eyre & Milton's scheme as runPolarization F:21808-21851 drives it.  The state is the polarisation
+// P = (C + C0) : eps with C0 = 2 mu_0 Id, held in eps_ (pol_state_); one pass is polarizationScheme F:20536-20554:
+//   Q = (C - C0)(C + C0)^-1 P per voxel,  P00 = <Q>,  P_hat = -4 mu_0 Gamma0_hat : Q_hat + Q_hat,  P_hat(0) = P00 + 4 mu_0 E.
+void Solver::polar_check() const {
+  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("method polarization is not available on slab-decomposed solvers");
+  if (opt_.mode != 0) throw std::runtime_error("method polarization is available in mode elasticity only (not heat / porous / viscosity)");
+  if (opt_.mixing != kMixVoigt) throw std::runtime_error("method polarization supports mixing_rule voigt only (not laminate)");
+  if (dfg()) throw std::runtime_error("method polarization is not available with gamma_scheme full_staggered / half_staggered");
+  if (opt_.error_estimator != 0 && opt_.error_estimator != 4)
+    throw std::runtime_error("method polarization supports error_estimator epsilon and none only (not sigma / energy / residual: "
+                             "the loop's field is the polarisation, not the strain)");
+  if (frobenius(BC_Q_) != 0.0)   // Q = Id - P != 0  <=>  |MQ| >= eps
+    throw std::runtime_error("method polarization supports pure-strain boundary conditions only (bc_projector = identity; the "
+                             "reference switches the mixed check off)");
+  if (opt_.bc_relax != 1.0) throw std::runtime_error("method polarization supports bc_relax = 1 only");
+}
+
+void Solver::polar_start(const double* E6) {
+  Vec6 P0;
+  for (int c = 0; c < 6; ++c) P0.v[c] = 4 * opt_.mu_0 * E6[c];
+  launch_set_const6(g_, ptrs6(eps_), P0, stream_);   // epsilon.setConstant(4 mu_0 E)  F:21828
+  pol_mu0_ = opt_.mu_0;
+  pol_state_ = true;
+  u_valid_ = false;
+  eps_stale_ = false;
+}
+
+void Solver::polar_pass(const double* E6) {
+  if (pt_.n < 1) throw std::runtime_error("No materials specified");
+  const double mu_0 = opt_.mu_0, alpha = -4 * mu_0;   // GammaOperator(P00 + P0, ..., -4 mu_0, 1)  F:20553
+  Vec6 P0;
+  for (int c = 0; c < 6; ++c) P0.v[c] = 4 * mu_0 * E6[c];   // F:21836
+  double* sums = dscal_ + kSlotPolar;
+  time_begin(0);
+  launch_polarize(g_, phase_table(), mu_0, false, ptrs6(eps_), phase_ptrs(), ptrs6(tau_), partial_, sums, stream_);
+  time_end(0);
+  if (opt_.gamma_scheme == 0) {
+    // the consistent staggered form (SolverOptions::method): u = -4 mu_0 G0 div_h Q, P = Q + sym grad_h u + P0; <Q> passes through
+    time_begin(1);
+    launch_div(g_, ptrs6(tau_), ptrs3(fu_), XHalo{{nullptr, nullptr}, {nullptr, nullptr}}, stream_);
+    time_end(1);
+    fft_g0_chain(fu_, alpha, nullptr, nullptr);   // (Q stays in tau_: no scratch for the x-contiguous layout)
+    time_begin(9);
+    launch_polar_back(g_, ptrs3(fu_), ptrs6(tau_), ptrs6(eps_), P0, partial_, dscal_ + kSlotSumSq, stream_);
+    time_end(9);
+  } else {
+    time_begin(2);
+    fft_->forward(tau_, 6, g_.n, 1 / (double)nglobal_);
+    time_end(2);
+    time_begin(5);
+    if (willot()) {
+      launch_gamma_willot(g_, ptrs6(tau_), willot_tables(), mu_0, opt_.lambda_0, alpha, 1.0, P0, sums, 1 / (double)nglobal_, stream_);
+    } else {
+      XiTables xt;
+      for (int a = 0; a < 3; ++a) xt.xi[a] = xi_[a];
+      const double c10 = alpha / (4 * mu_0);
+      const double c20 = -alpha / (mu_0 * (1 + mu_0 / (opt_.lambda_0 + mu_0)));
+      launch_gamma_collocated(g_, ptrs6(tau_), xt, c10, c20, 1.0, P0, stream_, sums, 1 / (double)nglobal_);
+    }
+    time_end(5);
+    time_begin(8);
+    fft_->inverse(tau_, 6, g_.n);
+    time_end(8);
+    time_begin(9);
+    launch_copy(tau_, eps_, 6 * g_.n, stream_);
+    launch_sum6(g_, ptrs6(eps_), true, partial_, dscal_ + kSlotSumSq, stream_);
+    time_end(9);
+  }
+  if (timing_) times_.count++;
+  pol_state_ = true;
+  u_valid_ = false;
+  eps_stale_ = false;
+  for (int c = 0; c < 6; ++c) E_cur_[c] = E6[c];
+}
+
+void Solver::polar_settle() {
+  if (!pol_state_) return;
+  FG_HIP_CHECK(hipSetDevice(device_));
+  polar_to_strain();
+}
+
+void Solver::polar_to_strain() {
+  launch_polarize(g_, phase_table(), pol_mu0_, true, ptrs6(eps_), phase_ptrs(), ptrs6(eps_), partial_, nullptr, stream_);
+  pol_state_ = false;
+  u_valid_ = false;
+  eps_stale_ = false;
+}
+
+// runPolarization  F:21808-21851 for one load step.  The estimator watches the polarisation field (ee->update() on it), the
+// boundary-condition check is off (check_bc = false F:21819).  The reference never advances its iteration counter in this loop
+// (so its maxiter cannot end it); here the counter runs like in every other loop.
+bool Solver::run_polarization(const double* E0, const double* S0, double prev0) {
+  const double t_start = now_seconds();
+  for (int i = 0; i < 6; ++i) F00_[i] = 0.0;
+  if (opt_.update_ref != 0) calc_ref_material();   // F:21823-21825
+  double E[6];
+  bc_mean(BC_QC0_, BC_M_, opt_.bc_relax, E0, S0, E);   // F:21826
+  polar_start(E);
+  pending_back_ = back_ready_ = false;
+  in_run_ = true;
+  StopRule rule = stop_rule(prev0);
+  long iter = 1;
+  bool failed = false;
+  for (;;) {
+    polar_pass(E);
+    fetch_norms_and_errors("polarization");
+    for (int c = 0; c < 6; ++c) sumsq_[c] = hscal_[kSlotSumSq + c];
+    rule.measure(norm9_of_sums(sumsq_, (double)nglobal_));
+    if (opt_.error_estimator >= 2) estimator_update(&rule.abs_err, &rule.rel_err);   // none
+    if (converged(rule, iter, [] { return true; }, &failed)) break;
+    iter++;
+  }
+  in_run_ = false;
+  iterations_ = iter;
+  ensure_eps();   // calcPolarization(..., inv = true)  F:21850
   FG_HIP_CHECK(hipStreamSynchronize(stream_));
   solve_time_ += now_seconds() - t_start;
   return failed;
@@ -2407,7 +2552,7 @@ int Solver::field_components(const std::string& name) const {
     if (name == "sumsq") return 6;
     return 0;
   }
-  if (name == "epsilon" || name == "sigma" || name == "tau") return 6;
+  if (name == "epsilon" || name == "sigma" || name == "tau" || name == "polarization") return 6;
   if (name == "u" || name == "f" || name == "normals") return 3;
   if (name == "f_hat") return 3;
   if (name == "phi") return pt_.n;
@@ -2417,6 +2562,7 @@ int Solver::field_components(const std::string& name) const {
 
 double* Solver::device_component(const std::string& name, int c) {
   if (name == "epsilon" && c >= 0 && c < 6) return eps_ + (long)c * g_.n;
+  if (name == "polarization" && pol_state_ && c >= 0 && c < 6) return eps_ + (long)c * g_.n;   // the state of method polarization
   if (name == "tau" && c >= 0 && c < 6) return tau_ + (long)c * g_.n;
   if ((name == "f" || name == "u" || name == "f_hat") && c >= 0 && c < 3) return fu_ + (long)c * g_.n;
   if (name == "phi" && c >= 0 && c < pt_.n) return phi_ + (long)c * g_.n;
@@ -2427,6 +2573,11 @@ double* Solver::device_component(const std::string& name, int c) {
 // get_raw_field  F:15396-15684 (epsilon, sigma, u, phi, normals) + raw stage buffers for the tests
 void Solver::get_field(const std::string& name, double* out) {
   FG_HIP_CHECK(hipSetDevice(device_));
+  if (name == "polarization" && opt_.mode != 1) {   // the raw state of method polarization between passes (fg_iterate); reading it keeps it
+    if (!pol_state_) throw std::runtime_error("field 'polarization' exists only while method polarization holds its state (after fg_iterate)");
+    download_unpadded(eps_, out, 6, g_.n);
+    return;
+  }
   ensure_eps();
   // fu_ is overwritten by the displacement reconstruction (scalar modes: by an equivalent potential, still valid;
   // displacement-space CG: the reconstruction goes to the free buffer fu_alt_, fu_ is the iterate itself)

@@ -424,6 +424,121 @@ FG_HD void jacobi_minmax6(double (&A)[6][6], double* emin, double* emax) {
   *emax = hi;
 }
 
+// ---- method "polarization" (Eyre & Milton 1999; runPolarization F:21808-21851): the per-voxel map of calcPolarization
+// F:18044-18131 with C0 = 2 mu_0 Id (lambda_0 is not in it):  R = (C + C0)^-1 F,  and unless inv  Q = (C - C0) R.
+//
+// LinearIsotropicMaterialLaw::calcPolarization  F:11427-11467 in its operation order (P may not alias F)
+FG_HD void polarize_iso(const double* F, double mu, double lambda, double mu_0, bool inv, double* P) {
+  double m = 2.0 * (mu + mu_0);
+  const double a = 1.0 / m;
+  const double b = lambda / (m * (3.0 * lambda + m));
+  const double tr_F = F[0] + F[1] + F[2];
+  P[0] = a * F[0] - b * tr_F;
+  P[1] = a * F[1] - b * tr_F;
+  P[2] = a * F[2] - b * tr_F;
+  P[3] = a * F[3];
+  P[4] = a * F[4];
+  P[5] = a * F[5];
+  if (!inv) {
+    m = 2.0 * (mu - mu_0);
+    const double tr_P = P[0] + P[1] + P[2];
+    P[0] = m * P[0] + lambda * tr_P;
+    P[1] = m * P[1] + lambda * tr_P;
+    P[2] = m * P[2] + lambda * tr_P;
+    P[3] = m * P[3];
+    P[4] = m * P[4];
+    P[5] = m * P[5];
+  }
+}
+
+// MaterialLaw::calcPolarization  F:10414-10445 on the Voigt-mixed law: C = the FULL matrix dPK1 fills from the identity rows
+// (row m = C(:, m) f_m, f = (1, 1, 1, 2, 2, 2), built phase by phase like VoigtMixedMaterialLaw::dPK1 F:12763-12771 with the
+// threshold of pk1_voigt), Id the plain identity on the six stored components;  (C + 2 mu_0 Id) R = F  by Gaussian elimination
+// with partial pivoting (gesv),  Q = C R - 2 mu_0 R, evaluated as F - 4 mu_0 R (C R = F - 2 mu_0 R by the system just solved:
+// equal to rounding, and the matrix need not outlive the elimination).  Every index is a compile-time constant (the pivot
+// search is a chain of conditional row exchanges), so the one 6 x 7 matrix stays in registers on the device.
+template <int NPH>
+FG_HD void polarize_generic(const double* F, const double* phi, const PhaseTable& pt, double mu_0, bool inv, double* P) {
+  const double threshold = 10 * 2.220446049250313e-16;
+  double A[6][7];
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) A[i][j] = 0.0;
+#pragma unroll
+  for (int p = 0; p < NPH; ++p) {
+    if (p >= pt.n) break;
+    if (phi[p] <= threshold) continue;
+    if (pt.law[p] != kLawIso) {
+#pragma unroll
+      for (int m = 0; m < 6; ++m)
+#pragma unroll
+        for (int i = 0; i < 6; ++i) A[m][i] += (phi[p] * (m >= 3 ? 2.0 : 1.0)) * pt.C[p][6 * i + m];   // (the factor 2 is exact: same bits as phi (2 C))
+    } else {
+      const double tm = 2 * phi[p] * pt.mu[p], l = phi[p] * pt.lambda[p];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) A[i][i] += tm;
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) A[i][j] += l;
+    }
+  }
+  const double two_mu0 = 2.0 * mu_0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    A[i][i] += two_mu0;
+    A[i][6] = F[i];
+  }
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+#pragma unroll
+    for (int r = c + 1; r < 6; ++r) {   // after the chain row c holds the entry of largest magnitude in column c
+      const bool sw = fabs(A[r][c]) > fabs(A[c][c]);
+#pragma unroll
+      for (int j = c; j < 7; ++j) {
+        const double x = A[c][j], y = A[r][j];
+        A[c][j] = sw ? y : x;
+        A[r][j] = sw ? x : y;
+      }
+    }
+#pragma unroll
+    for (int r = c + 1; r < 6; ++r) {
+      const double m = A[r][c] / A[c][c];
+#pragma unroll
+      for (int j = c + 1; j < 7; ++j) A[r][j] -= m * A[c][j];
+    }
+  }
+  double R[6];
+#pragma unroll
+  for (int r = 5; r >= 0; --r) {
+    double v = A[r][6];
+#pragma unroll
+    for (int j = r + 1; j < 6; ++j) v -= A[r][j] * R[j];
+    R[r] = v / A[r][r];
+  }
+#pragma unroll
+  for (int m = 0; m < 6; ++m) P[m] = inv ? R[m] : F[m] - 2.0 * two_mu0 * R[m];
+}
+
+// MixedMaterialLaw::calcPolarization  F:12087-12099: the first phase with phi == 1 (exact) answers with its own law; an
+// isotropic one has the closed form, a general one has none of its own and takes the generic form like every mixed voxel.
+// Returns whether the generic form (the 6 x 6 solve) ran.
+template <int NPH>
+FG_HD bool polarize_voxel(const double* F, const double* phi, const PhaseTable& pt, double mu_0, bool inv, double* P) {
+#pragma unroll
+  for (int p = 0; p < NPH; ++p) {
+    if (p >= pt.n) break;
+    if (phi[p] == 1) {
+      if (pt.law[p] != kLawIso) break;
+      polarize_iso(F, pt.mu[p], pt.lambda[p], mu_0, inv, P);
+      return false;
+    }
+  }
+  polarize_generic<NPH>(F, phi, pt, mu_0, inv, P);
+  return true;
+}
+
 // G0OperatorFourierStaggeredGeneral frequency body  F:19873-19913
 //   kpm_a = sin(xi_a)/h_a, kp_a = kpm_a e^{i xi_a}, km_a = (-Re kp_a, Im kp_a)
 FG_HD void g0_point(cplx t0, cplx t1, cplx t2, double kpm0, double kpm1, double kpm2, cplx kp0, cplx kp1, cplx kp2,

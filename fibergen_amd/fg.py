@@ -28,7 +28,7 @@ import os
 import numpy as np
 
 from . import materials as _materials
-from .solver import LSSolver
+from .solver import METHODS, POLARIZATION_ERRORS, LSSolver
 from .xmlproject import XMLProject
 
 log = logging.getLogger("fibergen_amd")
@@ -275,7 +275,7 @@ class FG:
         self._mode = mode
         scalar = mode != "elasticity"      # laws with the single constant mu (ScalarLinearIsotropicMaterialLaw)
         method = self._child_value(solver, "method", "cg", str)
-        if method not in ("basic", "cg"):
+        if method not in METHODS:   # "basic+el", "nesterov" (experiments in the reference), "nl_cg": not built
             raise RuntimeError("Unknown solver method '%s'" % method)
         self._method = method
         scheme = self._child_value(solver, "gamma_scheme", "auto", str)
@@ -304,6 +304,19 @@ class FG:
             raise RuntimeError("gamma scheme '%s' is not available with mixing rule '%s' on the MI355X path (voigt only: the "
                                "laminate split is not linear in phi)" % (scheme, mixing))
 
+        # method polarization (runPolarization F:21808-21851): what it does not cover is refused before a solver exists, in the
+        # wording of the solver library (Solver::polar_check); the boundary conditions are checked in run_load_case
+        if method == "polarization":
+            if getattr(self, "_slabs", False):
+                raise RuntimeError(POLARIZATION_ERRORS["slab"])
+            if mode != "elasticity":
+                raise RuntimeError(POLARIZATION_ERRORS["mode"])
+            if mixing != "voigt":
+                raise RuntimeError(POLARIZATION_ERRORS["mixing"])
+            if dfg:
+                raise RuntimeError(POLARIZATION_ERRORS["dfg"])
+            if est not in ("epsilon", "none"):
+                raise RuntimeError(POLARIZATION_ERRORS["estimator"])
         # law="general" (a constant 6x6 stiffness): what it does not cover is refused before a solver exists, in the wording of
         # the solver library (Solver::general_check)
         mats_el = solver.find("materials") if solver is not None else None
@@ -854,6 +867,15 @@ class FG:
             self.init_phase()
             return None
         if name == "run_load_case":
+            solver_el = self._settings().find("solver")
+            if self._child_value(solver_el, "method", "cg", str) == "polarization":
+                # pure-strain boundary conditions only: refused before a solver exists
+                P0 = np.diag([1.0, 1.0, 1.0, 0.5, 0.5, 0.5])
+                for i in range(6):
+                    for j in range(6):
+                        key = "p%d%d" % (i + 1, j + 1)
+                        if key in act.attrib and self._eval(act.attrib[key]) != P0[i, j]:
+                            raise RuntimeError(POLARIZATION_ERRORS["bc"])
             self.init_lss()
             scalar = self._mode in ("heat", "porous")
             E = self._voigt_vector(act, "e")

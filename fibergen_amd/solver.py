@@ -14,6 +14,22 @@ from . import _lib
 
 MIXING = {"voigt": 0, "laminate": 1}
 
+# method option values: runBasic F:21716, runCGElasticity F:23153, runPolarization F:21808 (the Eyre-Milton scheme); the
+# reference's "basic+el" and "nesterov" are experiments and stay unknown here
+METHODS = {"basic": 0, "cg": 1, "polarization": 2}
+
+# what method polarization does not cover, in the wording of the solver library (Solver::polar_check)
+POLARIZATION_ERRORS = {
+    "slab": "method polarization is not available on slab-decomposed solvers",
+    "mode": "method polarization is available in mode elasticity only (not heat / porous / viscosity)",
+    "mixing": "method polarization supports mixing_rule voigt only (not laminate)",
+    "dfg": "method polarization is not available with gamma_scheme full_staggered / half_staggered",
+    "estimator": ("method polarization supports error_estimator epsilon and none only (not sigma / energy / residual: "
+                  "the loop's field is the polarisation, not the strain)"),
+    "bc": ("method polarization supports pure-strain boundary conditions only (bc_projector = identity; the "
+           "reference switches the mixed check off)"),
+}
+
 # gamma_scheme option values; full_staggered and half_staggered are the staggered operator with the material evaluated on
 # the doubly fine grid (use_dfg F:14894-14897, alias "full-staggered" F:15068): they differ only in how the fine phase
 # fields are made (voxelised on the fine grid, or replicated from the coarse one)
@@ -146,9 +162,9 @@ class LSSolver:
                     raise RuntimeError("Unknown mixing rule '%s'" % v)
                 self._check(self._lib.fg_set_option_i(self._h, b"mixing_rule", MIXING[v]))
             elif k == "method":
-                if v not in ("basic", "cg"):
+                if v not in METHODS:
                     raise RuntimeError("Unknown solver method '%s'" % v)
-                self._check(self._lib.fg_set_option_i(self._h, b"method", 1 if v == "cg" else 0))
+                self._check(self._lib.fg_set_option_i(self._h, b"method", METHODS[v]))
             elif k == "gamma_scheme":
                 if v not in GAMMA_SCHEMES:
                     raise RuntimeError("Unknown gamma scheme '%s'" % v)
@@ -234,7 +250,8 @@ class LSSolver:
         is transformed: 0 length 1, 1 power of two, 2 sub-lines p * 2^k, 3 tile kernels, 4 Bluestein, 5 O(n^2)),
         "fft_bluestein_m_x|y|z" (padded length of the axis' Bluestein pass, 0 = not on Bluestein), "phase_uploads" (host
         arrays received by set_phase / set_phase_fine / set_normals), "u_tile_aniso" (launches of the tiled sweep's anisotropic
-        form), "sc_tile_aniso" (launches of the tiled scalar sweep's aniso form); -1 = unknown name."""
+        form), "sc_tile_aniso" (launches of the tiled scalar sweep's aniso form), "polarization_generic_voxels" (method
+        polarization: voxels that took the 6 x 6 solve in the last forward pass); -1 = unknown name."""
         return int(self._lib.fg_get_counter(self._h, name.encode()))
 
     def iterate(self, E, n):

@@ -123,7 +123,18 @@ int fg_set_normals(fg_solver* s, const double* normals /* [3][nx][ny][nz] */);
  * every error estimator, load steps, mixed boundary conditions: the strain-state loops, like collocated) and viscosity; mode
  * heat / porous, slab-decomposed solvers and fg_set_phase_field_fine are refused),
  * method (0 = basic scheme, runBasic F:21716-21805; 1 = conjugate gradients, runCGElasticity
- * F:23153-23247, the reference's default), error_estimator (0 = epsilon F:14591-14637; 1 = residual F:14382-14405, method
+ * F:23153-23247, the reference's default; 2 = polarization, the Eyre-Milton scheme: runPolarization F:21808-21851,
+ * polarizationScheme F:20536-20554, calcPolarization F:18044-18131 with the per-voxel forms F:11427-11467 (isotropic, closed)
+ * and F:10414-10445 (6 x 6 solve: mixed voxels and general phases), dispatched as F:12087-12099; mu_0 = sqrt(min max) of the
+ * tangent spectrum F:12227-12229.  The loop's state is the polarisation P = (C + 2 mu_0) : eps; after a run, or on the first
+ * field / mean accessor after fg_iterate, it is converted to the strain (F:21850), fg_get_field "polarization" reads the raw
+ * state between passes.  Elasticity, Voigt mixing, iso and general phases, pure-strain boundary conditions, estimators epsilon
+ * and none, load steps, one GPU; laminate mixing, full_staggered, heat / porous / viscosity, a bc projector other than the
+ * identity, estimators sigma / energy / residual and slab solvers are refused by name.  gamma_scheme collocated and willot
+ * follow the reference to the operation (beta honoured F:19286-19734).  gamma_scheme staggered is a stated deviation: the
+ * reference's GammaOperatorStaggered F:20288-20300 takes beta and drops it, which is not Eyre-Milton's iteration; here
+ * P <- Q - 4 mu_0 grad_s_h G0 div_h Q with its mean replaced by P00 + P0.  fg_get_counter "polarization_generic_voxels":
+ * voxels that took the 6 x 6 solve in the last forward pass), error_estimator (0 = epsilon F:14591-14637; 1 = residual F:14382-14405, method
  * cg only; 2 = sigma F:14514-14587; 3 = energy F:14410-14468; 4 = none F:14370-14378 -- 2 and 3 re-measure <sigma> / <W> of
  * the strain field after every iteration (two more sweeps), the conjugate gradients then iterate on the strain field), and the implementation switches u_loop (2 = default: the loop carries the
  * displacement, fast kernels; 1 = the same with the reference's operation order, iterates bit-identical to 0; 0 = the

@@ -1,0 +1,145 @@
+"""method "polarization" at the project layer, without a GPU: the XML value reaches the solver's options, every refusal raises
+in the library's wording before a solver exists, and the reference's experimental methods stay unknown."""
+import os
+import re
+
+import pytest
+
+from fibergen_amd.fg import FG
+from fibergen_amd.solver import METHODS, POLARIZATION_ERRORS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+XML = """
+<settings>
+  <solver n="8">
+    <method>%s</method>
+    <materials>
+      <matrix E="1" nu="0.3" />
+      <fiber E="100" nu="0.2" />
+    </materials>
+  </solver>
+  <actions><select_material name="fiber" /><place_fiber R="0.3" /></actions>
+</settings>
+"""
+
+
+class FakeSolver:
+    """records what init_lss hands to the solver"""
+    made = []
+
+    def __init__(self, *a, **k):
+        self.calls = []
+        FakeSolver.made.append(self)
+
+    def set_num_phases(self, n):
+        self.calls.append(("n", n))
+
+    def set_phase(self, p, mu, lam, phi=None):
+        self.calls.append(("iso", p, mu, lam))
+
+    def set_phase_stiffness(self, p, C):
+        self.calls.append(("general", p))
+
+    def set_options(self, **kw):
+        self.calls.append(("opts", kw))
+
+    def set_convergence_callback(self, fn):
+        pass
+
+
+@pytest.fixture
+def fake(monkeypatch):
+    import fibergen_amd.fg as fgmod
+    FakeSolver.made = []
+    monkeypatch.setattr(fgmod, "LSSolver", FakeSolver)
+    return FakeSolver
+
+
+def project(method="polarization", **settings):
+    fg = FG()
+    fg.set_xml(XML % method)
+    for k, v in settings.items():
+        fg.set("solver." + k, v)
+    return fg
+
+
+def options_of(fake):
+    opts = {}
+    for c in fake.made[-1].calls:
+        if c[0] == "opts":
+            opts.update(c[1])
+    return opts
+
+
+@pytest.mark.parametrize("scheme", ["staggered", "collocated"])
+@pytest.mark.parametrize("est", ["epsilon", "none"])
+def test_the_xml_value_reaches_set_options(fake, scheme, est):
+    fg = project(gamma_scheme=scheme, error_estimator=est)
+    fg._init_python()
+    fg.init_lss()
+    opts = options_of(fake)
+    assert opts["method"] == "polarization" and opts["gamma_scheme"] == scheme and opts["error_estimator"] == est
+    assert METHODS["polarization"] == 2
+
+
+@pytest.mark.parametrize("settings,key", [
+    ({"mixing_rule": "laminate"}, "mixing"),
+    ({"gamma_scheme": "full_staggered"}, "dfg"),
+    ({"gamma_scheme": "half_staggered"}, "dfg"),
+    ({"mode": "heat"}, "mode"),
+    ({"mode": "porous"}, "mode"),
+    ({"mode": "viscosity"}, "mode"),
+    ({"error_estimator": "sigma"}, "estimator"),
+    ({"error_estimator": "energy"}, "estimator"),
+    ({"error_estimator": "residual"}, "estimator"),
+])
+def test_refusals_create_no_solver(fake, settings, key):
+    fg = project(**settings)
+    with pytest.raises(RuntimeError, match=re.escape(POLARIZATION_ERRORS[key])):
+        fg.init_lss()
+    assert not fake.made, "refused before a solver is created"
+
+
+def test_refused_on_slabs(fake):
+    fg = project()
+    fg._slabs = True
+    with pytest.raises(RuntimeError, match=re.escape(POLARIZATION_ERRORS["slab"])):
+        fg.init_lss()
+    assert not fake.made
+
+
+def test_mixed_boundary_conditions_are_refused_before_a_solver_exists(fake):
+    import xml.etree.ElementTree as ET
+    fg = project()
+    fg._init_python()
+    act = ET.fromstring('<run_load_case e11="1" s33="0" p33="0" />')
+    with pytest.raises(RuntimeError, match=re.escape(POLARIZATION_ERRORS["bc"])):
+        fg._run_action(act)
+    assert not fake.made
+
+
+@pytest.mark.parametrize("method", ["nesterov", "basic+el", "nl_cg"])
+def test_experimental_methods_stay_unknown(fake, method):
+    with pytest.raises(RuntimeError, match=re.escape("Unknown solver method '%s'" % method)):
+        project(method).init_lss()
+    assert not fake.made
+    from fibergen_amd import LSSolver
+    with pytest.raises(RuntimeError, match="Unknown solver method"):
+        LSSolver.set_options(object.__new__(LSSolver), method=method)
+
+
+def test_messages_are_the_library_s():
+    """the project layer raises in the wording of Solver::polar_check / fg_set_option_i"""
+    src = ""
+    for name in ("fg_solver.hip", "fg_capi.hip"):
+        src += open(os.path.join(ROOT, "fibergen_amd", "csrc", name)).read()
+    src = re.sub(r'"\s*\n\s*"', "", src)
+    for key, msg in POLARIZATION_ERRORS.items():
+        assert '"%s"' % msg in src, key
+
+
+def test_documented_in_the_header():
+    text = open(os.path.join(ROOT, "include", "fibergen_amd.h")).read()
+    for cite in ("F:21808-21851", "F:20536-20554", "F:18044-18131", "F:20288-20300", "polarization_generic_voxels"):
+        assert cite in text, cite
