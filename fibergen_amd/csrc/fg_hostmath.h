@@ -60,6 +60,17 @@ inline void bc_mean(const Mat6& QC0, const Mat6& M, double bc_relax, const doubl
   for (int i = 0; i < 6; ++i) E[i] = E0[i] + bc_relax * t3[i];
 }
 
+// applyBCProjector  F:20247-20270: R = alpha (bc_relax MQ:F0 - (1 - bc_relax) M:(QC0:F00)), F0 = <tau>, F00 = mean of the
+// operator's argument
+inline void bc_correction(const Mat6& MQ, const Mat6& M, const Mat6& QC0, double bc_relax, double alpha, const double* F0,
+                          const double* F00, double* R) {
+  double t1[6], t2[6], t3[6];
+  voigt_mv(MQ, F0, t1);
+  voigt_mv(QC0, F00, t2);
+  voigt_mv(M, t2, t3);
+  for (int i = 0; i < 6; ++i) R[i] = alpha * (bc_relax * t1[i] - (1 - bc_relax) * t3[i]);
+}
+
 // Voigt::dyad4(A, B) column by column  F:582-597
 inline Mat6 voigt_mm(const Mat6& A, const Mat6& B) {
   Mat6 C;

@@ -31,6 +31,7 @@ struct XHalo {
   const double* lo[2];
   const double* hi[2];
 };
+constexpr XHalo kNoXHalo = {{nullptr, nullptr}, {nullptr, nullptr}};   // the whole field is here: periodic wrap on both sides
 
 // collocated scheme: xi_a[m] = m_signed / d_a per axis (F:19385, 19411-19424), the z table holds nzc entries
 struct XiTables {

@@ -252,11 +252,11 @@ void Solver::slab_fetch_norms(int n) {
 bool Solver::slab_fast_ok(bool allow_mixed_bc) const {
   if (opt_.mode == 1)   // heat / porous: the potential sweep on the precomputed conductivity
     return opt_.u_loop >= 2 && opt_.gamma_scheme == 0 && pt_.n >= 1 && opt_.mixing == kMixVoigt && opt_.bc_relax == 1.0 && fft_ys_ &&
-           (frobenius(BC_MQ_) < kEps || allow_mixed_bc);
+           (!mixed_bc() || allow_mixed_bc);
   if (!(opt_.u_loop >= 2 && opt_.u_tile && opt_.mode == 0 && opt_.gamma_scheme == 0 && pt_.n >= 1 &&
         (opt_.mixing == kMixVoigt || (opt_.mixing == kMixLaminate && normals_)) && opt_.bc_relax == 1.0 && u_tile_supported(g_)))
     return false;
-  return frobenius(BC_MQ_) < kEps || allow_mixed_bc;
+  return !mixed_bc() || allow_mixed_bc;
 }
 
 void Solver::slab_moduli_step() {
@@ -526,9 +526,7 @@ void Solver::slab_front_exact(bool sum_tau) {
   comm_wait(kXSums);
   if (su_valid_ && eps_stale_) slab_materialise_eps();
   if (opt_.mixing == kMixLaminate && !normals_) throw std::runtime_error("laminate mixing needs interface normals");
-  FieldPtrs<3> nrm;
-  for (int c = 0; c < 3; ++c) nrm.p[c] = normals_ ? normals_ + (long)c * g_.n : nullptr;
-  launch_stress(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs6(eps_), phase_ptrs(), nrm, ptrs6(tau_), derr_, stream_);
+  launch_stress(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs6(eps_), phase_ptrs(), normal_ptrs(), ptrs6(tau_), derr_, stream_);
   sum_tau = sum_tau || opt_.mode == 2;   // viscosity: the Delta operator needs <tau> in every pass
   if (sum_tau) launch_sum6(g_, ptrs6(tau_), false, partial_, dscal_ + kSlotMean, stream_);
   const long plane = g_.nyzp, last = (long)(g_.nx - 1) * g_.nyzp;
@@ -791,8 +789,7 @@ void SlabGroup::mean_stress(double* out6) {
   prepare();
   for (Solver* s : m_) {
     if (s->su_valid_ && s->eps_stale_) s->slab_materialise_eps();
-    FieldPtrs<3> nrm;
-    for (int c = 0; c < 3; ++c) nrm.p[c] = s->normals_ ? s->normals_ + (long)c * s->g_.n : nullptr;
+    const FieldPtrs<3> nrm = s->normal_ptrs();
     // meanPK1: alpha /= nxyz (global), accumulate  F:12318-12340
     if (s->opt_.mode == 1)
       launch_sc_flux_mean(s->g_, s->scalar_params(0.0, 1.0 / (double)s->nglobal_), s->ptrs3(s->eps_), s->phase_ptrs(), s->partial_,
@@ -812,8 +809,7 @@ double SlabGroup::mean_energy() {
   for (Solver* s : m_) {
     if (s->opt_.mode == 1) throw std::runtime_error("the energy error estimator is not available in heat / porous mode");
     if (s->su_valid_ && s->eps_stale_) s->slab_materialise_eps();
-    FieldPtrs<3> nrm;
-    for (int c = 0; c < 3; ++c) nrm.p[c] = s->normals_ ? s->normals_ + (long)c * s->g_.n : nullptr;
+    const FieldPtrs<3> nrm = s->normal_ptrs();
     launch_energy_mean(s->g_, s->stress_params(0.0, 0.0, 1.0), s->ptrs6(s->eps_), s->phase_ptrs(), nrm, s->partial_,
                        s->dscal_ + kSlotMean, s->derr_, s->stream_);
   }
@@ -943,16 +939,12 @@ void SlabGroup::pass_exact(const double* E6, bool mixed_bc) {
     for (Solver* s : m_) FG_HIP_CHECK(hipEventSynchronize(s->ev_norm_));
     for (int c = 0; c < 6; ++c) F0[c] = a.hscal_[kSlotMean + c] / (double)a.nglobal_;
   }
-  // applyBCProjector  F:20247-20270: R = alpha*(bc_relax*MQ:F0 - (1-bc_relax)*M:(QC0:F00))
-  double R[6], t1[6], t2[6], t3[6];
-  voigt_mv(a.BC_MQ_, F0, t1);
-  voigt_mv(a.BC_QC0_, F00, t2);
-  voigt_mv(a.BC_M_, t2, t3);
+  // applyBCProjector  F:20247-20270
+  double R[6] = {0, 0, 0, 0, 0, 0};
+  if (mixed_bc || a.opt_.bc_relax != 1.0) bc_correction(a.BC_MQ_, a.BC_M_, a.BC_QC0_, a.opt_.bc_relax, alpha, F0, F00, R);
   bool add_R = false;
-  for (int c = 0; c < 6; ++c) {
-    R[c] = (!mixed_bc && a.opt_.bc_relax == 1.0) ? 0.0 : alpha * (a.opt_.bc_relax * t1[c] - (1 - a.opt_.bc_relax) * t3[c]);
+  for (int c = 0; c < 6; ++c)
     if (R[c] != 0.0) add_R = true;
-  }
   for (Solver* s : m_) s->slab_back_exact(E6, R);
   for (Solver* s : m_) s->slab_fetch_norms(6);
   for (Solver* s : m_) {
@@ -975,7 +967,7 @@ void SlabGroup::iterate(const double* E6, int n) {
         s->eps_stale_ = true;
         for (int i = 0; i < 6; ++i) s->E_cur_[i] = E6[i];
       }
-  const bool mixed_bc = !(frobenius(a.BC_MQ_) < kEps);
+  const bool mixed_bc = a.mixed_bc();
   const bool fast = fast_ok(false);
   int i = 0;
   if (fast) {
@@ -1115,7 +1107,7 @@ bool SlabGroup::run_step(const double* E0, const double* S0, bool fresh) {
       update_ref = false;
       if (fast) prepare();   // effective moduli are independent of the reference material, but may not exist yet
     }
-    const bool mixed_bc = !(frobenius(a.BC_MQ_) < kEps);
+    const bool mixed_bc = a.mixed_bc();
     if (carry) {
       carry = false;
       if (mixed_bc) {
@@ -1532,7 +1524,7 @@ bool SlabGroup::run_cg_strain(const double* E0, const double* S0, double prev0) 
   }
   if (a.opt_.update_ref) calc_ref_material();
   const bool voting = agree_on_voting();
-  const bool mixed_bc = !(frobenius(a.BC_MQ_) < kEps);
+  const bool mixed_bc = a.mixed_bc();
   Vec6 E, Z;
   bc_mean(a.BC_QC0_, a.BC_M_, a.opt_.bc_relax, E0, S0, E.v);
   for (int i = 0; i < 6; ++i) Z.v[i] = 0.0;

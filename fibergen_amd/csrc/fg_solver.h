@@ -20,6 +20,7 @@
 #include "fg_cg_loop.h"
 #include "fg_comm.h"
 #include "fg_fft.h"
+#include "fg_g0_chain.h"
 #include "fg_hostmath.h"
 #include "fg_kernels.h"
 #include "fg_stop_rule.h"
@@ -246,8 +247,31 @@ class Solver {
   long counter(const std::string& name) const;
 
  private:
-  // one pass  dst = E - Gamma0 : (C - C0) : src  (defaults: the solver's strain field, in place)
+  // one pass  dst = E - Gamma0 : (C - C0) : src  (defaults: the solver's strain field, in place): the checks, then one of the
+  // four operators below (willot_scheme for gamma_scheme willot in either mode)
   void basic_scheme(const double* E6, double* src = nullptr, double* dst = nullptr);
+  void pass_viscosity(const double* E6, double* src, double* dst);    // DeltaOperatorStaggered (dual Stokes scheme)
+  void pass_collocated(const double* E6, double* src, double* dst);   // GammaOperatorCollocated
+  void pass_staggered(const double* E6, double* src, double* dst);    // GammaOperatorStaggered
+  // the end of every pass: pass count, fu_ holds (or not) the displacement of the state, dst is written, E6 is its prescribed mean
+  void pass_done(const double* E6, const double* dst, bool u_valid);
+  // forward transform of tau_ (1/N), the operator on tau_hat, inverse transform, tau_ -> dst (xpay: dst = tau_ + *xpay dst),
+  // sums of squares of dst; timing slots 2, 5, 8, 9
+  struct GammaHat {
+    bool willot;            // Willot's rotated operator, else the collocated one
+    double mu, lambda;      // reference material of the operator
+    double alpha, beta;     // eta_hat = alpha Gamma0_hat : tau_hat + beta tau_hat
+    Vec6 mean;              // the zero frequency (bc: + R)
+    bool bc;                // mixed boundary conditions / bc_relax: R from F0 = Re tau_hat(0), fetched between the two
+    const double* sums;     // device sums added to the zero frequency with weight sums_scale, or nullptr
+    double sums_scale;
+  };
+  void fourier_pass6(const GammaHat& op, double* dst, const double* xpay = nullptr);
+  // boundary-condition projector: |MQ| >= eps (NaN until calcRefMaterial ran counts as mixed: Q != 0)
+  bool mixed_bc() const { return !(hostmath::frobenius(BC_MQ_) < 2.220446049250313e-16); }
+  // <tau> on the host: the six device sums of kSlotMean / N, or (spectrum) the zero frequency of the scaled tau_hat in tau_
+  void fetch_mean6(double* F0, bool spectrum = false);
+  void bc_adjust_sums(double factor);   // k_bc_adjust_sums on kSlotMean with the plain matrix of v -> MQ:v
   void release();
   bool run_one_step(const double* E0, const double* S0);
   double current_norm9();
@@ -294,24 +318,37 @@ class Solver {
   bool willot() const { return opt_.gamma_scheme == 3; }
   void willot_check() const;            // throws for the combinations the willot scheme does not cover
   WillotTables willot_tables();         // the per-axis tables of the scheme (built on first use)
-  void willot_scheme(const double* E6, double* src, double* dst, const FieldPtrs<kMaxPhases>& phi, const FieldPtrs<3>& nrm);
+  void willot_scheme(const double* E6, double* src, double* dst);
   FieldPtrs<5> dfg_moduli();            // gamma_scheme 2: A_n, B_n, A_23, A_13, A_12 (once per geometry)
   // calcStress into tau_: the phase fractions, or under gamma_scheme 2 the five moduli
-  void stress_to_tau(const StressParams& sp, double* src, const FieldPtrs<kMaxPhases>& phi, const FieldPtrs<3>& nrm);
+  void stress_to_tau(const StressParams& sp, double* src);
   void build_laminate_lists();          // interface / affected voxel lists of the laminate correction (once per geometry)
   void u_pass_front(const double* E6);  // u_k (fu_) -> sums of squares of eps_k, f_{k+1} (fu_alt_)
   void u_pass_back();                   // f_{k+1} -> u_{k+1}, buffers swapped
   // r2c, y, x + Green operator + x^-1, y^-1, c2r on 3 components
   // c12: optional {c10, c20} replacing the factors derived from (mu_0, lambda_0, alpha)
   // xscratch: three free components the spectrum may pass through in the x-contiguous layout (nullptr: in place, plain layout)
+  // (fills a G0ChainPlan and runs g0_chain, fg_g0_chain.h; the chain_* members are the passes it calls back)
   bool plane_fft_on() const;
   void fft_g0_chain(double* buf, double alpha = -1.0, const double* c12 = nullptr, double* xscratch = nullptr);
+  template <class Site>
+  friend void g0_chain(Site&, const G0ChainPlan&, double*, double*);
+  void chain_r2c_z(double* buf, int ncomp, int x0, int np);
+  void chain_c2r_z(double* buf, int ncomp, int x0, int np);
+  void chain_c2c_y(double* buf, int ncomp, int dir, double scale, int x0, int np);
+  void chain_c2c_y_xlayout(double* in, double* out, int ncomp, int dir, int x0, int np);
+  void chain_c2c_x(double* buf, int ncomp, int dir, double scale);
+  void chain_zy_plane(double* buf, int ncomp, int dir);
+  void chain_scale(double* buf, int ncomp, double scale);
+  void chain_fused_x(double* data, int ncomp, double scale, double c10, double c20, bool xlayout);
+  void chain_green(double* buf, int ncomp, double c10, double c20);
   void ensure_eps();                    // materialise eps = E + sym grad u if the loop left it implicit
   void recompute_bc();
   double bc_error(const double* E_cur, const double* S_cur);
   StressParams stress_params(double mu_0, double lambda_0, double alpha) const;
   ScalarParams scalar_params(double mu_0, double alpha) const;
   FieldPtrs<kMaxPhases> phase_ptrs() const;
+  FieldPtrs<3> normal_ptrs() const;   // nullptr entries until normals are set
   PhaseTable phase_table() const;  // constants the kernels see (viscosity: Hooke constants equivalent to the scalar law)
   FieldPtrs<6> ptrs6(double* base) const;
   FieldPtrs<3> ptrs3(double* base) const;
@@ -324,10 +361,7 @@ class Solver {
   bool staged_copy(size_t bytes, bool download) const;
   void upload_rows(const std::vector<RowBlock>& blocks, long len, long pitch);
   void download_rows(const std::vector<RowBlock>& blocks, long len, long pitch);
-  int pair_chunk_planes(int ncomp) const;
-  template <class A, class B>
-  void run_pairs(int pc, A first, B second);
-
+  int pair_chunk_planes() const;
 
   void time_begin(int stage);
   void time_end(int stage);

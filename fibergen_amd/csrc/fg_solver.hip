@@ -588,7 +588,7 @@ void Solver::check_device_error(const char* where) {
 // The same check, but the host waits only for the copies enqueued so far (an event), not for work enqueued after them.
 void Solver::fetch_norms_and_errors(const char* where) {
   static_assert(kSlotMean == kSlotSumSq + 6, "the displacement sweep writes norms and tau sums as one block of 12");
-  const bool mixed_u = pending_back_ && !(frobenius(BC_MQ_) < kEps);
+  const bool mixed_u = pending_back_ && mixed_bc();
   const int nfetch = mixed_u ? 12 : 6;
   const int n2 = (mixed_u && opt_.mixing != kMixVoigt) ? 6 : 0;   // mixed BC + laminate: + sums of the interface differences
   {
@@ -685,7 +685,7 @@ long Solver::counter(const std::string& name) const {
     FG_HIP_CHECK(hipMemcpy(&v, dscal_ + kSlotPolar + 6, sizeof(double), hipMemcpyDeviceToHost));
     return (long)v;
   }
-  if (name == "pair_chunk_planes") return (long)pair_chunk_planes(opt_.mode == 1 ? 1 : 3);
+  if (name == "pair_chunk_planes") return (long)pair_chunk_planes();
   return -1;
 }
 
@@ -707,8 +707,8 @@ void Solver::time_end(int stage) {
 }
 
 // ------------------------------------------------------------------ one pass of the basic scheme
-// basicScheme  F:20558-20578 + GammaOperatorStaggered  F:20288-20300:
-//   tau = (C - C0):eps ; f = div tau ; u = G0 f ; eps = E + sym grad u (+ R)
+// basicScheme  F:20558-20578: the checks, the strain state and the mean of the operator's argument, then the operator of the
+// mode and gamma_scheme; every operator ends in pass_done
 void Solver::basic_scheme(const double* E6, double* src, double* dst) {
   if (!src) src = eps_;
   if (!dst) dst = eps_;
@@ -718,151 +718,173 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
   if (dfg()) dfg_check();
   if (willot()) willot_check();
   general_check();
-  FieldPtrs<kMaxPhases> phi;
-  for (int q = 0; q < kMaxPhases; ++q) phi.p[q] = q < pt_.n ? phi_ + (long)q * g_.n : nullptr;
-  FieldPtrs<3> nrm;
-  for (int c = 0; c < 3; ++c) nrm.p[c] = normals_ ? normals_ + (long)c * g_.n : nullptr;
-  const double alpha = -1.0;  // GammaOperator(..., -1)  F:20575
 
   ensure_eps();  // the displacement-based loop may have left the strain implicit
   if (opt_.bc_relax != 1.0) {  // F:20563-20565: mean of the operator's argument
     launch_sum6(g_, ptrs6(src), false, partial_, dscal_ + kSlotMean, stream_);
-    FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean, dscal_ + kSlotMean, 6 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    FG_HIP_CHECK(hipStreamSynchronize(stream_));
-    for (int c = 0; c < 6; ++c) F00_[c] = hscal_[kSlotMean + c] / (double)nglobal_;
+    fetch_mean6(F00_);
   }
-
   if (opt_.mode == 2) {
-    // DeltaOperatorStaggered  F:20422-20460 (dual Stokes scheme), called with alpha = -1 by basicScheme:
-    //   m = 1/(4 mu0);  adj = E - 2 alpha m <tau>;  eta = GammaStaggered(adj; mu = -1/(4 m), lambda = inf)(tau)
-    //   + 2 alpha m tau.   lambda0 = inf makes c20 = c10 in G0OperatorFourierStaggered (F:19749-19755).
     if (opt_.gamma_scheme == 1) throw std::runtime_error("viscosity mode supports gamma_scheme staggered, full_staggered and willot only");
     if (opt_.mixing != kMixVoigt) throw std::runtime_error("viscosity mode supports Voigt mixing only");
     if (opt_.bc_relax != 1.0) throw std::runtime_error("viscosity mode supports bc_relax = 1 only");
-    if (willot()) {
-      willot_scheme(E6, src, dst, phi, nrm);
-      return;
-    }
-    const bool mixed_bc = !(frobenius(BC_MQ_) < kEps);   // initBCProjector / applyBCProjector inside GammaOperatorStaggered
-    const double m = 1 / (4 * opt_.mu_0);
-    // full_staggered: the fused form exists as the tiled sweep only (other grids store the polarisation)
-    const bool fused = opt_.fuse_stress_div != 0 && (!dfg() || (opt_.u_loop >= 2 && u_tile_supported(g_)));
-    if (fused) {
-      // the polarisation is a point-wise function of the strain: it is evaluated inside the divergence sweep (with its
-      // six sums) and again in the tail sweep, and never stored
-      time_begin(0);
-      if (dfg())
-        launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), dfg_moduli(), ptrs3(fu_), partial_, dscal_ + kSlotMean,
-                        stream_);
-      else if (opt_.u_loop >= 2 && u_tile_supported(g_))   // fast kernels allowed: the LDS-tiled marching form
-        launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), effective_moduli(), ptrs3(fu_), partial_,
-                        dscal_ + kSlotMean, stream_);
-      else
-        launch_stress_div_sum_voigt(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs6(src), phi, ptrs3(fu_), partial_,
-                                    dscal_ + kSlotMean, stream_);
-      time_end(0);
-    } else {
-      time_begin(0);
-      stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), src, phi, nrm);
-      time_end(0);
-      launch_sum6(g_, ptrs6(tau_), false, partial_, dscal_ + kSlotMean, stream_);   // tau_copy->average(), stays on the device
-      time_begin(1);
-      launch_div(g_, ptrs6(tau_), ptrs3(fu_), XHalo{{nullptr, nullptr}, {nullptr, nullptr}}, stream_);
-      time_end(1);
-    }
-    if (mixed_bc) {
-      Mat36 B;
-      for (int j = 0; j < 6; ++j) {
-        double e[6] = {0, 0, 0, 0, 0, 0}, col[6];
-        e[j] = 1.0;
-        voigt_mv(BC_MQ_, e, col);
-        for (int c = 0; c < 6; ++c) B.a[c * 6 + j] = col[c];
-      }
-      hipLaunchKernelGGL(k_bc_adjust_sums, dim3(1), dim3(64), 0, stream_, dscal_ + kSlotMean, B, alpha / (2 * alpha * m));
-      FG_HIP_CHECK(hipGetLastError());
-    }
-    const double mu_g = -1.0 / (4 * m);
-    const double c12[2] = {-alpha / mu_g, -alpha / mu_g};
-    fft_g0_chain(fu_, alpha, c12, fused ? tau_ : nullptr);   // (fused: the polarisation is never stored, its field is free for the x-contiguous layout)
-    // adj = E - 2 alpha m <tau>;  eta = adj + sym grad u;  eta.xpay(eta, 2 alpha m, tau_copy)  F:20438-20452, one sweep
-    Vec6 Ev;
-    for (int c = 0; c < 6; ++c) Ev.v[c] = E6[c];
-    time_begin(9);
-    if (fused && dfg())
-      launch_eps_delta_recompute(g_, ptrs3(fu_), ptrs6(src), stress_params(opt_.mu_0, opt_.lambda_0, 1.0), dfg_moduli(),
-                                 dscal_ + kSlotMean, (double)nglobal_, Ev, 2 * alpha * m, ptrs6(dst), partial_,
-                                 dscal_ + kSlotSumSq, stream_);
-    else if (fused)
-      launch_eps_delta_recompute(g_, ptrs3(fu_), ptrs6(src), stress_params(opt_.mu_0, opt_.lambda_0, 1.0), phi,
-                                 dscal_ + kSlotMean, (double)nglobal_, Ev, 2 * alpha * m, ptrs6(dst), partial_,
-                                 dscal_ + kSlotSumSq, stream_);
-    else
-      launch_eps_delta(g_, ptrs3(fu_), ptrs6(tau_), dscal_ + kSlotMean, (double)nglobal_, Ev, 2 * alpha * m, ptrs6(dst),
-                       partial_, dscal_ + kSlotSumSq, stream_);
-    time_end(9);
-    if (timing_) times_.count++;
-    u_valid_ = false;
-    if (dst == eps_) eps_stale_ = false;
-    for (int c = 0; c < 6; ++c) E_cur_[c] = E6[c];
-    return;
   }
-  if (willot()) {
-    willot_scheme(E6, src, dst, phi, nrm);
-    return;
+  if (willot()) willot_scheme(E6, src, dst);
+  else if (opt_.mode == 2) pass_viscosity(E6, src, dst);
+  else if (opt_.gamma_scheme == 1) pass_collocated(E6, src, dst);
+  else pass_staggered(E6, src, dst);
+}
+
+void Solver::pass_done(const double* E6, const double* dst, bool u_valid) {
+  if (timing_) times_.count++;
+  u_valid_ = u_valid;
+  if (dst == eps_) eps_stale_ = false;
+  for (int c = 0; c < 6; ++c) E_cur_[c] = E6[c];
+}
+
+void Solver::fetch_mean6(double* F0, bool spectrum) {
+  if (spectrum) {   // the forward transform is scaled by 1/N: Re tau_hat(0) is the mean
+    for (int c = 0; c < 6; ++c)
+      FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean + c, tau_ + (long)c * g_.n, sizeof(double), hipMemcpyDeviceToHost, stream_));
+  } else {
+    FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean, dscal_ + kSlotMean, 6 * sizeof(double), hipMemcpyDeviceToHost, stream_));
   }
-  if (opt_.gamma_scheme == 1) {
-    // GammaOperatorCollocated  F:20302-20310: fftTensor, initBCProjector, Gamma0_hat, applyBCProjector, fftInvTensor on the
-    // six components
+  FG_HIP_CHECK(hipStreamSynchronize(stream_));
+  for (int c = 0; c < 6; ++c) F0[c] = spectrum ? hscal_[kSlotMean + c] : hscal_[kSlotMean + c] / (double)nglobal_;
+}
+
+void Solver::bc_adjust_sums(double factor) {
+  Mat36 B;
+  for (int j = 0; j < 6; ++j) {
+    double e[6] = {0, 0, 0, 0, 0, 0}, col[6];
+    e[j] = 1.0;
+    voigt_mv(BC_MQ_, e, col);
+    for (int c = 0; c < 6; ++c) B.a[c * 6 + j] = col[c];
+  }
+  hipLaunchKernelGGL(k_bc_adjust_sums, dim3(1), dim3(64), 0, stream_, dscal_ + kSlotMean, B, factor);
+  FG_HIP_CHECK(hipGetLastError());
+}
+
+// DeltaOperatorStaggered  F:20422-20460 (dual Stokes scheme), called with alpha = -1 by basicScheme:
+//   m = 1/(4 mu0);  adj = E - 2 alpha m <tau>;  eta = GammaStaggered(adj; mu = -1/(4 m), lambda = inf)(tau)
+//   + 2 alpha m tau.   lambda0 = inf makes c20 = c10 in G0OperatorFourierStaggered (F:19749-19755).
+void Solver::pass_viscosity(const double* E6, double* src, double* dst) {
+  const double alpha = -1.0;  // GammaOperator(..., -1)  F:20575
+  const double m = 1 / (4 * opt_.mu_0);
+  const StressParams sp = stress_params(opt_.mu_0, opt_.lambda_0, 1.0);
+  // full_staggered: the fused form exists as the tiled sweep only (other grids store the polarisation)
+  const bool fused = opt_.fuse_stress_div != 0 && (!dfg() || (opt_.u_loop >= 2 && u_tile_supported(g_)));
+  if (fused) {
+    // the polarisation is a point-wise function of the strain: it is evaluated inside the divergence sweep (with its
+    // six sums) and again in the tail sweep, and never stored
     time_begin(0);
-    stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), src, phi, nrm);
+    if (dfg())
+      launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), dfg_moduli(), ptrs3(fu_), partial_, dscal_ + kSlotMean,
+                      stream_);
+    else if (opt_.u_loop >= 2 && u_tile_supported(g_))   // fast kernels allowed: the LDS-tiled marching form
+      launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), effective_moduli(), ptrs3(fu_), partial_,
+                      dscal_ + kSlotMean, stream_);
+    else
+      launch_stress_div_sum_voigt(g_, sp, ptrs6(src), phase_ptrs(), ptrs3(fu_), partial_, dscal_ + kSlotMean, stream_);
     time_end(0);
-    time_begin(2);
-    fft_->forward(tau_, 6, g_.n, 1 / (double)nglobal_);   // fftTensor: 1/N on the forward transform  F:18531-18560
-    time_end(2);
+  } else {
+    time_begin(0);
+    stress_to_tau(sp, src);
+    time_end(0);
+    launch_sum6(g_, ptrs6(tau_), false, partial_, dscal_ + kSlotMean, stream_);   // tau_copy->average(), stays on the device
+    time_begin(1);
+    launch_div(g_, ptrs6(tau_), ptrs3(fu_), kNoXHalo, stream_);
+    time_end(1);
+  }
+  // initBCProjector / applyBCProjector inside GammaOperatorStaggered (k_bc_adjust_sums has the algebra)
+  if (mixed_bc()) bc_adjust_sums(alpha / (2 * alpha * m));
+  const double mu_g = -1.0 / (4 * m);
+  const double c12[2] = {-alpha / mu_g, -alpha / mu_g};
+  fft_g0_chain(fu_, alpha, c12, fused ? tau_ : nullptr);   // (fused: the polarisation is never stored, its field is free for the x-contiguous layout)
+  // adj = E - 2 alpha m <tau>;  eta = adj + sym grad u;  eta.xpay(eta, 2 alpha m, tau_copy)  F:20438-20452, one sweep
+  Vec6 Ev;
+  for (int c = 0; c < 6; ++c) Ev.v[c] = E6[c];
+  time_begin(9);
+  if (fused && dfg())
+    launch_eps_delta_recompute(g_, ptrs3(fu_), ptrs6(src), sp, dfg_moduli(), dscal_ + kSlotMean, (double)nglobal_, Ev,
+                               2 * alpha * m, ptrs6(dst), partial_, dscal_ + kSlotSumSq, stream_);
+  else if (fused)
+    launch_eps_delta_recompute(g_, ptrs3(fu_), ptrs6(src), sp, phase_ptrs(), dscal_ + kSlotMean, (double)nglobal_, Ev,
+                               2 * alpha * m, ptrs6(dst), partial_, dscal_ + kSlotSumSq, stream_);
+  else
+    launch_eps_delta(g_, ptrs3(fu_), ptrs6(tau_), dscal_ + kSlotMean, (double)nglobal_, Ev, 2 * alpha * m, ptrs6(dst),
+                     partial_, dscal_ + kSlotSumSq, stream_);
+  time_end(9);
+  pass_done(E6, dst, false);
+}
+
+// The six-component Fourier pass of the collocated and the willot operators (fftTensor, Gamma0_hat, fftInvTensor), also
+// method polarization's.  op.bc: F0 = Re tau_hat(0) (initBCProjector(tau_hat) F:20219-20225) and the zero frequency of eta_hat
+// becomes mean + R (applyBCProjector(eta_hat, alpha) F:20272-20279) -- the Fourier kernels set it to the value handed in.
+// xpay: dst holds a field that is added with this weight (eta.xpay of the Delta operators) instead of being overwritten.
+void Solver::fourier_pass6(const GammaHat& op, double* dst, const double* xpay) {
+  time_begin(2);
+  fft_->forward(tau_, 6, g_.n, 1 / (double)nglobal_);   // fftTensor: 1/N on the forward transform  F:18531-18560
+  time_end(2);
+  Vec6 mean = op.mean;
+  if (op.bc) {
+    double F0[6], R[6];
+    fetch_mean6(F0, true);
+    bc_correction(BC_MQ_, BC_M_, BC_QC0_, opt_.bc_relax, op.alpha, F0, F00_, R);
+    for (int c = 0; c < 6; ++c) mean.v[c] += R[c];
+  }
+  if (op.willot) {
+    const WillotTables wt = willot_tables();   // (built on first use, outside the slot)
+    time_begin(5);
+    launch_gamma_willot(g_, ptrs6(tau_), wt, op.mu, op.lambda, op.alpha, op.beta, mean, op.sums, op.sums_scale, stream_);
+    time_end(5);
+  } else {
     XiTables xt;
     for (int a = 0; a < 3; ++a) xt.xi[a] = xi_[a];
-    Vec6 Ev;
-    for (int c = 0; c < 6; ++c) Ev.v[c] = E6[c];
-    if (!(frobenius(BC_MQ_) < kEps) || opt_.bc_relax != 1.0) {
-      // mixed boundary conditions: F0 = Re tau_hat(0) (initBCProjector(tau_hat) F:20219-20225; the forward transform is
-      // scaled, so this is the mean of tau), and the zero frequency of eta_hat becomes E + R (applyBCProjector(eta_hat,
-      // alpha) F:20272-20279) -- the Fourier kernel sets it to the value handed in
-      double F0[6], t1[6], t2[6], t3[6];
-      for (int c = 0; c < 6; ++c)
-        FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean + c, tau_ + (long)c * g_.n, sizeof(double), hipMemcpyDeviceToHost, stream_));
-      FG_HIP_CHECK(hipStreamSynchronize(stream_));
-      for (int c = 0; c < 6; ++c) F0[c] = hscal_[kSlotMean + c];
-      voigt_mv(BC_MQ_, F0, t1);
-      voigt_mv(BC_QC0_, F00_, t2);
-      voigt_mv(BC_M_, t2, t3);
-      for (int c = 0; c < 6; ++c) Ev.v[c] += alpha * (opt_.bc_relax * t1[c] - (1 - opt_.bc_relax) * t3[c]);
-    }
-    const double c10 = alpha / (4 * opt_.mu_0);
-    const double c20 = -alpha / (opt_.mu_0 * (1 + opt_.mu_0 / (opt_.lambda_0 + opt_.mu_0)));
+    const double c10 = op.alpha / (4 * op.mu);
+    const double c20 = -op.alpha / (op.mu * (1 + op.mu / (op.lambda + op.mu)));
     time_begin(5);
-    launch_gamma_collocated(g_, ptrs6(tau_), xt, c10, c20, 0.0, Ev, stream_);
+    launch_gamma_collocated(g_, ptrs6(tau_), xt, c10, c20, op.beta, mean, stream_, op.sums, op.sums_scale);
     time_end(5);
-    time_begin(8);
-    fft_->inverse(tau_, 6, g_.n);
-    time_end(8);
-    time_begin(9);
-    launch_copy(tau_, dst, 6 * g_.n, stream_);
-    launch_sum6(g_, ptrs6(dst), true, partial_, dscal_ + kSlotSumSq, stream_);
-    time_end(9);
-    if (timing_) times_.count++;
-    u_valid_ = false;
-    if (dst == eps_) eps_stale_ = false;
-    for (int c = 0; c < 6; ++c) E_cur_[c] = E6[c];
-    return;
   }
+  time_begin(8);
+  fft_->inverse(tau_, 6, g_.n);
+  time_end(8);
+  time_begin(9);
+  if (xpay) {
+    const double* in[2] = {tau_, dst};
+    const double w[2] = {1.0, *xpay};
+    launch_lincomb(2, in, w, dst, 6 * g_.n, stream_);
+  } else {
+    launch_copy(tau_, dst, 6 * g_.n, stream_);
+  }
+  launch_sum6(g_, ptrs6(dst), true, partial_, dscal_ + kSlotSumSq, stream_);
+  time_end(9);
+}
 
+// GammaOperatorCollocated  F:20302-20310: fftTensor, initBCProjector, Gamma0_hat, applyBCProjector, fftInvTensor on the
+// six components
+void Solver::pass_collocated(const double* E6, double* src, double* dst) {
+  time_begin(0);
+  stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), src);
+  time_end(0);
+  GammaHat op = {false, opt_.mu_0, opt_.lambda_0, -1.0, 0.0, {}, mixed_bc() || opt_.bc_relax != 1.0, nullptr, 0.0};
+  for (int c = 0; c < 6; ++c) op.mean.v[c] = E6[c];
+  fourier_pass6(op, dst);
+  pass_done(E6, dst, false);
+}
+
+// GammaOperatorStaggered  F:20288-20300:  tau = (C - C0):eps ; f = div tau ; u = G0 f ; eps = E + sym grad u (+ R)
+void Solver::pass_staggered(const double* E6, double* src, double* dst) {
+  const double alpha = -1.0;  // GammaOperator(..., -1)  F:20575
+  const StressParams sp = stress_params(opt_.mu_0, opt_.lambda_0, 1.0);
   // initBCProjector  F:20228-20239 needs <tau> only for mixed boundary conditions
   double F0[6] = {0, 0, 0, 0, 0, 0};
-  const bool mq_zero = frobenius(BC_MQ_) < kEps;
+  const bool mixed = mixed_bc();
   // Voigt mixing: polarisation and divergence in one sweep (tau never stored); the laminate rule keeps the
   // two-kernel form (its per-voxel Newton solve is too costly to repeat at the six neighbours)
   // (general phases: both fused forms evaluate the polarisation from (mu, lambda) -- the stored-polarisation form serves them)
-  const bool fuse_sd = opt_.fuse_stress_div && opt_.mixing == kMixVoigt && mq_zero && !dfg() && !general_phase();
+  const bool fuse_sd = opt_.fuse_stress_div && opt_.mixing == kMixVoigt && !mixed && !dfg() && !general_phase();
   // with the fast kernels allowed (u_loop = 2) the LDS-tiled form takes over where the grid fits; it also delivers
   // the sums of tau, so mixed boundary conditions keep the fused sweep
   const bool tile_sd = opt_.fuse_stress_div && opt_.mixing == kMixVoigt && opt_.u_loop >= 2 && u_tile_supported(g_) && !general_phase();
@@ -874,52 +896,37 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
       launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), effective_moduli(), ptrs3(fu_), partial_, dscal_ + kSlotMean,
                       stream_);
     time_end(0);
-    if (!mq_zero) {
-      FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean, dscal_ + kSlotMean, 6 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-      FG_HIP_CHECK(hipStreamSynchronize(stream_));
-      for (int c = 0; c < 6; ++c) F0[c] = hscal_[kSlotMean + c] / (double)nglobal_;
-    }
+    if (mixed) fetch_mean6(F0);
   } else if (fuse_sd) {
     time_begin(0);
-    launch_stress_div_voigt(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs6(src), phi, ptrs3(fu_), stream_);
+    launch_stress_div_voigt(g_, sp, ptrs6(src), phase_ptrs(), ptrs3(fu_), stream_);
     time_end(0);
   } else {
     time_begin(0);
-    stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), src, phi, nrm);
+    stress_to_tau(sp, src);
     time_end(0);
-    if (!mq_zero) {
+    if (mixed) {
       launch_sum6(g_, ptrs6(tau_), false, partial_, dscal_ + kSlotMean, stream_);
-      FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean, dscal_ + kSlotMean, 6 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-      FG_HIP_CHECK(hipStreamSynchronize(stream_));
-      for (int c = 0; c < 6; ++c) F0[c] = hscal_[kSlotMean + c] / (double)nglobal_;
+      fetch_mean6(F0);
     }
     time_begin(1);
-    launch_div(g_, ptrs6(tau_), ptrs3(fu_), XHalo{{nullptr, nullptr}, {nullptr, nullptr}}, stream_);
+    launch_div(g_, ptrs6(tau_), ptrs3(fu_), kNoXHalo, stream_);
     time_end(1);
   }
-  fft_g0_chain(fu_, -1.0, nullptr, tau_);   // the polarisation is dead once its divergence is taken
+  fft_g0_chain(fu_, alpha, nullptr, tau_);   // the polarisation is dead once its divergence is taken
 
-  // applyBCProjector  F:20247-20270: R = alpha*(bc_relax*MQ:F0 - (1-bc_relax)*M:(QC0:F00))
+  // applyBCProjector  F:20247-20270
   Vec6 E, R;
-  double t1[6], t2[6], t3[6];
-  voigt_mv(BC_MQ_, F0, t1);
-  voigt_mv(BC_QC0_, F00_, t2);
-  voigt_mv(BC_M_, t2, t3);
+  for (int c = 0; c < 6; ++c) E.v[c] = E6[c], R.v[c] = 0.0;
+  if (mixed || opt_.bc_relax != 1.0) bc_correction(BC_MQ_, BC_M_, BC_QC0_, opt_.bc_relax, alpha, F0, F00_, R.v);
   bool add_R = false;
-  for (int c = 0; c < 6; ++c) {
-    E.v[c] = E6[c];
-    R.v[c] = mq_zero && opt_.bc_relax == 1.0 ? 0.0 : alpha * (opt_.bc_relax * t1[c] - (1 - opt_.bc_relax) * t3[c]);
+  for (int c = 0; c < 6; ++c)
     if (R.v[c] != 0.0) add_R = true;
-  }
   time_begin(9);
-  launch_eps_norm(g_, ptrs3(fu_), ptrs6(dst), E, R, add_R, partial_, dscal_ + kSlotSumSq,
-                  XHalo{{nullptr, nullptr}, {nullptr, nullptr}}, stream_);
+  launch_eps_norm(g_, ptrs3(fu_), ptrs6(dst), E, R, add_R, partial_, dscal_ + kSlotSumSq, kNoXHalo, stream_);
   time_end(9);
-  if (timing_) times_.count++;
   // fu_ now holds the displacement this strain was built from (eps = E + sym grad u when R == 0)
-  u_valid_ = !add_R && dst == eps_;
-  if (dst == eps_) eps_stale_ = false;
-  for (int c = 0; c < 6; ++c) E_cur_[c] = E6[c];
+  pass_done(E6, dst, !add_R && dst == eps_);
 }
 
 // GammaOperatorFourierWillotR  F:19130-19152: tan(q / 2) / (4 w) and 1 + e^{iq} per axis, host libm; built and uploaded on
@@ -948,72 +955,31 @@ WillotTables Solver::willot_tables() {
 // scheme.  Viscosity: DeltaOperatorWillotR  F:20380-20418: m = 1 / (4 mu0); adj = E - 2 alpha m <tau>;
 // eta = GammaWillotR(adj; mu = -1 / (4 m), lambda = inf)(tau) + 2 alpha m tau_copy -- tau_copy lives in dst (the strain the
 // polarisation was made from is dead by then), <tau> stays on the device as in the staggered Delta path.
-void Solver::willot_scheme(const double* E6, double* src, double* dst, const FieldPtrs<kMaxPhases>& phi, const FieldPtrs<3>& nrm) {
+void Solver::willot_scheme(const double* E6, double* src, double* dst) {
   const double alpha = -1.0;  // GammaOperator(..., -1)  F:20575
   const bool visc = opt_.mode == 2;
-  const bool mixed_bc = !(frobenius(BC_MQ_) < kEps);
   const double m = visc ? 1 / (4 * opt_.mu_0) : 0.0;
-  const WillotTables wt = willot_tables();
-  Vec6 Ev;
-  for (int c = 0; c < 6; ++c) Ev.v[c] = E6[c];
   time_begin(0);
-  stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), src, phi, nrm);
+  stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), src);
   time_end(0);
-  if (visc) {
-    launch_sum6(g_, ptrs6(tau_), false, partial_, dscal_ + kSlotMean, stream_);   // tau_copy->average(), stays on the device
-    if (mixed_bc) {   // applyBCProjector(eta_hat, alpha): R = alpha MQ <tau> folded into the sums, as in the staggered Delta path
-      Mat36 B;
-      for (int j = 0; j < 6; ++j) {
-        double e[6] = {0, 0, 0, 0, 0, 0}, col[6];
-        e[j] = 1.0;
-        voigt_mv(BC_MQ_, e, col);
-        for (int c = 0; c < 6; ++c) B.a[c * 6 + j] = col[c];
-      }
-      hipLaunchKernelGGL(k_bc_adjust_sums, dim3(1), dim3(64), 0, stream_, dscal_ + kSlotMean, B, alpha / (2 * alpha * m));
-      FG_HIP_CHECK(hipGetLastError());
-    }
-    launch_copy(tau_, dst, 6 * g_.n, stream_);   // tau_copy
-  }
-  time_begin(2);
-  fft_->forward(tau_, 6, g_.n, 1 / (double)nglobal_);   // fftTensor: 1/N on the forward transform  F:18531-18560
-  time_end(2);
-  if (!visc && (mixed_bc || opt_.bc_relax != 1.0)) {
-    // F0 = Re tau_hat(0) (initBCProjector(tau_hat) F:20219-20225), the zero frequency of eta_hat becomes E + R
-    // (applyBCProjector(eta_hat, alpha) F:20272-20279), as in the collocated branch of basic_scheme
-    double F0[6], t1[6], t2[6], t3[6];
-    for (int c = 0; c < 6; ++c)
-      FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean + c, tau_ + (long)c * g_.n, sizeof(double), hipMemcpyDeviceToHost, stream_));
-    FG_HIP_CHECK(hipStreamSynchronize(stream_));
-    for (int c = 0; c < 6; ++c) F0[c] = hscal_[kSlotMean + c];
-    voigt_mv(BC_MQ_, F0, t1);
-    voigt_mv(BC_QC0_, F00_, t2);
-    voigt_mv(BC_M_, t2, t3);
-    for (int c = 0; c < 6; ++c) Ev.v[c] += alpha * (opt_.bc_relax * t1[c] - (1 - opt_.bc_relax) * t3[c]);
-  }
-  time_begin(5);
-  if (visc)
-    launch_gamma_willot(g_, ptrs6(tau_), wt, -1.0 / (4 * m), INFINITY, alpha, 0.0, Ev, dscal_ + kSlotMean,
-                        -(2 * alpha * m) / (double)nglobal_, stream_);
-  else
-    launch_gamma_willot(g_, ptrs6(tau_), wt, opt_.mu_0, opt_.lambda_0, alpha, 0.0, Ev, nullptr, 0.0, stream_);
-  time_end(5);
-  time_begin(8);
-  fft_->inverse(tau_, 6, g_.n);
-  time_end(8);
-  time_begin(9);
-  if (visc) {   // eta.xpay(eta, 2 alpha m, tau_copy)  F:20411
-    const double* in[2] = {tau_, dst};
-    const double w[2] = {1.0, 2 * alpha * m};
-    launch_lincomb(2, in, w, dst, 6 * g_.n, stream_);
+  GammaHat op = {true, opt_.mu_0, opt_.lambda_0, alpha, 0.0, {}, mixed_bc() || opt_.bc_relax != 1.0, nullptr, 0.0};
+  for (int c = 0; c < 6; ++c) op.mean.v[c] = E6[c];
+  if (!visc) {
+    fourier_pass6(op, dst);
   } else {
-    launch_copy(tau_, dst, 6 * g_.n, stream_);
+    launch_sum6(g_, ptrs6(tau_), false, partial_, dscal_ + kSlotMean, stream_);   // tau_copy->average(), stays on the device
+    // applyBCProjector(eta_hat, alpha): R = alpha MQ <tau> folded into the sums, as in the staggered Delta path
+    if (mixed_bc()) bc_adjust_sums(alpha / (2 * alpha * m));
+    launch_copy(tau_, dst, 6 * g_.n, stream_);   // tau_copy
+    op.mu = -1.0 / (4 * m);
+    op.lambda = INFINITY;
+    op.bc = false;
+    op.sums = dscal_ + kSlotMean;
+    op.sums_scale = -(2 * alpha * m) / (double)nglobal_;
+    const double xpay = 2 * alpha * m;   // eta.xpay(eta, 2 alpha m, tau_copy)  F:20411
+    fourier_pass6(op, dst, &xpay);
   }
-  launch_sum6(g_, ptrs6(dst), true, partial_, dscal_ + kSlotSumSq, stream_);
-  time_end(9);
-  if (timing_) times_.count++;
-  u_valid_ = false;
-  if (dst == eps_) eps_stale_ = false;
-  for (int c = 0; c < 6; ++c) E_cur_[c] = E6[c];
+  pass_done(E6, dst, false);
 }
 
 // z and y transforms of a plane in one kernel (grids whose complex z-y plane fits the LDS): option plane_fft (-1 = where
@@ -1022,220 +988,87 @@ bool Solver::plane_fft_on() const {
   return opt_.plane_fft != 0 && nranks_ == 1 && fft_->can_plane();
 }
 
-// One chunked pair of the transform chain: first(c) then second(c) for runs c of `pc` x planes.
-template <class A, class B>
-void Solver::run_pairs(int pc, A first, B second) {
-  for (int x0 = 0; x0 < g_.nx; x0 += pc) {
-    const int np = std::min(pc, g_.nx - x0);
-    first(x0, np);
-    second(x0, np);
-  }
-}
-
-void Solver::fft_g0_chain(double* buf, double alpha, const double* c12, double* xscratch) {  // alpha = -1: GammaOperator(..., -1)  F:20575
+// The transform chain of a pass on buf (one component in the scalar modes, else three): the decisions, made once, and the
+// Green operator's constants; g0_chain (fg_g0_chain.h) has the schedule and the timing slots.
+// alpha = -1: GammaOperator(..., -1)  F:20575
+void Solver::fft_g0_chain(double* buf, double alpha, const double* c12, double* xscratch) {
   fft_->set_joint_x(opt_.joint_x != 0);
-  if (opt_.mode == 1) {
-    // G0OperatorStaggeredHeat  F:20118-20135 on one component: fftVector(., 1), c1 = c10/|k|^2, fftInvVector
-    const double scale = 1 / (double)nglobal_;
-    const bool has_x = g_.nx > 1, has_y = g_.ny > 1;
-    const bool plane = plane_fft_on() && has_x;
-    const int pc1 = pair_chunk_planes(1);
-    if (plane) {
-      time_begin(2);
-      fft_->zy_plane(buf, 1, g_.n, -1);
-      time_end(2);
-    } else if (pc1) {
-      time_begin(2);
-      run_pairs(pc1, [&](int x0, int np) { const PlaneWindow w = {x0, np}; fft_->r2c_z(buf, 1, g_.n, &w); },
-                [&](int x0, int np) { const PlaneWindow w = {x0, np}; fft_->c2c_y(buf, 1, g_.n, -1, 1.0, &w); });
-      time_end(2);
-    } else {
-      time_begin(2);
-      fft_->r2c_z(buf, 1, g_.n);
-      time_end(2);
-      time_begin(3);
-      fft_->c2c_y(buf, 1, g_.n, -1, (has_x || !has_y) ? 1.0 : scale);
-      time_end(3);
-    }
-    const double c10 = -alpha / (2 * opt_.mu_0);  // G0OperatorFourierStaggeredHeat  F:19759-19764
-    if (opt_.fuse_x && fft_->can_fuse(0, 1) && has_x) {
-      // x transform, 1/N, scalar Green operator and inverse x transform in one kernel
-      G0Params gp;
-      for (int a = 0; a < 3; ++a) gp.kpm[a] = g0_kpm_[a], gp.kp[a] = g0_kp_[a];
-      gp.c10 = c10;
-      gp.c20 = 0.0;
-      gp.inv_h0 = 2.0 * nxg_ / g_.dx;
-      time_begin(5);
-      fft_->fused_g0(buf, g_.n, 0, scale, gp, 0, 1);
-      time_end(5);
-    } else {
-      time_begin(4);
-      fft_->c2c_x(buf, 1, g_.n, -1, has_x ? scale : 1.0);
-      time_end(4);
-      if (!has_x && !has_y) fft_->scale(buf, 1, g_.n, scale);
-      G0Tables tb;
-      for (int a = 0; a < 3; ++a) {
-        tb.kpm[a] = g0_kpm_[a];
-        tb.kp[a] = g0_kp_[a];
-      }
-      time_begin(5);
-      launch_g0_heat(g_, buf, tb, c10, stream_);
-      time_end(5);
-      time_begin(6);
-      fft_->c2c_x(buf, 1, g_.n, +1, 1.0);
-      time_end(6);
-    }
-    if (plane) {
-      time_begin(8);
-      fft_->zy_plane(buf, 1, g_.n, +1);
-      time_end(8);
-      return;
-    }
-    if (pc1) {
-      time_begin(7);
-      run_pairs(pc1, [&](int x0, int np) { const PlaneWindow w = {x0, np}; fft_->c2c_y(buf, 1, g_.n, +1, 1.0, &w); },
-                [&](int x0, int np) { const PlaneWindow w = {x0, np}; fft_->c2r_z(buf, 1, g_.n, &w); });
-      time_end(7);
-      return;
-    }
-    time_begin(7);
-    fft_->c2c_y(buf, 1, g_.n, +1, 1.0);
-    time_end(7);
-    time_begin(8);
-    fft_->c2r_z(buf, 1, g_.n);
-    time_end(8);
-    return;
-  }
-  bool fuse_x = false, plane = false;
+  const bool scalar = opt_.mode == 1;
+  G0ChainPlan p;
+  p.ncomp = scalar ? 1 : 3;
+  p.nx = g_.nx;
+  p.has_x = g_.nx > 1;
+  p.has_y = g_.ny > 1;
+  p.scale = 1 / (double)nglobal_;
   // x-contiguous layout for the fused pass: on by size (fields beyond the Infinity Cache, where the fused pass's tile of nx
   // segments 2 MB apart is what bounds it) unless the option x_layout says otherwise
   const int xl_opt = opt_.x_layout;
-  const bool xl = xscratch && opt_.fuse_x && fft_->can_fuse(0) && fft_->can_xlayout() && g_.nx > 1 && g_.ny > 1 &&
-                  (xl_opt > 0 || (xl_opt < 0 && 3.0 * (double)g_.n * sizeof(double) > 1024.0 * 1024 * 1024));
-  const int pc = pair_chunk_planes(3);
-  if (xl) {
-    if (pc) {   // r2c(c) -> y(c) per run of x planes: the spectrum of a chunk is still in the Infinity Cache when the y pass reads it
-      time_begin(2);
-      run_pairs(pc, [&](int x0, int np) { const PlaneWindow w = {x0, np}; fft_->r2c_z(buf, 3, g_.n, &w); },
-                [&](int x0, int np) { const PlaneWindow w = {x0, np}; fft_->c2c_y_xlayout(buf, g_.n, xscratch, g_.n, 3, -1, 1.0, &w); });
-      time_end(2);
-    } else {
-      time_begin(2);
-      fft_->r2c_z(buf, 3, g_.n);
-      time_end(2);
-      time_begin(3);
-      fft_->c2c_y_xlayout(buf, g_.n, xscratch, g_.n, 3, -1, 1.0);
-      time_end(3);
-    }
-    G0Params gp;
-    gp.c10 = -alpha / (opt_.mu_0);
-    gp.c20 = -alpha / (opt_.mu_0 * (1 + opt_.mu_0 / (opt_.lambda_0 + opt_.mu_0)));
-    gp.inv_h0 = 2.0 * nxg_ / g_.dx;
-    if (c12) gp.c10 = c12[0], gp.c20 = c12[1];
-    for (int a = 0; a < 3; ++a) gp.kpm[a] = g0_kpm_[a], gp.kp[a] = g0_kp_[a];
-    time_begin(5);
-    fft_->fused_g0(xscratch, g_.n, 0, 1 / (double)nglobal_, gp, 0, 3, 31, 0, true);
-    time_end(5);
-    if (pc) {
-      time_begin(7);
-      run_pairs(pc, [&](int x0, int np) { const PlaneWindow w = {x0, np}; fft_->c2c_y_xlayout(xscratch, g_.n, buf, g_.n, 3, +1, 1.0, &w); },
-                [&](int x0, int np) { const PlaneWindow w = {x0, np}; fft_->c2r_z(buf, 3, g_.n, &w); });
-      time_end(7);
-      return;
-    }
-    time_begin(7);
-    fft_->c2c_y_xlayout(xscratch, g_.n, buf, g_.n, 3, +1, 1.0);
-    time_end(7);
-    time_begin(8);
-    fft_->c2r_z(buf, 3, g_.n);
-    time_end(8);
-    return;
+  p.xlayout = !scalar && xscratch && opt_.fuse_x && fft_->can_fuse(0) && fft_->can_xlayout() && p.has_x && p.has_y &&
+              (xl_opt > 0 || (xl_opt < 0 && 3.0 * (double)g_.n * sizeof(double) > 1024.0 * 1024 * 1024));
+  p.plane = !p.xlayout && plane_fft_on() && p.has_x;   // small grids
+  p.pair_chunk = pair_chunk_planes();                  // (0 where the plane kernel is on)
+  p.fuse_x = opt_.fuse_x && fft_->can_fuse(0, p.ncomp);   // (no length-1 x pass is fusable: has_x need not be asked)
+  if (scalar) {
+    p.c10 = -alpha / (2 * opt_.mu_0);  // G0OperatorFourierStaggeredHeat  F:19759-19764
+    p.c20 = 0.0;
+  } else {
+    p.c10 = -alpha / (opt_.mu_0);      // G0OperatorFourierStaggered  F:19749-19755
+    p.c20 = -alpha / (opt_.mu_0 * (1 + opt_.mu_0 / (opt_.lambda_0 + opt_.mu_0)));
+    if (c12) p.c10 = c12[0], p.c20 = c12[1];
   }
-  {
-    // fftVector  F:18481-18510: r2c in z, c2c in y, c2c in x; the 1/N of F:18501-18506 rides on the last pass
-    const double scale = 1 / (double)nglobal_;
-    const bool has_x = g_.nx > 1, has_y = g_.ny > 1;
-    plane = plane_fft_on() && has_x;
-    if (plane) {   // small grids: z and y transforms of a plane in one kernel
-      time_begin(2);
-      fft_->zy_plane(buf, 3, g_.n, -1);
-      time_end(2);
-    } else if (pc) {
-      time_begin(2);
-      run_pairs(pc, [&](int x0, int np) { const PlaneWindow w = {x0, np}; fft_->r2c_z(buf, 3, g_.n, &w); },
-                [&](int x0, int np) { const PlaneWindow w = {x0, np}; fft_->c2c_y(buf, 3, g_.n, -1, 1.0, &w); });
-      time_end(2);
-    } else {
-      time_begin(2);
-      fft_->r2c_z(buf, 3, g_.n);
-      time_end(2);
-      time_begin(3);
-      fft_->c2c_y(buf, 3, g_.n, -1, (has_x || !has_y) ? 1.0 : scale);
-      time_end(3);
-    }
-    fuse_x = opt_.fuse_x && fft_->can_fuse(0);
-    if (!fuse_x) {
-      time_begin(4);
-      fft_->c2c_x(buf, 3, g_.n, -1, has_x ? scale : 1.0);
-      time_end(4);
-      if (!has_x && !has_y) fft_->scale(buf, 3, g_.n, scale);
-    }
+  g0_chain(*this, p, buf, xscratch);
+}
+
+// the passes g0_chain calls back; a window (x0, np) with np < 0 is the whole field
+void Solver::chain_r2c_z(double* buf, int ncomp, int x0, int np) {
+  const PlaneWindow w = {x0, np};
+  fft_->r2c_z(buf, ncomp, g_.n, np < 0 ? nullptr : &w);
+}
+void Solver::chain_c2r_z(double* buf, int ncomp, int x0, int np) {
+  const PlaneWindow w = {x0, np};
+  fft_->c2r_z(buf, ncomp, g_.n, np < 0 ? nullptr : &w);
+}
+void Solver::chain_c2c_y(double* buf, int ncomp, int dir, double scale, int x0, int np) {
+  const PlaneWindow w = {x0, np};
+  fft_->c2c_y(buf, ncomp, g_.n, dir, scale, np < 0 ? nullptr : &w);
+}
+void Solver::chain_c2c_y_xlayout(double* in, double* out, int ncomp, int dir, int x0, int np) {
+  const PlaneWindow w = {x0, np};
+  fft_->c2c_y_xlayout(in, g_.n, out, g_.n, ncomp, dir, 1.0, np < 0 ? nullptr : &w);
+}
+void Solver::chain_c2c_x(double* buf, int ncomp, int dir, double scale) { fft_->c2c_x(buf, ncomp, g_.n, dir, scale); }
+void Solver::chain_zy_plane(double* buf, int ncomp, int dir) { fft_->zy_plane(buf, ncomp, g_.n, dir); }
+void Solver::chain_scale(double* buf, int ncomp, double scale) { fft_->scale(buf, ncomp, g_.n, scale); }
+
+// x transform, 1/N, Green operator and inverse x transform in one kernel (spectrum stays in registers)
+void Solver::chain_fused_x(double* data, int ncomp, double scale, double c10, double c20, bool xlayout) {
+  G0Params gp;
+  for (int a = 0; a < 3; ++a) gp.kpm[a] = g0_kpm_[a], gp.kp[a] = g0_kp_[a];
+  gp.c10 = c10;
+  gp.c20 = c20;
+  gp.inv_h0 = 2.0 * nxg_ / g_.dx;
+  fft_->fused_g0(data, g_.n, 0, scale, gp, 0, ncomp, 31, 0, xlayout);   // (xsplit 31, xjump 0: the defaults, no slab layout)
+}
+
+void Solver::chain_green(double* buf, int ncomp, double c10, double c20) {
+  G0Tables tb;
+  for (int a = 0; a < 3; ++a) {
+    tb.kpm[a] = g0_kpm_[a];
+    tb.kp[a] = g0_kp_[a];
   }
-  {
-    // G0OperatorFourierStaggered  F:19749-19755
-    G0Params gp;
-    gp.c10 = -alpha / (opt_.mu_0);
-    gp.c20 = -alpha / (opt_.mu_0 * (1 + opt_.mu_0 / (opt_.lambda_0 + opt_.mu_0)));
-    gp.inv_h0 = 2.0 * nxg_ / g_.dx;
-    if (c12) gp.c10 = c12[0], gp.c20 = c12[1];
-    G0Tables tb;
-    for (int a = 0; a < 3; ++a) {
-      tb.kpm[a] = gp.kpm[a] = g0_kpm_[a];
-      tb.kp[a] = gp.kp[a] = g0_kp_[a];
-    }
-    time_begin(5);
-    if (fuse_x) {
-      // x transform, 1/N, Green operator and inverse x transform in one kernel (spectrum stays in registers)
-      fft_->fused_g0(buf, g_.n, 0, 1 / (double)nglobal_, gp, 0);
-    } else {
-      launch_g0(g_, ptrs3(buf), tb, gp.c10, gp.c20, G0Layout{0, 0, 0}, stream_);
-    }
-    time_end(5);
-  }
-  if (!fuse_x) {
-    time_begin(6);
-    fft_->c2c_x(buf, 3, g_.n, +1, 1.0);
-    time_end(6);
-  }
-  if (plane) {
-    time_begin(8);
-    fft_->zy_plane(buf, 3, g_.n, +1);
-    time_end(8);
-    return;
-  }
-  if (pc) {
-    time_begin(7);
-    run_pairs(pc, [&](int x0, int np) { const PlaneWindow w = {x0, np}; fft_->c2c_y(buf, 3, g_.n, +1, 1.0, &w); },
-              [&](int x0, int np) { const PlaneWindow w = {x0, np}; fft_->c2r_z(buf, 3, g_.n, &w); });
-    time_end(7);
-    return;
-  }
-  time_begin(7);
-  fft_->c2c_y(buf, 3, g_.n, +1, 1.0);
-  time_end(7);
-  time_begin(8);
-  fft_->c2r_z(buf, 3, g_.n);
-  time_end(8);
+  if (ncomp == 1) launch_g0_heat(g_, buf, tb, c10, stream_);   // G0OperatorStaggeredHeat  F:20118-20135: c1 = c10 / |k|^2
+  else launch_g0(g_, ptrs3(buf), tb, c10, c20, G0Layout{0, 0, 0}, stream_);
 }
 
 // Planes per chunk of the paired z / y passes (0 = whole-field passes, the default).  Measured in round 6 and NOT faster:
 // a bytes-only pair of copy passes gains 1.32 x from 128-MB chunks (tools/mall_chunk_probe.hip), the transform passes lose
 // 3-10 % at every chunk size (EXPERIMENTS.md, round 6) -- they are bound by the requests a workgroup keeps in flight, which an
 // Infinity-Cache hit does not shorten.  Kept as an option: same kernels on the same lines, bit-identical iterates.
-int Solver::pair_chunk_planes(int) const {
+int Solver::pair_chunk_planes() const {
   if (opt_.pair_chunk <= 0 || !fft_->can_window() || g_.nx < 2 || g_.ny < 2 || plane_fft_on()) return 0;
   return std::min(opt_.pair_chunk, g_.nx);
 }
+
 
 // ------------------------------------------------------------------ displacement-based pass
 // eps_k = E + sym grad u_k is implied by the displacement of the previous pass, so the loop can carry
@@ -1261,13 +1094,19 @@ FieldPtrs<kMaxPhases> Solver::phase_ptrs() const {
   return phi;
 }
 
+FieldPtrs<3> Solver::normal_ptrs() const {
+  FieldPtrs<3> nrm;
+  for (int c = 0; c < 3; ++c) nrm.p[c] = normals_ ? normals_ + (long)c * g_.n : nullptr;
+  return nrm;
+}
+
 bool Solver::u_loop_eligible(bool allow_mixed_bc) {
   if (opt_.mode == 1) {
     // the scalar modes only have the potential-based loop
     if (nranks_ != 1) throw std::runtime_error("heat / porous mode is not available on slab-decomposed solvers");
     if (opt_.mixing != kMixVoigt) throw std::runtime_error("heat / porous mode supports Voigt mixing only");
     if (opt_.bc_relax != 1.0) throw std::runtime_error("heat / porous mode does not support bc_relax != 1");
-    if (frobenius(BC_MQ_) >= kEps && !allow_mixed_bc)
+    if (mixed_bc() && !allow_mixed_bc)
       throw std::runtime_error("heat / porous mode: mixed boundary conditions run with method=basic (fg_run_load_case) only");
     return pt_.n >= 1;
   }
@@ -1280,7 +1119,7 @@ bool Solver::u_loop_eligible(bool allow_mixed_bc) {
   if (!(opt_.u_loop && opt_.mode == 0 && scheme_ok && nranks_ == 1 && pt_.n >= 1 &&
         (opt_.mixing == kMixVoigt || (opt_.mixing == kMixLaminate && normals_)) && opt_.bc_relax == 1.0))
     return false;
-  if (frobenius(BC_MQ_) < kEps) return true;
+  if (!mixed_bc()) return true;
   // mixed boundary conditions: <tau> of every pass corrects the prescribed mean of the next one; the tiled Voigt sweep
   // delivers it with the norms (run() only: the correction needs the host between passes)
   return allow_mixed_bc && opt_.u_loop >= 2 && opt_.u_tile && u_tile_supported(g_);   // Voigt, or laminate as its correction
@@ -1400,15 +1239,14 @@ FieldPtrs<5> Solver::dfg_moduli() {
   return mod;
 }
 
-void Solver::stress_to_tau(const StressParams& sp, double* src, const FieldPtrs<kMaxPhases>& phi, const FieldPtrs<3>& nrm) {
+void Solver::stress_to_tau(const StressParams& sp, double* src) {
   if (dfg()) launch_dfg_stress(0, g_, sp, ptrs6(src), dfg_moduli(), ptrs6(tau_), nullptr, nullptr, stream_);
-  else launch_stress(g_, sp, ptrs6(src), phi, nrm, ptrs6(tau_), derr_, stream_);
+  else launch_stress(g_, sp, ptrs6(src), phase_ptrs(), normal_ptrs(), ptrs6(tau_), derr_, stream_);
 }
 
 void Solver::build_laminate_lists() {
   if (!mixed_dirty_) return;
-  FieldPtrs<kMaxPhases> phi;
-  for (int q = 0; q < kMaxPhases; ++q) phi.p[q] = q < pt_.n ? phi_ + (long)q * g_.n : nullptr;
+  const FieldPtrs<kMaxPhases> phi = phase_ptrs();
   for (void* p : {(void*)mixed_list_, (void*)aff_list_, (void*)aff_slots_, (void*)dtau_})
     if (p) FG_HIP_CHECK(hipFree(p));
   mixed_list_ = aff_list_ = nullptr;
@@ -1426,9 +1264,7 @@ void Solver::build_laminate_lists() {
     FG_HIP_CHECK(hipMalloc(&lam_phic_, n * pt_.n * sizeof(double)));
     FG_HIP_CHECK(hipMalloc(&lam_nrmc_, n * 3 * sizeof(double)));
     FG_HIP_CHECK(hipMalloc(&lam_epsc_, n * 6 * sizeof(double)));
-    FieldPtrs<3> nrm;
-    for (int c = 0; c < 3; ++c) nrm.p[c] = normals_ ? normals_ + (long)c * g_.n : nullptr;
-    launch_interface_static(g_, pt_.n, phi, nrm, mixed_list_, mixed_n_, lam_phic_, lam_nrmc_, stream_);
+    launch_interface_static(g_, pt_.n, phi, normal_ptrs(), mixed_list_, mixed_n_, lam_phic_, lam_nrmc_, stream_);
     // x-slab: no x neighbours across the slab faces in the slots (gu_: the grid with the slab's plane mapping)
     aff_n_ = launch_affected_list(slab_layout_ ? gu_ : g_, mixed_list_, mixed_n_, &aff_list_, &aff_slots_, stream_);
   }
@@ -1436,8 +1272,7 @@ void Solver::build_laminate_lists() {
 }
 
 void Solver::u_pass_front(const double* E6) {
-  FieldPtrs<kMaxPhases> phi;
-  for (int q = 0; q < kMaxPhases; ++q) phi.p[q] = q < pt_.n ? phi_ + (long)q * g_.n : nullptr;
+  const FieldPtrs<kMaxPhases> phi = phase_ptrs();
   // the strain that belongs to u_k was built with the prescribed strain of ITS pass (E_cur_);
   // E6 is the prescribed strain of the pass being started and takes effect with u_{k+1}
   Vec6 E;
@@ -1450,10 +1285,10 @@ void Solver::u_pass_front(const double* E6) {
     if (opt_.u_loop >= 2 && !aniso_phase()) {
       // fast variant: effective conductivity a = sum_p phi_p mu_p precomputed (first moduli array); an aniso phase has no
       // such array and takes the exact-order sweep's 13-point form
-      const bool mixed = !(frobenius(BC_MQ_) < kEps) && in_run_;
+      const bool mixed = mixed_bc() && in_run_;
       sc_tau_sums_ = launch_sc_sweep_fast(g_, opt_.mu_0, fu_, effective_moduli().p[0], fu_alt_, E, partial_, dscal_ + kSlotSumSq,
                                           stream_, mixed ? dscal_ + kSlotMean : nullptr);
-    } else if (sc_tile_aniso_ok(!(frobenius(BC_MQ_) < kEps) && in_run_)) {
+    } else if (sc_tile_aniso_ok(mixed_bc() && in_run_)) {
       double K0[6], K1[6];
       sc_aniso_constants(K0, K1);
       sc_tau_sums_ = false;
@@ -1465,13 +1300,11 @@ void Solver::u_pass_front(const double* E6) {
     }
   } else if (opt_.mixing != kMixVoigt && opt_.u_loop < 2) {
     // laminate mixing, exact order: strain + polarisation from u in one sweep (tau stored), divergence as its own sweep
-    FieldPtrs<3> nrm;
-    for (int c = 0; c < 3; ++c) nrm.p[c] = normals_ ? normals_ + (long)c * g_.n : nullptr;
-    launch_u_stress(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs3(fu_), phi, nrm, ptrs6(tau_), E, partial_,
+    launch_u_stress(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs3(fu_), phi, normal_ptrs(), ptrs6(tau_), E, partial_,
                     dscal_ + kSlotSumSq, derr_, stream_);
     time_end(0);
     time_begin(1);
-    launch_div(g_, ptrs6(tau_), ptrs3(fu_alt_), XHalo{{nullptr, nullptr}, {nullptr, nullptr}}, stream_);
+    launch_div(g_, ptrs6(tau_), ptrs3(fu_alt_), kNoXHalo, stream_);
     time_end(1);
     eps_stale_ = true;
     return;
@@ -1493,7 +1326,7 @@ void Solver::u_pass_front(const double* E6) {
       }
     }
     if (opt_.u_tile && u_tile_supported(g_)) {
-      const bool sum_tau = !(frobenius(BC_MQ_) < kEps);   // mixed BC: sums of tau land in kSlotMean
+      const bool sum_tau = mixed_bc();   // mixed BC: sums of tau land in kSlotMean
       if (dfg()) {   // full_staggered: the five moduli, also for two complementary phases
         launch_u_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), dfg_moduli(), ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq,
                       stream_, sum_tau);
@@ -1521,8 +1354,6 @@ void Solver::u_pass_front(const double* E6) {
     if (laminate) {
       // laminate mixing = the Voigt sweep over all voxels + the divergence of (tau_laminate - tau_voigt), which lives
       // on the interface voxels (lists built once per geometry, see k_interface_strain)
-      FieldPtrs<3> nrm;
-      for (int c = 0; c < 3; ++c) nrm.p[c] = normals_ ? normals_ + (long)c * g_.n : nullptr;
       // d depends on u only: its two kernels (a light gather, a short solve) run on a second stream beside the sweep
       hipStream_t ds = opt_.laminate_overlap ? aux_stream_ : stream_;
       if (ds != stream_) FG_HIP_CHECK(hipStreamWaitEvent(ds, ev_fork_, 0));
@@ -1533,7 +1364,7 @@ void Solver::u_pass_front(const double* E6) {
         FG_HIP_CHECK(hipStreamWaitEvent(stream_, ev_join_, 0));
       }
       launch_delta_div(g_, aff_list_, aff_slots_, aff_n_, dtau_, ptrs3(fu_alt_), stream_);
-      if (!(frobenius(BC_MQ_) < kEps))   // mixed BC: <tau_laminate> = <tau_voigt> (from the sweep) + sum of the differences / N
+      if (mixed_bc())   // mixed BC: <tau_laminate> = <tau_voigt> (from the sweep) + sum of the differences / N
         launch_sum_dtau(dtau_, mixed_n_, partial_, dscal_ + kSlotScratch, stream_);
     }
   } else {
@@ -1565,7 +1396,7 @@ void Solver::ensure_eps() {
     return;
   }
   launch_eps_norm(g_, ptrs3(fu_), ptrs6(eps_), E, R, false, partial_, dscal_ + kSlotScratch,
-                  XHalo{{nullptr, nullptr}, {nullptr, nullptr}}, stream_);
+                  kNoXHalo, stream_);
   eps_stale_ = false;
 }
 
@@ -1618,17 +1449,13 @@ void Solver::mean_stress(double* out6) {
     for (int c = 0; c < 6; ++c) out6[c] = c < 3 ? hscal_[kSlotMean + c] : 0.0;
     return;
   }
-  FieldPtrs<kMaxPhases> phi;
-  for (int q = 0; q < kMaxPhases; ++q) phi.p[q] = q < pt_.n ? phi_ + (long)q * g_.n : nullptr;
-  FieldPtrs<3> nrm;
-  for (int c = 0; c < 3; ++c) nrm.p[c] = normals_ ? normals_ + (long)c * g_.n : nullptr;
   // meanPK1: alpha /= nxyz, accumulate  F:12318-12340
   if (dfg())
     launch_dfg_stress(1, g_, stress_params(0.0, 0.0, 1.0 / (double)nglobal_), ptrs6(eps_), dfg_moduli(), FieldPtrs<6>{}, partial_,
                       dscal_ + kSlotMean, stream_);
   else
-    launch_stress_mean(g_, stress_params(0.0, 0.0, 1.0 / (double)nglobal_), ptrs6(eps_), phi, nrm, partial_,
-                       dscal_ + kSlotMean, derr_, stream_);
+    launch_stress_mean(g_, stress_params(0.0, 0.0, 1.0 / (double)nglobal_), ptrs6(eps_), phase_ptrs(), normal_ptrs(),
+                       partial_, dscal_ + kSlotMean, derr_, stream_);
   FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean, dscal_ + kSlotMean, 6 * sizeof(double), hipMemcpyDeviceToHost, stream_));
   FG_HIP_CHECK(hipStreamSynchronize(stream_));
   for (int c = 0; c < 6; ++c) out6[c] = hscal_[kSlotMean + c];
@@ -1639,14 +1466,12 @@ double Solver::mean_energy() {
   ensure_eps();
   if (pt_.n < 1) throw std::runtime_error("No materials specified");
   if (opt_.mode == 1) throw std::runtime_error("the energy error estimator is not available in heat / porous mode");
-  FieldPtrs<3> nrm;
-  for (int c = 0; c < 3; ++c) nrm.p[c] = normals_ ? normals_ + (long)c * g_.n : nullptr;
   if (dfg())
     launch_dfg_stress(2, g_, stress_params(0.0, 0.0, 1.0), ptrs6(eps_), dfg_moduli(), FieldPtrs<6>{}, partial_, dscal_ + kSlotMean,
                       stream_);
   else
-    launch_energy_mean(g_, stress_params(0.0, 0.0, 1.0), ptrs6(eps_), phase_ptrs(), nrm, partial_, dscal_ + kSlotMean, derr_,
-                       stream_);
+    launch_energy_mean(g_, stress_params(0.0, 0.0, 1.0), ptrs6(eps_), phase_ptrs(), normal_ptrs(), partial_, dscal_ + kSlotMean,
+                       derr_, stream_);
   FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean, dscal_ + kSlotMean, sizeof(double), hipMemcpyDeviceToHost, stream_));
   FG_HIP_CHECK(hipStreamSynchronize(stream_));
   return hscal_[kSlotMean] / (double)nglobal_;
@@ -1680,9 +1505,7 @@ void Solver::mean_strain(double* out6) {
   FG_HIP_CHECK(hipSetDevice(device_));
   ensure_eps();
   launch_sum6(g_, ptrs6(eps_), false, partial_, dscal_ + kSlotMean, stream_);
-  FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean, dscal_ + kSlotMean, 6 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-  FG_HIP_CHECK(hipStreamSynchronize(stream_));
-  for (int c = 0; c < 6; ++c) out6[c] = hscal_[kSlotMean + c] / (double)nglobal_;
+  fetch_mean6(out6);
 }
 
 double Solver::volume_fraction(int p) {
@@ -1699,12 +1522,10 @@ void Solver::calc_ref_material() {
   FG_HIP_CHECK(hipSetDevice(device_));
   if (pt_.n < 1) throw std::runtime_error("No materials specified");
   general_check();
-  FieldPtrs<kMaxPhases> phi;
-  for (int q = 0; q < kMaxPhases; ++q) phi.p[q] = q < pt_.n ? phi_ + (long)q * g_.n : nullptr;
   if (opt_.mode == 1)
-    launch_sc_minmax(g_, scalar_params(0.0, 1.0), phi, partial_, dscal_ + kSlotMinMax, stream_);
+    launch_sc_minmax(g_, scalar_params(0.0, 1.0), phase_ptrs(), partial_, dscal_ + kSlotMinMax, stream_);
   else
-    launch_tangent_minmax(g_, phase_table(), opt_.mixing, phi, partial_, dscal_ + kSlotMinMax, derr_, stream_);
+    launch_tangent_minmax(g_, phase_table(), opt_.mixing, phase_ptrs(), partial_, dscal_ + kSlotMinMax, derr_, stream_);
   FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMinMax, dscal_ + kSlotMinMax, 2 * sizeof(double), hipMemcpyDeviceToHost, stream_));
   check_device_error("reference material");
   double lambda_min = hscal_[kSlotMinMax], lambda_max = -hscal_[kSlotMinMax + 1];
@@ -1953,7 +1774,7 @@ bool Solver::run_one_step(const double* E0, const double* S0) {
   // Displacement-based loop: eps_0 = 0 gives tau = 0, u_1 = 0 and eps_1 = E, so the loop starts from
   // u = 0 and every pass is [u_k -> norms of eps_k, f_{k+1}] + [f_{k+1} -> u_{k+1}] (see u_pass_front).
   bool uloop = u_loop_eligible(true);
-  const bool mixed_bc = !(frobenius(BC_MQ_) < kEps);   // (NaN until calcRefMaterial ran: Q != 0)
+  const bool mixed_bc = this->mixed_bc();   // (NaN until calcRefMaterial ran: Q != 0)
   if (uloop && fresh_step_) {
     FG_HIP_CHECK(hipMemsetAsync(fu_, 0, 3 * g_.n * sizeof(double), stream_));
     u_valid_ = true;
@@ -2083,40 +1904,18 @@ void Solver::polar_pass(const double* E6) {
   if (opt_.gamma_scheme == 0) {
     // the consistent staggered form (SolverOptions::method): u = -4 mu_0 G0 div_h Q, P = Q + sym grad_h u + P0; <Q> passes through
     time_begin(1);
-    launch_div(g_, ptrs6(tau_), ptrs3(fu_), XHalo{{nullptr, nullptr}, {nullptr, nullptr}}, stream_);
+    launch_div(g_, ptrs6(tau_), ptrs3(fu_), kNoXHalo, stream_);
     time_end(1);
     fft_g0_chain(fu_, alpha, nullptr, nullptr);   // (Q stays in tau_: no scratch for the x-contiguous layout)
     time_begin(9);
     launch_polar_back(g_, ptrs3(fu_), ptrs6(tau_), ptrs6(eps_), P0, partial_, dscal_ + kSlotSumSq, stream_);
     time_end(9);
   } else {
-    time_begin(2);
-    fft_->forward(tau_, 6, g_.n, 1 / (double)nglobal_);
-    time_end(2);
-    time_begin(5);
-    if (willot()) {
-      launch_gamma_willot(g_, ptrs6(tau_), willot_tables(), mu_0, opt_.lambda_0, alpha, 1.0, P0, sums, 1 / (double)nglobal_, stream_);
-    } else {
-      XiTables xt;
-      for (int a = 0; a < 3; ++a) xt.xi[a] = xi_[a];
-      const double c10 = alpha / (4 * mu_0);
-      const double c20 = -alpha / (mu_0 * (1 + mu_0 / (opt_.lambda_0 + mu_0)));
-      launch_gamma_collocated(g_, ptrs6(tau_), xt, c10, c20, 1.0, P0, stream_, sums, 1 / (double)nglobal_);
-    }
-    time_end(5);
-    time_begin(8);
-    fft_->inverse(tau_, 6, g_.n);
-    time_end(8);
-    time_begin(9);
-    launch_copy(tau_, eps_, 6 * g_.n, stream_);
-    launch_sum6(g_, ptrs6(eps_), true, partial_, dscal_ + kSlotSumSq, stream_);
-    time_end(9);
+    const GammaHat op = {willot(), mu_0, opt_.lambda_0, alpha, 1.0, P0, false, sums, 1 / (double)nglobal_};
+    fourier_pass6(op, eps_);
   }
-  if (timing_) times_.count++;
+  pass_done(E6, eps_, false);
   pol_state_ = true;
-  u_valid_ = false;
-  eps_stale_ = false;
-  for (int c = 0; c < 6; ++c) E_cur_[c] = E6[c];
 }
 
 void Solver::polar_settle() {
@@ -2488,23 +2287,19 @@ void Solver::run_stage(int stage, const double* E6) {
   }
   ensure_eps();
   if (stage != kStageIteration) u_valid_ = false;  // the stage buffers are being used as scratch
-  FieldPtrs<kMaxPhases> phi;
-  for (int q = 0; q < kMaxPhases; ++q) phi.p[q] = q < pt_.n ? phi_ + (long)q * g_.n : nullptr;
-  FieldPtrs<3> nrm;
-  for (int c = 0; c < 3; ++c) nrm.p[c] = normals_ ? normals_ + (long)c * g_.n : nullptr;
   const double zero6[6] = {0, 0, 0, 0, 0, 0};
   const double* E = E6 ? E6 : zero6;
   switch (stage) {
     case kStageStress:
       if (pt_.n < 1) throw std::runtime_error("No materials specified");
-      stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), eps_, phi, nrm);
+      stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), eps_);
       check_device_error("stress");
       break;
     case kStageStressConst:
       launch_stress_const(g_, opt_.mu_0, opt_.lambda_0, ptrs6(eps_), ptrs6(tau_), stream_);
       break;
     case kStageDiv:
-      launch_div(g_, ptrs6(tau_), ptrs3(fu_), XHalo{{nullptr, nullptr}, {nullptr, nullptr}}, stream_);
+      launch_div(g_, ptrs6(tau_), ptrs3(fu_), kNoXHalo, stream_);
       break;
     case kStageFftForward:
       fft_->forward(fu_, 3, g_.n, 1 / (double)nglobal_);
@@ -2528,7 +2323,7 @@ void Solver::run_stage(int stage, const double* E6) {
       Vec6 Ev, R;
       for (int c = 0; c < 6; ++c) Ev.v[c] = E[c], R.v[c] = 0.0;
       launch_eps_norm(g_, ptrs3(fu_), ptrs6(eps_), Ev, R, false, partial_, dscal_ + kSlotSumSq,
-                      XHalo{{nullptr, nullptr}, {nullptr, nullptr}}, stream_);
+                      kNoXHalo, stream_);
       FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotSumSq, dscal_ + kSlotSumSq, 6 * sizeof(double), hipMemcpyDeviceToHost, stream_));
       FG_HIP_CHECK(hipStreamSynchronize(stream_));
       for (int c = 0; c < 6; ++c) sumsq_[c] = hscal_[kSlotSumSq + c];
@@ -2612,23 +2407,16 @@ void Solver::get_field(const std::string& name, double* out) {
   }
   if (name == "sigma") {  // calcStress with C0 = 0  F:15496-15508
     if (pt_.n < 1) throw std::runtime_error("No materials specified");
-    FieldPtrs<kMaxPhases> phi;
-    for (int q = 0; q < kMaxPhases; ++q) phi.p[q] = q < pt_.n ? phi_ + (long)q * g_.n : nullptr;
-    FieldPtrs<3> nrm;
-    for (int c = 0; c < 3; ++c) nrm.p[c] = normals_ ? normals_ + (long)c * g_.n : nullptr;
-    stress_to_tau(stress_params(0.0, 0.0, 1.0), eps_, phi, nrm);
+    stress_to_tau(stress_params(0.0, 0.0, 1.0), eps_);
     check_device_error("sigma");
     download_unpadded(tau_, out, 6, g_.n);
     return;
   }
   if (name == "u" && opt_.mode == 2) {
     // velocity  F:15528-15535: calcStressDiff, div, G0(1/(4 mu0), inf, alpha = 1/(2 mu0)): c10 = c20 = -alpha/mu = -2
-    FieldPtrs<kMaxPhases> phi = phase_ptrs();
-    FieldPtrs<3> nrm;
-    for (int c = 0; c < 3; ++c) nrm.p[c] = normals_ ? normals_ + (long)c * g_.n : nullptr;
-    stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), eps_, phi, nrm);
+    stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), eps_);
     check_device_error("u");
-    launch_div(g_, ptrs6(tau_), ptrs3(fu_), XHalo{{nullptr, nullptr}, {nullptr, nullptr}}, stream_);
+    launch_div(g_, ptrs6(tau_), ptrs3(fu_), kNoXHalo, stream_);
     const double a = 1 / (2 * opt_.mu_0), mu_g = 1 / (4 * opt_.mu_0);
     const double c12[2] = {-a / mu_g, -a / mu_g};
     const bool timing = timing_;
@@ -2641,7 +2429,7 @@ void Solver::get_field(const std::string& name, double* out) {
   if (name == "u") {  // u = G0 div (C0 : eps), alpha = 1  F:15509-15521
     double* const ub = cg_u_active_ ? fu_alt_ : fu_;
     launch_stress_const(g_, opt_.mu_0, opt_.lambda_0, ptrs6(eps_), ptrs6(tau_), stream_);
-    launch_div(g_, ptrs6(tau_), ptrs3(ub), XHalo{{nullptr, nullptr}, {nullptr, nullptr}}, stream_);
+    launch_div(g_, ptrs6(tau_), ptrs3(ub), kNoXHalo, stream_);
     fft_->forward(ub, 3, g_.n, 1 / (double)nglobal_);
     const double alpha = 1.0;
     const double c10 = -alpha / (opt_.mu_0);

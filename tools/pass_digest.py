@@ -1,0 +1,186 @@
+"""SHA-256 of the residual history and of the final epsilon field for a fixed list of short runs (tol = abs_tol = -1,
+maxiter = 5: every run makes the same five passes whatever it computes).  Two builds that print the same lines enqueue the same
+arithmetic on every path the list reaches: the check for a change that must leave every iterate bit-identical.
+
+    python tools/pass_digest.py > profiles/pass_digest_<build>.txt
+
+One line per run: grid, name, the digest of the residuals, the digest of the field and the iteration count -- or the solver's
+error text where a combination is refused (a refusal is part of the behaviour that is compared)."""
+import hashlib
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from fibergen_amd import LSSolver  # noqa: E402
+
+FIXED = dict(tol=-1.0, abs_tol=-1.0, maxiter=5)
+E6 = np.array([0.5, -0.2, 0.1, 0.05, -0.1, 0.3])
+E3 = np.array([1.0, -0.5, 0.25])
+# sigma_11 prescribed, the other five strains prescribed
+P_MIXED = np.diag([0.0, 1.0, 1.0, 0.5, 0.5, 0.5])
+E_MIXED = np.array([0.0, -0.2, 0.1, 0.05, -0.1, 0.3])
+S_MIXED = np.array([0.1, 0, 0, 0, 0, 0.0])
+P3_MIXED = np.diag([0.0, 1.0, 1.0, 0.5, 0.5, 0.5])   # heat: flux component 1 prescribed
+E3_MIXED = np.array([0.0, -0.5, 0.25])
+S3_MIXED = np.array([0.2, 0.0, 0.0])
+
+
+def geometry(grid):
+    """a blurred sphere (fractions strictly between 0 and 1 on its surface, so laminate mixing has work) and its normals"""
+    ax = [(np.arange(n) + 0.5) / n - 0.5 for n in grid]
+    v = np.stack(np.broadcast_arrays(ax[0][:, None, None], ax[1][None, :, None], ax[2][None, None, :])).astype(np.float64)
+    r = np.sqrt((v * v).sum(axis=0))
+    phi = np.clip(0.5 + (0.3 - r) * 6.0, 0.0, 1.0)
+    rr = np.where(r == 0, 1.0, r)
+    return phi, v / rr
+
+
+def general_stiffness():
+    rng = np.random.default_rng(11)
+    a = rng.standard_normal((6, 6))
+    return a @ a.T / 6 + 2.0 * np.eye(6)
+
+
+def solver(grid, mode="elasticity", mats=((0.4, 0.6), (4.0, 2.5)), normals=False, general=False, aniso=False, fine=False, **opts):
+    phi, nrm = geometry(grid)
+    s = LSSolver(*grid)
+    s.set_options(mode=mode)
+    if "gamma_scheme" in opts:
+        s.set_options(gamma_scheme=opts.pop("gamma_scheme"))
+    s.set_num_phases(2)
+    for p, f in enumerate((1.0 - phi, phi)):
+        s.set_phase(p, mats[p][0], mats[p][1], f)
+        if fine:
+            s.set_phase_fine(p, np.repeat(np.repeat(np.repeat(f, 2, 0), 2, 1), 2, 2))
+    if general:
+        s.set_phase_stiffness(1, general_stiffness())
+    if aniso:
+        s.set_phase_conductivity(1, [3.0, 1.5, 0.7, 0.2, -0.1, 0.3])
+    if normals:
+        s.set_normals(nrm)
+    s.set_options(**FIXED)
+    s.set_options(**opts)
+    return s
+
+
+def digest(a):
+    return hashlib.sha256(np.ascontiguousarray(a, dtype=np.float64).tobytes()).hexdigest()
+
+
+def report(name, grid, E=E6, mixed=False, **kw):
+    tag = "%s %s" % ("x".join(map(str, grid)), name)
+    try:
+        s = solver(grid, **kw)
+        if mixed:
+            s.set_bc_projector(P_MIXED)
+            E = E3_MIXED if len(E) == 3 else E_MIXED
+        s.run(E, (S3_MIXED if len(E) == 3 else S_MIXED) if mixed else None)
+        print("%s: %s %s %d" % (tag, digest(s.residuals), digest(s.get_field("epsilon")), s.iterations))
+        s.close()
+    except Exception as exc:   # noqa: BLE001
+        print("%s: ERROR %s" % (tag, str(exc).splitlines()[0] if str(exc) else type(exc).__name__))
+    sys.stdout.flush()
+
+
+def opts(o):
+    return " ".join("%s=%s" % kv for kv in o.items()) or "defaults"
+
+
+# the schedules of the transform chain; the plane kernel needs ny >= 16, the x layout rows of 64 points
+CHAIN = [dict(fuse_x=0, plane_fft=0), dict(plane_fft=0), dict(), dict(fuse_x=0), dict(plane_fft=0, pair_chunk=4),
+         dict(fuse_x=0, plane_fft=0, pair_chunk=4), dict(plane_fft=0, x_layout=1), dict(plane_fft=0, x_layout=1, pair_chunk=4)]
+G16, G64, GODD, G32 = (16, 8, 16), (16, 16, 64), (12, 10, 7), (32, 32, 32)
+VISC = dict(mode="viscosity", mats=((1.0, 0.0), (0.05, 0.0)))
+HEAT = dict(mode="heat", mats=((1.0, 0.0), (7.0, 0.0)), E=E3)
+LAM = dict(normals=True, mixing_rule="laminate")
+
+
+def features(grid, full):
+    """every operator and loop on one grid; full: with each of its variants, else its default form"""
+    for ul in (0, 1, 2) if full else (2,):
+        report("laminate u_loop=%d" % ul, grid, u_loop=ul, **LAM)
+    report("laminate mixed bc", grid, mixed=True, **LAM)
+    # mixed boundary conditions and bc_relax on the three schemes, full_staggered
+    for scheme, ul in (("staggered", 0), ("staggered", 2), ("collocated", 2), ("willot", 2)):
+        o = dict(gamma_scheme=scheme, u_loop=ul)
+        report("%s u_loop=%d mixed bc" % (scheme, ul), grid, mixed=True, **o)
+        if ul == 2:
+            report("%s mixed bc bc_relax=0.5" % scheme, grid, mixed=True, bc_relax=0.5, **o)
+        if full and scheme != "willot":
+            report("%s u_loop=%d bc_relax=0.5" % (scheme, ul), grid, bc_relax=0.5, **o)
+        if scheme != "staggered":
+            report(scheme, grid, gamma_scheme=scheme)
+    for ul in (0, 2) if full else (2,):
+        report("full_staggered u_loop=%d" % ul, grid, gamma_scheme="full_staggered", fine=True, u_loop=ul)
+    report("full_staggered mixed bc", grid, mixed=True, gamma_scheme="full_staggered", fine=True)
+    # viscosity: fused, unfused, mixed boundary conditions, willot, full_staggered
+    for sd in (0, 1):
+        report("viscosity fuse_stress_div=%d" % sd, grid, fuse_stress_div=sd, **VISC)
+        report("viscosity fuse_stress_div=%d mixed bc" % sd, grid, mixed=True, fuse_stress_div=sd, **VISC)
+        if full:
+            report("viscosity fuse_stress_div=%d u_loop=0" % sd, grid, fuse_stress_div=sd, u_loop=0, **VISC)
+            report("viscosity full_staggered fuse_stress_div=%d" % sd, grid, gamma_scheme="full_staggered", fine=True, fuse_stress_div=sd,
+                   **VISC)
+    report("viscosity willot", grid, gamma_scheme="willot", **VISC)
+    report("viscosity willot mixed bc", grid, mixed=True, gamma_scheme="willot", **VISC)
+    # heat, with and without an aniso phase
+    for an in (0, 1):
+        for ul in (1, 2) if full else (2,):
+            for c in CHAIN[:6] if full and not an else CHAIN[:2]:
+                report("heat aniso=%d u_loop=%d %s" % (an, ul, opts(c)), grid, aniso=an, u_loop=ul, **c, **HEAT)
+        report("heat aniso=%d mixed bc" % an, grid, mixed=True, aniso=an, **HEAT)
+        report("heat aniso=%d cg" % an, grid, aniso=an, method="cg", **HEAT)
+    # a general phase
+    for scheme, ul in (("staggered", 0), ("staggered", 2), ("collocated", 2), ("willot", 2)):
+        report("general %s u_loop=%d" % (scheme, ul), grid, general=True, gamma_scheme=scheme, u_loop=ul)
+    if full:
+        report("general aniso_tile=0", grid, general=True, aniso_tile=0)
+        report("general mixed bc", grid, mixed=True, general=True)
+    # conjugate gradients: strain space, displacement space (four kernels / fused sweeps); the scalar form is above
+    report("cg u_loop=0", grid, method="cg", u_loop=0)
+    for cf in (0, 1):
+        report("cg cg_fused=%d" % cf, grid, method="cg", cg_fused=cf)
+        if full:
+            report("cg laminate cg_fused=%d" % cf, grid, method="cg", cg_fused=cf, **LAM)
+    if full:
+        report("cg x_layout=1 plane_fft=0", grid, method="cg", x_layout=1, plane_fft=0)
+        report("cg mixed bc", grid, mixed=True, method="cg")
+        report("cg collocated", grid, method="cg", gamma_scheme="collocated")
+        report("cg general", grid, method="cg", general=True)
+    # method polarization on the three schemes
+    for scheme in ("staggered", "collocated", "willot"):
+        for gen in (0, 1) if full else (0,):
+            report("polarization %s general=%d" % (scheme, gen), grid, method="polarization", gamma_scheme=scheme, general=gen)
+
+
+def main():
+    # elasticity, staggered: the sweeps (u_loop, fuse_stress_div) against every schedule of the chain
+    for ul in (0, 1, 2):
+        for c in CHAIN:
+            report("stag u_loop=%d %s" % (ul, opts(c)), G64, u_loop=ul, **c)
+        for grid in (G16, G64, GODD):
+            report("stag u_loop=%d fuse_stress_div=0" % ul, grid, u_loop=ul, fuse_stress_div=0)
+        for grid in (G16, GODD):
+            for fx in (0, 1):
+                report("stag u_loop=%d fuse_x=%d plane_fft=0" % (ul, fx), grid, u_loop=ul, fuse_x=fx, plane_fft=0)
+    for c in CHAIN[4:]:   # options the small grid does not take: the chain falls back
+        report("stag %s" % opts(c), G16, **c)
+    for grid in ((1, 8, 16), (1, 1, 16)):   # no x pass / neither x nor y pass
+        for fx in (0, 1):
+            report("stag fuse_x=%d" % fx, grid, fuse_x=fx)
+            report("heat fuse_x=%d" % fx, grid, fuse_x=fx, **HEAT)
+    features(G64, True)
+    features(G16, False)
+    # the untiled sweeps and the generic transforms once more per operator; 32^3: two waves per row, more than one block everywhere
+    for grid in (GODD, G32):
+        for name, o in (("laminate", LAM), ("collocated mixed bc bc_relax=0.5", dict(gamma_scheme="collocated", mixed=True, bc_relax=0.5)),
+                        ("willot", dict(gamma_scheme="willot")), ("viscosity mixed bc", dict(mixed=True, **VISC)), ("heat", HEAT),
+                        ("cg", dict(method="cg")), ("polarization collocated", dict(method="polarization", gamma_scheme="collocated"))):
+            report(name, grid, **o)
+
+
+if __name__ == "__main__":
+    main()
