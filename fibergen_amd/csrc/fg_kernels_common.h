@@ -113,19 +113,23 @@ __device__ __forceinline__ double read_lane(double v, int lane) {
   return __hiloint2double(hi, lo);
 }
 
-// Deterministic block reduction of NV values per thread: fixed rotate tree inside each row of 16
-// lanes, the four row totals and then the four waves combined in a fixed order; thread 0 holds the result.
+// The per-wave step of the deterministic reductions: fixed rotate tree (8, 4, 2, 1) inside each row of 16 lanes, then the four
+// row totals as (lane 0 + lane 16) + (lane 32 + lane 48); every lane holds the result.
+template <class Op>
+__device__ __forceinline__ double wave_reduce(double a, Op op) {
+  a = op(a, dpp_move<0x128>(a));
+  a = op(a, dpp_move<0x124>(a));
+  a = op(a, dpp_move<0x122>(a));
+  a = op(a, dpp_move<0x121>(a));
+  return op(op(read_lane(a, 0), read_lane(a, 16)), op(read_lane(a, 32), read_lane(a, 48)));
+}
+
+// Deterministic block reduction of NV values per thread: wave_reduce, then the four waves combined in a fixed order;
+// thread 0 holds the result.
 template <int NV, class Op>
 __device__ __forceinline__ void block_reduce(double* v, double* smem, Op op) {
 #pragma unroll
-  for (int q = 0; q < NV; ++q) {
-    double a = v[q];
-    a = op(a, dpp_move<0x128>(a));
-    a = op(a, dpp_move<0x124>(a));
-    a = op(a, dpp_move<0x122>(a));
-    a = op(a, dpp_move<0x121>(a));
-    v[q] = op(op(read_lane(a, 0), read_lane(a, 16)), op(read_lane(a, 32), read_lane(a, 48)));
-  }
+  for (int q = 0; q < NV; ++q) v[q] = wave_reduce(v[q], op);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   constexpr int nw = kBlock / 64;
   if (lane == 0) {
@@ -147,6 +151,45 @@ __device__ __forceinline__ void block_reduce(double* v, double* smem, Op op) {
 struct OpSum { __device__ double operator()(double a, double b) const { return a + b; } };
 struct OpMin { __device__ double operator()(double a, double b) const { return a < b ? a : b; } };
 struct OpMax { __device__ double operator()(double a, double b) const { return a > b ? a : b; } };
+
+// The fixed-order sums of a tiled marching sweep (fg_kernels_fast.hip): wave_reduce, then the WAVES waves of the workgroup
+// in ascending order from 0.0 by thread c for column c (red: WAVES * NS doubles of LDS).  The workgroup writes its row of
+// ncols >= NS columns of the partials -- zeros past NS.  wv, l: the wave and lane of the thread, as the kernel holds them.
+template <int NS, int WAVES>
+__device__ __forceinline__ void tile_reduce(double (&acc)[NS], double* red, double* partial, int ncols, int wv, int l) {
+#pragma unroll
+  for (int c = 0; c < NS; ++c) acc[c] = wave_reduce(acc[c], OpSum());
+  if (l == 0) {
+#pragma unroll
+    for (int c = 0; c < NS; ++c) red[wv * NS + c] = acc[c];
+  }
+  __syncthreads();
+  if (threadIdx.x < ncols) {
+    double a = 0.0;
+    if (threadIdx.x < NS)
+      for (int w = 0; w < WAVES; ++w) a += red[w * NS + threadIdx.x];
+    partial[(long)blockIdx.x * ncols + threadIdx.x] = a;
+  }
+}
+
+// Store of a pair by a tiled sweep.  The output is read back only after the whole sweep: with fields larger than the
+// Infinity Cache it is stored past the cache (nt), see cstore_stream
+__device__ __forceinline__ void tile_store(double* base, long off, double2 v, int nt) {
+  if (nt) {
+    typedef double fg_v2d __attribute__((ext_vector_type(2)));
+    fg_v2d t;
+    t.x = v.x;
+    t.y = v.y;
+    __builtin_nontemporal_store(t, reinterpret_cast<fg_v2d*>(base + off));
+  } else {
+    st2(base, off, v);
+  }
+}
+
+// z neighbours of a tiled sweep: the adjacent lanes' values.  Lane 0 of lane_prev and lane 63 of lane_next get nothing of
+// use: halo lanes, or (whole rows, ZS >= 1) fixed up by the caller from the adjacent wave's entry in LDS.
+__device__ __forceinline__ double lane_prev(double v) { return dpp_move<0x138>(v); }   // lane i <- i-1
+__device__ __forceinline__ double lane_next(double v) { return dpp_move<0x130>(v); }   // lane i <- i+1
 
 struct Row4 {
   double v[4];

@@ -7,10 +7,12 @@
 #include "fg_kernels.h"
 
 #include <cstdlib>
+#include <tuple>
 #include <type_traits>
 
 #include "fg_hip_util.h"
 #include "fg_kernels_common.h"
+#include "fg_tile_frame.h"
 
 namespace fg {
 
@@ -242,11 +244,9 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, dou
                                                                       std::conditional_t<ANISO, AnisoLin, PhaseLin> lin,
                                                                       CgDirection cg) {
   static_assert(!ANISO || (PHI2 && NMOD == 2), "the anisotropic form reads phi_1 like PHI2");
-  constexpr bool FULLROW = ZS > 0;
-  constexpr int NZS = ZS ? ZS : 1;        // waves per row
-  constexpr int TYU = TYR - 2;            // rows with output
-  constexpr int TZU = FULLROW ? 64 * NZS : 62;  // pairs with output per tile row
-  constexpr int RW = NZS * 64;            // LDS entries per row
+  using S = TileShape<TYR, ZS>;
+  constexpr bool FULLROW = S::FULLROW;
+  constexpr int NZS = S::NZS, RW = S::RW;
   extern __shared__ __align__(16) double2 tile_lds[];
   // ANISO: the image of u has one more row on either side (the rows before halo row 0 and after the last halo row), UO = 1
   constexpr int UO = ANISO ? 1 : 0, UR = TYR + 2 * UO;
@@ -257,55 +257,9 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, dou
   __shared__ double red[TYR * NZS * NS];
   __shared__ double edge[3][TYR][NZS];    // tau2.y of lane 63, tau3.x and tau4.x of lane 0 of every wave (ZS >= 1)
 
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int r = wv / NZS, zs = wv % NZS;  // tile row, z segment of the row
-  const int li = zs * 64 + l;             // entry of this thread in an LDS row
-  const int zprev = (zs + NZS - 1) % NZS, znext = (zs + 1) % NZS;
-  const int nzh = g.nz / 2;
-  // workgroups of one XCD (blockIdx % 8) take a contiguous run of tiles: z- and y-adjacent tiles, which share halo
-  // rows and 128-byte segments, then meet in that XCD's L2 (FETCH_SIZE 2.1x -> see profiles/ for the effect)
-  int b = blockIdx.x;
-  {
-    const int nb = gridDim.x;
-    if (nb % 8 == 0) b = (b % 8) * (nb / 8) + b / 8;
-  }
-  const int tz = b % ntz;
-  b /= ntz;
-  const int ty = b % nty;
-  const int tx = b / nty;
-  const bool surplus = tx * LX >= g.nx;   // padding workgroup (grid rounded up to a multiple of 8)
-  const int j0 = min(ty * TYU, g.ny - TYU), kp0 = min(tz * TZU, nzh - TZU), x0 = surplus ? 0 : tx * LX;
-  const int jr = j0 - 1 + r;                              // may be -1 or ny
-  const int j = jr < 0 ? jr + g.ny : (jr >= g.ny ? jr - g.ny : jr);
-  const int kr = FULLROW ? li : kp0 - 1 + l;
-  const int kp = kr < 0 ? kr + nzh : (kr >= nzh ? kr - nzh : kr);
-  const bool own = r >= 1 && r <= TYU && jr >= ty * TYU && (FULLROW || (l >= 1 && l <= TZU && kr >= tz * TZU));
-  const long rowoff = (long)j * g.nzp + 2 * kp;
-  const int rm = r > 0 ? r - 1 : 0, rp = r + 1 < TYR ? r + 1 : TYR - 1;
-  const double hx = g.hx, hy = g.hy, hz = g.hz;
-  const int nsteps = surplus ? -2 : (x0 + LX <= g.nx ? LX : g.nx - x0);   // surplus: no steps at all
-
-  // element offset of x plane q (periodic, or the halo planes of an x-slab; q in [-1, 2 nx)).  The anisotropic form also asks for
-  // q = -2: it runs on whole grids only (general phases are refused on slabs), where xw_lo = nx >= 4 wraps any q in [-nx, 0)
-  auto plane = [&](int q) {
-    const int x = q < 0 ? q + g.xw_lo : (q >= g.nx ? q - g.xw_hi : q);
-    return (long)x * g.nyzp + rowoff;
-  };
-  // f is read back by the z pass only after the whole sweep: with fields larger than the Infinity Cache it is stored
-  // past the cache (nt), see cstore_stream
-  auto store_f = [&](double* base, long off, double2 v) {
-    if (nt) {
-      typedef double fg_v2d __attribute__((ext_vector_type(2)));
-      fg_v2d t;
-      t.x = v.x;
-      t.y = v.y;
-      __builtin_nontemporal_store(t, reinterpret_cast<fg_v2d*>(base + off));
-    } else {
-      st2(base, off, v);
-    }
-  };
-  auto prev_y = [&](double v) { return dpp_move<0x138>(v); };  // lane i <- i-1 (lane 0: fixed up below when ZS >= 1)
-  auto next_x = [&](double v) { return dpp_move<0x130>(v); };  // lane i <- i+1 (lane 63: likewise)
+  // x planes through Grid::xw_lo / xw_hi (periodic, or the halo planes of an x-slab; q in [-1, 2 nx)).  The anisotropic form also
+  // asks for q = -2: it runs on whole grids only (general phases are refused on slabs), where xw_lo = nx >= 4 wraps any q in [-nx, 0)
+  FG_TILE_FRAME(TYR, ZS, XWrap::slab, -2, g, nty, ntz, LX, blockIdx.x, gridDim.x, threadIdx.x);
 
   const double cgb = CGP ? (cg.sc[cg.i_num] / cg.nvox + cg.small) / (cg.sc[cg.i_den] / cg.nvox + cg.small) : 0.0;
   // the displacement of component c at offset o (CGP: the new direction, kept where `keep` says the plane is this tile's)
@@ -394,7 +348,7 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, dou
     FG_K1_MARK(3);
     const int ub = ANISO ? r : rm, uf = ANISO ? r + 2 : rp;   // ANISO: rows r - 1, r + 1 of the extended image
     const double2 U0yb = Ub[0][ub][li], U1yf = Ub[1][uf][li], U2yb = Ub[2][ub][li];
-    double U0zb = prev_y(uc[0].y), U1zb = prev_y(uc[1].y), U2zf = next_x(uc[2].x);
+    double U0zb = lane_prev(uc[0].y), U1zb = lane_prev(uc[1].y), U2zf = lane_next(uc[2].x);
     if (FULLROW) {   // wave edges: the neighbour pair lives in the adjacent wave of the same row
       if (l == 0) {
         U0zb = Ub[0][r + UO][zprev * 64 + 63].y;
@@ -483,7 +437,7 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, dou
     __syncthreads();
     FG_K1_MARK(6);
     const double2 t1yb = Tb[0][rm][li], t5yf = Tb[1][rp][li], t3yf = Tb[2][rp][li];
-    double t2zb = prev_y(t2.y), t3zf = next_x(t3.x), t4zf = next_x(t4.x);
+    double t2zb = lane_prev(t2.y), t3zf = lane_next(t3.x), t4zf = lane_next(t4.x);
     if (FULLROW) {
       if (l == 0) t2zb = edge[0][r][zprev];
       if (l == 63) {
@@ -497,12 +451,12 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, dou
         double2 f0;
         f0.x = (t0.x - t0m.x) * hx + (t5yf.x - t5.x) * hy + (t4.y - t4.x) * hz;
         f0.y = (t0.y - t0m.y) * hx + (t5yf.y - t5.y) * hy + (t4zf - t4.y) * hz;
-        store_f(fo.p[0], oq, f0);
+        tile_store(fo.p[0], oq, f0, nt);
       }
       if (st >= 1) {
         const long op = plane(q - 1);
-        store_f(fo.p[1], op, make_double2((t5.x - t5m.x) * hx + part1.x, (t5.y - t5m.y) * hx + part1.y));
-        store_f(fo.p[2], op, make_double2((t4.x - t4m.x) * hx + part2.x, (t4.y - t4m.y) * hx + part2.y));
+        tile_store(fo.p[1], op, make_double2((t5.x - t5m.x) * hx + part1.x, (t5.y - t5m.y) * hx + part1.y), nt);
+        tile_store(fo.p[2], op, make_double2((t4.x - t4m.x) * hx + part2.x, (t4.y - t4m.y) * hx + part2.y), nt);
       }
     }
     part1.x = (t1.x - t1yb.x) * hy + (t3.y - t3.x) * hz;
@@ -522,25 +476,7 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, dou
     FG_K1_MARK(8);   // end of the march
   }
   // ---- sums of squares: fixed-order reduction over the workgroup
-#pragma unroll
-  for (int c = 0; c < NS; ++c) {
-    double a = acc[c];
-    a += dpp_move<0x128>(a);
-    a += dpp_move<0x124>(a);
-    a += dpp_move<0x122>(a);
-    a += dpp_move<0x121>(a);
-    acc[c] = (read_lane(a, 0) + read_lane(a, 16)) + (read_lane(a, 32) + read_lane(a, 48));
-  }
-  if (l == 0) {
-#pragma unroll
-    for (int c = 0; c < NS; ++c) red[wv * NS + c] = acc[c];
-  }
-  __syncthreads();
-  if (threadIdx.x < NS) {
-    double a = 0.0;
-    for (int w = 0; w < TYR * NZS; ++w) a += red[w * NS + threadIdx.x];
-    partial[(long)blockIdx.x * NS + threadIdx.x] = a;
-  }
+  tile_reduce<NS, TYR * NZS>(acc, red, partial, NS, wv, l);
 }
 
 // Tiled marching form of the vector sweeps of the conjugate gradients in displacement space (k_cgu_dot / k_cgu_axpy,
@@ -558,60 +494,17 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_cgu_tile(Grid g, F
                                                                         const double* sc, int i_num, int i_den, double nvox,
                                                                         double small, double* partial, int nty, int ntz, int LX,
                                                                         int nt) {
-  constexpr bool FULLROW = ZS > 0;
-  constexpr int NZS = ZS ? ZS : 1;
-  constexpr int TYU = TYR - 2;
-  constexpr int TZU = FULLROW ? 64 * NZS : 62;
-  constexpr int RW = NZS * 64;
+  using S = TileShape<TYR, ZS>;
+  constexpr bool FULLROW = S::FULLROW;
+  constexpr int NZS = S::NZS, RW = S::RW;
   constexpr int NS = 7;
   extern __shared__ __align__(16) double2 tile_lds[];
   double2(*Xb)[TYR][RW] = reinterpret_cast<double2(*)[TYR][RW]>(tile_lds);   // [6][TYR][RW]: A0 A1 A2 B0 B1 B2 of the plane
   __shared__ double red[TYR * NZS * NS];
 
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int r = wv / NZS, zs = wv % NZS;
-  const int li = zs * 64 + l;
-  const int zprev = (zs + NZS - 1) % NZS, znext = (zs + 1) % NZS;
-  const int nzh = g.nz / 2;
-  int bi = blockIdx.x;
-  {
-    const int nb = gridDim.x;
-    if (nb % 8 == 0) bi = (bi % 8) * (nb / 8) + bi / 8;
-  }
-  const int tz = bi % ntz;
-  bi /= ntz;
-  const int ty = bi % nty;
-  const int tx = bi / nty;
-  const bool surplus = tx * LX >= g.nx;
-  const int j0 = min(ty * TYU, g.ny - TYU), kp0 = min(tz * TZU, nzh - TZU), x0 = surplus ? 0 : tx * LX;
-  const int jr = j0 - 1 + r;
-  const int j = jr < 0 ? jr + g.ny : (jr >= g.ny ? jr - g.ny : jr);
-  const int kr = FULLROW ? li : kp0 - 1 + l;
-  const int kp = kr < 0 ? kr + nzh : (kr >= nzh ? kr - nzh : kr);
-  const bool own = r >= 1 && r <= TYU && jr >= ty * TYU && (FULLROW || (l >= 1 && l <= TZU && kr >= tz * TZU));
-  const long rowoff = (long)j * g.nzp + 2 * kp;
-  const int rm = r > 0 ? r - 1 : 0, rp = r + 1 < TYR ? r + 1 : TYR - 1;
-  const double hx = g.hx, hy = g.hy, hz = g.hz;
-  const int nsteps = surplus ? -2 : (x0 + LX <= g.nx ? LX : g.nx - x0);
+  FG_TILE_FRAME(TYR, ZS, XWrap::slab, -2, g, nty, ntz, LX, blockIdx.x, gridDim.x, threadIdx.x);
   const double al = MODE == 1 ? (sc[i_num] / nvox + small) / (sc[i_den] / nvox + small) : 0.0;
 
-  auto plane = [&](int q) {
-    const int x = q < 0 ? q + g.xw_lo : (q >= g.nx ? q - g.xw_hi : q);
-    return (long)x * g.nyzp + rowoff;
-  };
-  auto store = [&](double* base, long off, double2 v) {
-    if (nt) {
-      typedef double fg_v2d __attribute__((ext_vector_type(2)));
-      fg_v2d t;
-      t.x = v.x;
-      t.y = v.y;
-      __builtin_nontemporal_store(t, reinterpret_cast<fg_v2d*>(base + off));
-    } else {
-      st2(base, off, v);
-    }
-  };
-  auto prev_y = [&](double v) { return dpp_move<0x138>(v); };
-  auto next_x = [&](double v) { return dpp_move<0x130>(v); };
   // the two fields of plane q (as stored, or updated), and their store where this thread owns the voxels of an owned plane
   auto fetch = [&](int q, double2 (&A)[3], double2 (&B)[3], bool keep) {
     const long o = plane(q);
@@ -626,8 +519,8 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_cgu_tile(Grid g, F
         B[c].x = B[c].x - al * (yv.x - wv2.x);
         B[c].y = B[c].y - al * (yv.y - wv2.y);
         if (keep && own) {
-          store(ao.p[c], o, A[c]);
-          store(bo.p[c], o, B[c]);
+          tile_store(ao.p[c], o, A[c], nt);
+          tile_store(bo.p[c], o, B[c], nt);
         }
       }
     }
@@ -652,8 +545,8 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_cgu_tile(Grid g, F
       __syncthreads();
       const double2 A0yb = Xb[0][rm][li], A1yf = Xb[1][rp][li], A2yb = Xb[2][rm][li];
       const double2 B0yb = Xb[3][rm][li], B1yf = Xb[4][rp][li], B2yb = Xb[5][rm][li];
-      double A0zb = prev_y(Ac[0].y), A1zb = prev_y(Ac[1].y), A2zf = next_x(Ac[2].x);
-      double B0zb = prev_y(Bc[0].y), B1zb = prev_y(Bc[1].y), B2zf = next_x(Bc[2].x);
+      double A0zb = lane_prev(Ac[0].y), A1zb = lane_prev(Ac[1].y), A2zf = lane_next(Ac[2].x);
+      double B0zb = lane_prev(Bc[0].y), B1zb = lane_prev(Bc[1].y), B2zf = lane_next(Bc[2].x);
       if (FULLROW) {
         if (l == 0) {
           A0zb = Xb[0][r][zprev * 64 + 63].y;
@@ -714,25 +607,7 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_cgu_tile(Grid g, F
       if (st + 1 < nsteps) fetch(q + 2, An, Bn, st + 2 < nsteps);   // plane q + 2: the forward x neighbour of the next step
     }
   }
-#pragma unroll
-  for (int c = 0; c < NS; ++c) {
-    double v = acc[c];
-    v += dpp_move<0x128>(v);
-    v += dpp_move<0x124>(v);
-    v += dpp_move<0x122>(v);
-    v += dpp_move<0x121>(v);
-    acc[c] = (read_lane(v, 0) + read_lane(v, 16)) + (read_lane(v, 32) + read_lane(v, 48));
-  }
-  if (l == 0) {
-#pragma unroll
-    for (int c = 0; c < NS; ++c) red[wv * NS + c] = acc[c];
-  }
-  __syncthreads();
-  if (threadIdx.x < NS) {
-    double v = 0.0;
-    for (int q = 0; q < TYR * NZS; ++q) v += red[q * NS + threadIdx.x];
-    partial[(long)blockIdx.x * NS + threadIdx.x] = v;
-  }
+  tile_reduce<NS, TYR * NZS>(acc, red, partial, NS, wv, l);
 }
 
 // The second half of k_u_tile on its own, for passes whose state is the strain field (viscosity mode; mixed boundary
@@ -744,59 +619,16 @@ template <int TYR, int ZS, int NMOD = 2>
 __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_eps_tile(Grid g, double beta, double gamma, FieldPtrs<6> eps,
                                                                         FieldPtrs<NMOD> mod, FieldPtrs<3> fo, double* partial,
                                                                         int nty, int ntz, int LX, int nt) {
-  constexpr bool FULLROW = ZS > 0;
-  constexpr int NZS = ZS ? ZS : 1;
-  constexpr int TYU = TYR - 2;
-  constexpr int TZU = FULLROW ? 64 * NZS : 62;
-  constexpr int RW = NZS * 64;
+  using S = TileShape<TYR, ZS>;
+  constexpr bool FULLROW = S::FULLROW;
+  constexpr int NZS = S::NZS, RW = S::RW;
   extern __shared__ __align__(16) double2 tile_lds[];
   double2(*Tb)[3][TYR][RW] = reinterpret_cast<double2(*)[3][TYR][RW]>(tile_lds);   // [2][3][TYR][RW]
   __shared__ double red[TYR * NZS * 6];
   __shared__ double edge[2][3][TYR][NZS];
 
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int r = wv / NZS, zs = wv % NZS;
-  const int li = zs * 64 + l;
-  const int zprev = (zs + NZS - 1) % NZS, znext = (zs + 1) % NZS;
-  const int nzh = g.nz / 2;
-  int b = blockIdx.x;
-  {
-    const int nb = gridDim.x;
-    if (nb % 8 == 0) b = (b % 8) * (nb / 8) + b / 8;
-  }
-  const int tz = b % ntz;
-  b /= ntz;
-  const int ty = b % nty;
-  const int tx = b / nty;
-  const bool surplus = tx * LX >= g.nx;
-  const int j0 = min(ty * TYU, g.ny - TYU), kp0 = min(tz * TZU, nzh - TZU), x0 = surplus ? 0 : tx * LX;
-  const int jr = j0 - 1 + r;
-  const int j = jr < 0 ? jr + g.ny : (jr >= g.ny ? jr - g.ny : jr);
-  const int kr = FULLROW ? li : kp0 - 1 + l;
-  const int kp = kr < 0 ? kr + nzh : (kr >= nzh ? kr - nzh : kr);
-  const bool own = r >= 1 && r <= TYU && jr >= ty * TYU && (FULLROW || (l >= 1 && l <= TZU && kr >= tz * TZU));
-  const long rowoff = (long)j * g.nzp + 2 * kp;
-  const int rm = r > 0 ? r - 1 : 0, rp = r + 1 < TYR ? r + 1 : TYR - 1;
-  const double hx = g.hx, hy = g.hy, hz = g.hz;
-  const int nsteps = surplus ? -2 : (x0 + LX <= g.nx ? LX : g.nx - x0);
-
-  auto plane = [&](int q) {
-    const int x = q < 0 ? q + g.nx : (q >= g.nx ? q - g.nx : q);
-    return (long)x * g.nyzp + rowoff;
-  };
-  auto store_f = [&](double* base, long off, double2 v) {
-    if (nt) {
-      typedef double fg_v2d __attribute__((ext_vector_type(2)));
-      fg_v2d t;
-      t.x = v.x;
-      t.y = v.y;
-      __builtin_nontemporal_store(t, reinterpret_cast<fg_v2d*>(base + off));
-    } else {
-      st2(base, off, v);
-    }
-  };
-  auto prev_y = [&](double v) { return dpp_move<0x138>(v); };
-  auto next_x = [&](double v) { return dpp_move<0x130>(v); };
+  // the strain is the state of whole grids only (no x-slab form): the planes wrap with nx
+  FG_TILE_FRAME(TYR, ZS, XWrap::periodic, -2, g, nty, ntz, LX, blockIdx.x, gridDim.x, threadIdx.x);
 
   double2 en[6], An, Bn;   // inputs of the coming step
   [[maybe_unused]] double2 Sn[3];
@@ -871,7 +703,7 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_eps_tile(Grid g, d
     }
     __syncthreads();
     const double2 t1yb = Tb[img][0][rm][li], t5yf = Tb[img][1][rp][li], t3yf = Tb[img][2][rp][li];
-    double t2zb = prev_y(t2.y), t3zf = next_x(t3.x), t4zf = next_x(t4.x);
+    double t2zb = lane_prev(t2.y), t3zf = lane_next(t3.x), t4zf = lane_next(t4.x);
     if (FULLROW) {
       if (l == 0) t2zb = edge[img][0][r][zprev];
       if (l == 63) {
@@ -885,12 +717,12 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_eps_tile(Grid g, d
         double2 f0;
         f0.x = (t0.x - t0m.x) * hx + (t5yf.x - t5.x) * hy + (t4.y - t4.x) * hz;
         f0.y = (t0.y - t0m.y) * hx + (t5yf.y - t5.y) * hy + (t4zf - t4.y) * hz;
-        store_f(fo.p[0], oq, f0);
+        tile_store(fo.p[0], oq, f0, nt);
       }
       if (st >= 1) {
         const long op = plane(q - 1);
-        store_f(fo.p[1], op, make_double2((t5.x - t5m.x) * hx + part1.x, (t5.y - t5m.y) * hx + part1.y));
-        store_f(fo.p[2], op, make_double2((t4.x - t4m.x) * hx + part2.x, (t4.y - t4m.y) * hx + part2.y));
+        tile_store(fo.p[1], op, make_double2((t5.x - t5m.x) * hx + part1.x, (t5.y - t5m.y) * hx + part1.y), nt);
+        tile_store(fo.p[2], op, make_double2((t4.x - t4m.x) * hx + part2.x, (t4.y - t4m.y) * hx + part2.y), nt);
       }
     }
     part1.x = (t1.x - t1yb.x) * hy + (t3.y - t3.x) * hz;
@@ -899,25 +731,7 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_eps_tile(Grid g, d
     part2.y = (t3yf.y - t3.y) * hy + (t2.y - t2.x) * hz;
     t0m = t0; t5m = t5; t4m = t4;
   }
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    double a = acc[c];
-    a += dpp_move<0x128>(a);
-    a += dpp_move<0x124>(a);
-    a += dpp_move<0x122>(a);
-    a += dpp_move<0x121>(a);
-    acc[c] = (read_lane(a, 0) + read_lane(a, 16)) + (read_lane(a, 32) + read_lane(a, 48));
-  }
-  if (l == 0) {
-#pragma unroll
-    for (int c = 0; c < 6; ++c) red[wv * 6 + c] = acc[c];
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    double a = 0.0;
-    for (int w = 0; w < TYR * NZS; ++w) a += red[w * 6 + threadIdx.x];
-    partial[(long)blockIdx.x * 6 + threadIdx.x] = a;
-  }
+  tile_reduce<6, TYR * NZS>(acc, red, partial, 6, wv, l);
 }
 
 // Scalar modes (heat / porous), fast variant of k_sc_sweep (fg_kernels_scalar.hip): the per-voxel effective
@@ -1042,22 +856,30 @@ bool u_tile_supported(const Grid& g) {
   return g.nz % 2 == 0 && nzh >= 40 && g.ny >= 14 && g.nx >= 4;
 }
 
-// Planes per march of the tiled sweep.  A march of LX planes costs LX + 3 steps (pipeline fill), the workgroups are dealt
-// to the CUs in rounds, and a CU with two workgroups runs each at half speed, so the sweep takes about
-// ceil(tiles * ceil(nx / LX) / CUs) * (LX + 3) steps: the LX with the smallest product wins, the longer march on a tie.
-// Measured against the fixed 32 / 16 of round 1: 128^3 16 -> 12 planes (242 workgroups on 256 CUs) 0.0366 -> 0.0347 ms,
-// 11 planes (264: a second round) 0.049 ms; 256^3 32 -> 64 (exactly 256 workgroups) 0.210 -> 0.203 ms, 48 (384) 0.265 ms;
-// 512^3 32 -> 64: -1 %; thin x-slabs 32 x 256 x 256 -> 8, 64 x 512 x 512 -> 16 as measured before (44.7 -> 39.9 us,
-// 281 -> 240 us).
-inline int march_length(int nx, long tiles, int cus) {
-  int best = nx < 4 ? nx : 4;
-  long best_cost = -1;
-  for (int lx = 4; lx <= nx && lx <= 64; ++lx) {   // (128-plane marches: 384^3 0.727 -> 0.766 ms, 512^3 no gain: neighbouring tiles drift apart)
-    const long groups = tiles * ((nx + lx - 1) / lx);
-    const long cost = ((groups + cus - 1) / cus) * (lx + 3);
-    if (best_cost < 0 || cost <= best_cost) best = lx, best_cost = cost;
+// nt of a sweep whose output is `fields` components: set where they are larger than `mb` MB, i.e. than what the Infinity
+// Cache keeps until the next kernel reads them (tile_store)
+static int tile_nt(const Grid& g, int fields, double mb) {
+  return (double)fields * (double)g.n * sizeof(double) > mb * 1024 * 1024 ? 1 : 0;
+}
+
+// One launch of a tiled marching sweep with tiles of TYR x ZS: the plan for march_cus CUs (fg_tile_frame.h), the opt-in to
+// `lds` bytes of dynamic LDS once per device and kernel (0: the images are static), the launch with the arguments
+// args_of(plan) returns as a tuple, and the fold of the workgroups' ncols partial columns into sums.
+template <auto Kernel, int TYR, int ZS, class ArgsOf>
+void launch_tile(const Grid& g, int march_cus, MarchRule rule, size_t lds, int ncols, double* partial, double* sums, hipStream_t s,
+                 ArgsOf&& args_of) {
+  const TilePlan p = tile_plan(g, TYR, ZS, march_cus, rule);
+  if (lds > 0) {
+    static PerDeviceOnce configured;
+    if (auto once = configured.first_use()) {
+      FG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
   }
-  return best;
+  std::apply([&](auto... a) { hipLaunchKernelGGL(Kernel, dim3(p.nb), dim3(TileShape<TYR, ZS>::THREADS), lds, s, a...); },
+             args_of(p));
+  FG_HIP_CHECK(hipGetLastError());
+  fold_sum(partial, p.nb, ncols, sums, s);
+  FG_HIP_CHECK(hipGetLastError());
 }
 
 template <int TYR, int ZS, bool SUMT, bool PHI2 = false, bool CGP = false, int NMOD = 2, bool ANISO = false>
@@ -1065,71 +887,21 @@ void launch_u_tile_t(const Grid& g, double mu_0, double lambda_0, const FieldPtr
                      const FieldPtrs<3>& f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s,
                      const std::conditional_t<ANISO, AnisoLin, PhaseLin>& lin = std::conditional_t<ANISO, AnisoLin, PhaseLin>{},
                      const CgDirection& cg = CgDirection{}) {
-  constexpr int NZS = ZS ? ZS : 1;
-  constexpr int TYU = TYR - 2, TZU = ZS ? 64 * ZS : 62;
-  const int nzh = g.nz / 2;
-  const int nty = (g.ny + TYU - 1) / TYU, ntz = (nzh + TZU - 1) / TZU;
-  const int cus = device_cu_count();
-  int LX = march_length(g.nx, (long)nty * ntz, cus);   // (a sweep of fixed lengths 3 ... 10 at 100^3 - 150^3: none beats it)
-  if (LX > g.nx) LX = g.nx;
-  const int ntx = (g.nx + LX - 1) / LX;
-  int nb = nty * ntz * ntx;
-  if (nb >= 8) nb = ((nb + 7) / 8) * 8;
-  const size_t lds = (6 * TYR + (ANISO ? 6 : 0)) * NZS * 64 * sizeof(double2);   // ANISO: two more rows of u per component
-  static PerDeviceOnce configured;
-  if (auto once = configured.first_use()) {
-    FG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_u_tile<TYR, ZS, SUMT, PHI2, CGP, NMOD, ANISO>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  const int nt = 3.0 * (double)g.n * sizeof(double) > 256.0 * 1024 * 1024 ? 1 : 0;
-  hipLaunchKernelGGL((k_u_tile<TYR, ZS, SUMT, PHI2, CGP, NMOD, ANISO>), dim3(nb), dim3(TYR * NZS * 64), lds, s, g, -2 * mu_0, -lambda_0, u, mod, f,
-                     E, partial, nty, ntz, LX, nt, lin, cg);
-  FG_HIP_CHECK(hipGetLastError());
-  fold_sum(partial, nb, SUMT ? 12 : 6, sumsq6, s);
-  FG_HIP_CHECK(hipGetLastError());
+  const size_t lds = (6 * TYR + (ANISO ? 6 : 0)) * TileShape<TYR, ZS>::RW * sizeof(double2);   // ANISO: two more rows of u per component
+  const int nt = tile_nt(g, 3, 256.0);
+  // (a sweep of fixed march lengths 3 ... 10 at 100^3 - 150^3: none beats march_length)
+  launch_tile<&k_u_tile<TYR, ZS, SUMT, PHI2, CGP, NMOD, ANISO>, TYR, ZS>(
+      g, device_cu_count(), MarchRule::balanced, lds, SUMT ? 12 : 6, partial, sumsq6, s, [&](const TilePlan& p) {
+        return std::make_tuple(g, -2 * mu_0, -lambda_0, u, mod, f, E, partial, p.nty, p.ntz, p.LX, nt, lin, cg);
+      });
 }
 
-void launch_u_tile(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& u, const FieldPtrs<2>& mod,
-                   const FieldPtrs<3>& f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s,
-                   bool sum_tau, const PhaseTable* two_phase) {
-  const int nzh = g.nz / 2;
-  if (two_phase) {   // mod.p[0] is phi_1 of two complementary phases: the default tile shapes
-    const PhaseLin lin = {2 * two_phase->mu[0] - 2 * mu_0, 2 * (two_phase->mu[1] - two_phase->mu[0]),
-                          two_phase->lambda[0] - lambda_0, two_phase->lambda[1] - two_phase->lambda[0]};
-#define FG_PHI(R, Z)                                                                                                  \
-  do {                                                                                                                \
-    if (sum_tau) launch_u_tile_t<R, Z, true, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s, lin);        \
-    else launch_u_tile_t<R, Z, false, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s, lin);               \
-  } while (0)
-    if (nzh == 64) FG_PHI(8, 1);
-    else if (nzh == 128) FG_PHI(6, 2);
-    else FG_PHI(8, 0);
-#undef FG_PHI
-    return;
-  }
-  if (sum_tau) {   // sumsq6[0..5] sums of squares of the strain, sumsq6[6..11] sums of the polarisation
-    if (nzh == 64) launch_u_tile_t<8, 1, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s);
-    else if (nzh == 128) launch_u_tile_t<6, 2, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s);
-    else launch_u_tile_t<8, 0, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s);
-    return;
-  }
-#define FG_TILE(R, Z) launch_u_tile_t<R, Z, false>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s)
-  if (nzh == 64) {          // a z row is one wave
-    FG_TILE(8, 1);
-  } else if (nzh == 128) {  // a z row is two waves: 6 rows x 2 segments (256^3: 0.268 ms against 0.325 ms with halo lanes;
-    FG_TILE(6, 2);          // 8 x 2 = 16 waves in lock-step 0.38 ms, 4 x 2 0.31 ms)
-  } else {                  // general: tiles of 62 pairs with halo lanes
-    FG_TILE(8, 0);       // (12- and 16-row tiles move fewer halo bytes -- 512^3: 8.95 -> 8.5 GB -- in the same time: rounds 1 and 5)
-  }
-#undef FG_TILE
+static PhaseLin make_phase_lin(const PhaseTable& pt, double mu_0, double lambda_0) {
+  return PhaseLin{2 * pt.mu[0] - 2 * mu_0, 2 * (pt.mu[1] - pt.mu[0]), pt.lambda[0] - lambda_0, pt.lambda[1] - pt.lambda[0]};
 }
 
-// k_u_tile with the search direction of the conjugate gradients formed on the fly: u := r + b u -> po (see CgDirection);
-// the default tile shapes, no sums of tau
-void launch_u_tile_cg(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& p_old, const FieldPtrs<3>& r,
-                      const FieldPtrs<3>& p_new, const FieldPtrs<2>& mod, const FieldPtrs<3>& f, const Vec6& E, const double* sc,
-                      int i_num, int i_den, double nvox, double small, double* partial, double* sumsq6, hipStream_t s,
-                      const PhaseTable* two_phase) {
+static CgDirection make_cg_direction(const FieldPtrs<3>& r, const FieldPtrs<3>& p_new, const double* sc, int i_num, int i_den,
+                                     double nvox, double small) {
   CgDirection cg;
   for (int c = 0; c < 3; ++c) cg.r[c] = r.p[c], cg.po[c] = p_new.p[c];
   cg.sc = sc;
@@ -1137,20 +909,41 @@ void launch_u_tile_cg(const Grid& g, double mu_0, double lambda_0, const FieldPt
   cg.i_den = i_den;
   cg.nvox = nvox;
   cg.small = small;
-  const int nzh = g.nz / 2;
-  PhaseLin lin = {0, 0, 0, 0};
-  if (two_phase)
-    lin = PhaseLin{2 * two_phase->mu[0] - 2 * mu_0, 2 * (two_phase->mu[1] - two_phase->mu[0]), two_phase->lambda[0] - lambda_0,
-                   two_phase->lambda[1] - two_phase->lambda[0]};
-#define FG_CGK(R, Z)                                                                                                            \
-  do {                                                                                                                          \
-    if (two_phase) launch_u_tile_t<R, Z, false, true, true>(g, mu_0, lambda_0, p_old, mod, f, E, partial, sumsq6, s, lin, cg);   \
-    else launch_u_tile_t<R, Z, false, false, true>(g, mu_0, lambda_0, p_old, mod, f, E, partial, sumsq6, s, lin, cg);            \
-  } while (0)
-  if (nzh == 64) FG_CGK(8, 1);
-  else if (nzh == 128) FG_CGK(6, 2);
-  else FG_CGK(8, 0);
-#undef FG_CGK
+  return cg;
+}
+
+// sum_tau: sumsq6[0..5] sums of squares of the strain, sumsq6[6..11] sums of the polarisation.  two_phase: mod.p[0] is phi_1
+// of two complementary phases
+void launch_u_tile(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& u, const FieldPtrs<2>& mod,
+                   const FieldPtrs<3>& f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s,
+                   bool sum_tau, const PhaseTable* two_phase) {
+  tile_shape_dispatch(g.nz / 2, [&](auto R, auto Z) {
+    constexpr int TYR = decltype(R)::value, ZS = decltype(Z)::value;
+    if (two_phase) {
+      const PhaseLin lin = make_phase_lin(*two_phase, mu_0, lambda_0);
+      if (sum_tau) launch_u_tile_t<TYR, ZS, true, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s, lin);
+      else launch_u_tile_t<TYR, ZS, false, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s, lin);
+    } else if (sum_tau) {
+      launch_u_tile_t<TYR, ZS, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s);
+    } else {
+      launch_u_tile_t<TYR, ZS, false>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s);
+    }
+  });
+}
+
+// k_u_tile with the search direction of the conjugate gradients formed on the fly: u := r + b u -> po (see CgDirection);
+// no sums of tau
+void launch_u_tile_cg(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& p_old, const FieldPtrs<3>& r,
+                      const FieldPtrs<3>& p_new, const FieldPtrs<2>& mod, const FieldPtrs<3>& f, const Vec6& E, const double* sc,
+                      int i_num, int i_den, double nvox, double small, double* partial, double* sumsq6, hipStream_t s,
+                      const PhaseTable* two_phase) {
+  const CgDirection cg = make_cg_direction(r, p_new, sc, i_num, i_den, nvox, small);
+  const PhaseLin lin = two_phase ? make_phase_lin(*two_phase, mu_0, lambda_0) : PhaseLin{0, 0, 0, 0};
+  tile_shape_dispatch(g.nz / 2, [&](auto R, auto Z) {
+    constexpr int TYR = decltype(R)::value, ZS = decltype(Z)::value;
+    if (two_phase) launch_u_tile_t<TYR, ZS, false, true, true>(g, mu_0, lambda_0, p_old, mod, f, E, partial, sumsq6, s, lin, cg);
+    else launch_u_tile_t<TYR, ZS, false, false, true>(g, mu_0, lambda_0, p_old, mod, f, E, partial, sumsq6, s, lin, cg);
+  });
 }
 
 // D0 = C_0 - C0 and D1 = C_1 - C_0 of two phases, an isotropic one expanded to its 6 x 6 (Voigt shear entries: C44 = mu), as
@@ -1182,25 +975,21 @@ static AnisoLin make_aniso_lin(const PhaseTable& pt, double mu_0, double lambda_
   return lin;
 }
 
-// the tiled sweep of two complementary phases with a general phase (k_u_tile ANISO): phi1 = phi_1, the default tile shapes
+// the tiled sweep of two complementary phases with a general phase (k_u_tile ANISO): phi1 = phi_1.
+// (no <6, 2> form: a workgroup of 768 threads may use 168 VGPRs and every variant tried spills past them into scratch, which
+// this kernel must not use -- figures in DESIGN.md 4a; rows of 128 pairs take the general tiles of 62 pairs)
 void launch_u_tile_aniso(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& u, const double* phi1,
                          const FieldPtrs<3>& f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s, bool sum_tau,
                          const PhaseTable& two_phase) {
-  const int nzh = g.nz / 2;
   const AnisoLin lin = make_aniso_lin(two_phase, mu_0, lambda_0);
   FieldPtrs<2> mod;
   mod.p[0] = const_cast<double*>(phi1);
   mod.p[1] = nullptr;
-#define FG_ANI(R, Z)                                                                                                              \
-  do {                                                                                                                            \
-    if (sum_tau) launch_u_tile_t<R, Z, true, true, false, 2, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s, lin);    \
-    else launch_u_tile_t<R, Z, false, true, false, 2, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s, lin);           \
-  } while (0)
-  // (no <6, 2> form: a workgroup of 768 threads may use 168 VGPRs and every variant tried spills past them into scratch, which
-  // this kernel must not use -- figures in DESIGN.md 4a; rows of 128 pairs take the general tiles of 62 pairs)
-  if (nzh == 64) FG_ANI(8, 1);
-  else FG_ANI(8, 0);
-#undef FG_ANI
+  tile_shape_dispatch<false>(g.nz / 2, [&](auto R, auto Z) {
+    constexpr int TYR = decltype(R)::value, ZS = decltype(Z)::value;
+    if (sum_tau) launch_u_tile_t<TYR, ZS, true, true, false, 2, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s, lin);
+    else launch_u_tile_t<TYR, ZS, false, true, false, 2, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s, lin);
+  });
 }
 
 // ... with the search direction of the conjugate gradients formed on the fly (see launch_u_tile_cg)
@@ -1208,52 +997,36 @@ void launch_u_tile_aniso_cg(const Grid& g, double mu_0, double lambda_0, const F
                             const FieldPtrs<3>& p_new, const double* phi1, const FieldPtrs<3>& f, const Vec6& E, const double* sc,
                             int i_num, int i_den, double nvox, double small, double* partial, double* sumsq6, hipStream_t s,
                             const PhaseTable& two_phase) {
-  CgDirection cg;
-  for (int c = 0; c < 3; ++c) cg.r[c] = r.p[c], cg.po[c] = p_new.p[c];
-  cg.sc = sc;
-  cg.i_num = i_num;
-  cg.i_den = i_den;
-  cg.nvox = nvox;
-  cg.small = small;
-  const int nzh = g.nz / 2;
+  const CgDirection cg = make_cg_direction(r, p_new, sc, i_num, i_den, nvox, small);
   const AnisoLin lin = make_aniso_lin(two_phase, mu_0, lambda_0);
   FieldPtrs<2> mod;
   mod.p[0] = const_cast<double*>(phi1);
   mod.p[1] = nullptr;
-  if (nzh == 64) launch_u_tile_t<8, 1, false, true, true, 2, true>(g, mu_0, lambda_0, p_old, mod, f, E, partial, sumsq6, s, lin, cg);
-  else launch_u_tile_t<8, 0, false, true, true, 2, true>(g, mu_0, lambda_0, p_old, mod, f, E, partial, sumsq6, s, lin, cg);
+  tile_shape_dispatch<false>(g.nz / 2, [&](auto R, auto Z) {
+    launch_u_tile_t<decltype(R)::value, decltype(Z)::value, false, true, true, 2, true>(g, mu_0, lambda_0, p_old, mod, f, E, partial,
+                                                                                        sumsq6, s, lin, cg);
+  });
 }
 
-// gamma_scheme full_staggered: the same sweeps on the five moduli of the doubly fine grid (default tile shapes)
+// gamma_scheme full_staggered: the same sweeps on the five moduli of the doubly fine grid
 void launch_u_tile(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& u, const FieldPtrs<5>& mod,
                    const FieldPtrs<3>& f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s, bool sum_tau) {
-  const int nzh = g.nz / 2;
-#define FG_DFG(R, Z)                                                                                                    \
-  do {                                                                                                                  \
-    if (sum_tau) launch_u_tile_t<R, Z, true, false, false, 5>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s);    \
-    else launch_u_tile_t<R, Z, false, false, false, 5>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s);           \
-  } while (0)
-  if (nzh == 64) FG_DFG(8, 1);
-  else if (nzh == 128) FG_DFG(6, 2);
-  else FG_DFG(8, 0);
-#undef FG_DFG
+  tile_shape_dispatch(g.nz / 2, [&](auto R, auto Z) {
+    constexpr int TYR = decltype(R)::value, ZS = decltype(Z)::value;
+    if (sum_tau) launch_u_tile_t<TYR, ZS, true, false, false, 5>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s);
+    else launch_u_tile_t<TYR, ZS, false, false, false, 5>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s);
+  });
 }
 
 void launch_u_tile_cg(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& p_old, const FieldPtrs<3>& r,
                       const FieldPtrs<3>& p_new, const FieldPtrs<5>& mod, const FieldPtrs<3>& f, const Vec6& E, const double* sc,
                       int i_num, int i_den, double nvox, double small, double* partial, double* sumsq6, hipStream_t s) {
-  CgDirection cg;
-  for (int c = 0; c < 3; ++c) cg.r[c] = r.p[c], cg.po[c] = p_new.p[c];
-  cg.sc = sc;
-  cg.i_num = i_num;
-  cg.i_den = i_den;
-  cg.nvox = nvox;
-  cg.small = small;
-  const int nzh = g.nz / 2;
+  const CgDirection cg = make_cg_direction(r, p_new, sc, i_num, i_den, nvox, small);
   const PhaseLin lin = {0, 0, 0, 0};
-  if (nzh == 64) launch_u_tile_t<8, 1, false, false, true, 5>(g, mu_0, lambda_0, p_old, mod, f, E, partial, sumsq6, s, lin, cg);
-  else if (nzh == 128) launch_u_tile_t<6, 2, false, false, true, 5>(g, mu_0, lambda_0, p_old, mod, f, E, partial, sumsq6, s, lin, cg);
-  else launch_u_tile_t<8, 0, false, false, true, 5>(g, mu_0, lambda_0, p_old, mod, f, E, partial, sumsq6, s, lin, cg);
+  tile_shape_dispatch(g.nz / 2, [&](auto R, auto Z) {
+    launch_u_tile_t<decltype(R)::value, decltype(Z)::value, false, false, true, 5>(g, mu_0, lambda_0, p_old, mod, f, E, partial,
+                                                                                    sumsq6, s, lin, cg);
+  });
 }
 
 // *flag := 0 unless phi0 == 1 - phi1 bit for bit at every voxel (what normalizePhi F:17613-17626 produces for two phases);
@@ -1301,57 +1074,16 @@ template <int TYR, int ZS, bool SUMT = false, bool CGP = false>
 __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_sc_tile(Grid g, double beta, const double* T, const double* a,
                                                                        double* fo, Vec6 E, double* partial, int nty, int ntz,
                                                                        int LX, int nt, ScCgDirection cg) {
-  constexpr bool FULLROW = ZS > 0;
-  constexpr int NZS = ZS ? ZS : 1;
-  constexpr int TYU = TYR - 2;
-  constexpr int TZU = FULLROW ? 64 * NZS : 62;
-  constexpr int RW = NZS * 64;
+  using S = TileShape<TYR, ZS>;
+  constexpr bool FULLROW = S::FULLROW;
+  constexpr int NZS = S::NZS, RW = S::RW;
   __shared__ double2 Tb[2][TYR][RW];
   __shared__ double2 Cb[2][TYR][RW];
   constexpr int NA = SUMT ? 6 : 3;
   __shared__ double red[TYR * NZS * NA];
 
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int r = wv / NZS, zs = wv % NZS;
-  const int li = zs * 64 + l;
-  const int zprev = (zs + NZS - 1) % NZS, znext = (zs + 1) % NZS;
-  const int nzh = g.nz / 2;
-  int b = blockIdx.x;
-  {
-    const int nb = gridDim.x;
-    if (nb % 8 == 0) b = (b % 8) * (nb / 8) + b / 8;   // one XCD takes a contiguous run of tiles
-  }
-  const int tz = b % ntz;
-  b /= ntz;
-  const int ty = b % nty;
-  const int tx = b / nty;
-  const bool surplus = tx * LX >= g.nx;
-  const int j0 = min(ty * TYU, g.ny - TYU), kp0 = min(tz * TZU, nzh - TZU), x0 = surplus ? 0 : tx * LX;
-  const int jr = j0 - 1 + r;
-  const int j = jr < 0 ? jr + g.ny : (jr >= g.ny ? jr - g.ny : jr);
-  const int kr = FULLROW ? li : kp0 - 1 + l;
-  const int kp = kr < 0 ? kr + nzh : (kr >= nzh ? kr - nzh : kr);
-  const bool own = r >= 1 && r <= TYU && jr >= ty * TYU && (FULLROW || (l >= 1 && l <= TZU && kr >= tz * TZU));
-  const long rowoff = (long)j * g.nzp + 2 * kp;
-  const int rm = r > 0 ? r - 1 : 0, rp = r + 1 < TYR ? r + 1 : TYR - 1;
-  const double hx = g.hx, hy = g.hy, hz = g.hz;
-  const int nsteps = surplus ? 0 : (x0 + LX <= g.nx ? LX : g.nx - x0);
-
-  auto plane = [&](int q) {   // x neighbours through Grid::xw_lo / xw_hi (periodic grid: both nx; x-slab: its spare planes)
-    const int x = q < 0 ? q + g.xw_lo : (q >= g.nx ? q - g.xw_hi : q);
-    return (long)x * g.nyzp + rowoff;
-  };
-  auto store_f = [&](long off, double2 v) {
-    if (nt) {
-      typedef double fg_v2d __attribute__((ext_vector_type(2)));
-      fg_v2d t;
-      t.x = v.x;
-      t.y = v.y;
-      __builtin_nontemporal_store(t, reinterpret_cast<fg_v2d*>(fo + off));
-    } else {
-      st2(fo, off, v);
-    }
-  };
+  // x neighbours through Grid::xw_lo / xw_hi (periodic grid: both nx; x-slab: its spare planes)
+  FG_TILE_FRAME(TYR, ZS, XWrap::slab, 0, g, nty, ntz, LX, blockIdx.x, gridDim.x, threadIdx.x);
 
   const double cgb = CGP ? (cg.sc[cg.i_num] / cg.nvox + cg.small) / (cg.sc[cg.i_den] / cg.nvox + cg.small) : 0.0;
   auto load_T = [&](long o, bool keep) {
@@ -1384,7 +1116,7 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_sc_tile(Grid g, do
     Cb[img][r][li] = cc;
     __syncthreads();
     const double2 Tyf = Tb[img][rp][li], Tyb = Tb[img][rm][li], cyb = Cb[img][rm][li];
-    double Tzb = dpp_move<0x138>(Tc.y), czb = dpp_move<0x138>(cc.y), Tzf = dpp_move<0x130>(Tc.x);
+    double Tzb = lane_prev(Tc.y), czb = lane_prev(cc.y), Tzf = lane_next(Tc.x);
     if (FULLROW) {
       if (l == 0) {
         Tzb = Tb[img][r][zprev * 64 + 63].y;
@@ -1411,31 +1143,12 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_sc_tile(Grid g, do
         acc[NA - 2] += cc.x * g1x + cc.y * g1y;
         acc[NA - 1] += cc.x * g2x + cc.y * g2y;
       }
-      store_f(oq, f);
+      tile_store(fo, oq, f, nt);
     }
     q0m.x = q0x; q0m.y = q0y;
     Tc = Tn; Tn = T2; ac = an;
   }
-#pragma unroll
-  for (int c = 0; c < NA; ++c) {
-    double v = acc[c];
-    v += dpp_move<0x128>(v);
-    v += dpp_move<0x124>(v);
-    v += dpp_move<0x122>(v);
-    v += dpp_move<0x121>(v);
-    acc[c] = (read_lane(v, 0) + read_lane(v, 16)) + (read_lane(v, 32) + read_lane(v, 48));
-  }
-  if (l == 0) {
-#pragma unroll
-    for (int c = 0; c < NA; ++c) red[wv * NA + c] = acc[c];
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    double v = 0.0;
-    if (threadIdx.x < NA)
-      for (int w = 0; w < TYR * NZS; ++w) v += red[w * NA + threadIdx.x];
-    partial[(long)blockIdx.x * 6 + threadIdx.x] = v;
-  }
+  tile_reduce<NA, TYR * NZS>(acc, red, partial, 6, wv, l);   // the fold takes six columns: zeros past NA
 }
 
 // sums of the scalar sweep with SUMT: [0..2] norms, [3..5] tau -> sumsq6 = (norms, 0, 0, 0), sumtau3 = tau sums
@@ -1447,38 +1160,25 @@ __global__ void k_sc_split_sums(double* sumsq6, double* sumtau3) {
   }
 }
 
-template <int TYR, int ZS>
-void launch_sc_tile_t(const Grid& g, double mu_0, const double* T, const double* a, double* f, const Vec6& E, double* partial,
-                      double* sumsq6, hipStream_t s, double* sumtau3, const ScCgDirection* cgd = nullptr) {
-  constexpr int NZS = ZS ? ZS : 1;
-  constexpr int TYU = TYR - 2, TZU = ZS ? 64 * ZS : 62;
-  const int nzh = g.nz / 2;
-  const int nty = (g.ny + TYU - 1) / TYU, ntz = (nzh + TZU - 1) / TZU;
-  const int cus = device_cu_count();
-  int LX = march_length(g.nx, (long)nty * ntz, 2 * cus);   // the light scalar sweep runs two workgroups per CU at full speed
-  if (LX > g.nx) LX = g.nx;
-  const int ntx = (g.nx + LX - 1) / LX;
-  int nb = nty * ntz * ntx;
-  if (nb >= 8) nb = ((nb + 7) / 8) * 8;
-  const int nt = (double)g.n * sizeof(double) > 128.0 * 1024 * 1024 ? 1 : 0;
+// the three forms of the tiled scalar sweep on the grid's tile shape: with the sums of tau (sumtau3), on the new direction of
+// the conjugate gradients (cgd), or plain.  The march is sized for two workgroups per CU: the light scalar sweeps run two at
+// full speed (likewise k_sc_tile_aniso and k_sc_cgu_tile).
+static void launch_sc_tile(const Grid& g, double mu_0, const double* T, const double* a, double* f, const Vec6& E, double* partial,
+                           double* sumsq6, hipStream_t s, double* sumtau3, const ScCgDirection* cgd = nullptr) {
+  const int nt = tile_nt(g, 1, 128.0);
+  const ScCgDirection cg = cgd ? *cgd : ScCgDirection{};
+  auto args = [&](const TilePlan& p) { return std::make_tuple(g, -2 * mu_0, T, a, f, E, partial, p.nty, p.ntz, p.LX, nt, cg); };
+  tile_shape_dispatch(g.nz / 2, [&](auto R, auto Z) {   // (<6, 2>: 48 KB of LDS images)
+    constexpr int TYR = decltype(R)::value, ZS = decltype(Z)::value;
+    const int cus = 2 * device_cu_count();
+    if (sumtau3) launch_tile<&k_sc_tile<TYR, ZS, true>, TYR, ZS>(g, cus, MarchRule::balanced, 0, 6, partial, sumsq6, s, args);
+    else if (cgd) launch_tile<&k_sc_tile<TYR, ZS, false, true>, TYR, ZS>(g, cus, MarchRule::balanced, 0, 6, partial, sumsq6, s, args);
+    else launch_tile<&k_sc_tile<TYR, ZS>, TYR, ZS>(g, cus, MarchRule::balanced, 0, 6, partial, sumsq6, s, args);
+  });
   if (sumtau3) {
-    hipLaunchKernelGGL((k_sc_tile<TYR, ZS, true>), dim3(nb), dim3(TYR * NZS * 64), 0, s, g, -2 * mu_0, T, a, f, E, partial, nty,
-                       ntz, LX, nt, ScCgDirection{});
-    FG_HIP_CHECK(hipGetLastError());
-    fold_sum(partial, nb, 6, sumsq6, s);
     hipLaunchKernelGGL(k_sc_split_sums, dim3(1), dim3(64), 0, s, sumsq6, sumtau3);
     FG_HIP_CHECK(hipGetLastError());
-    return;
   }
-  if (cgd)
-    hipLaunchKernelGGL((k_sc_tile<TYR, ZS, false, true>), dim3(nb), dim3(TYR * NZS * 64), 0, s, g, -2 * mu_0, T, a, f, E, partial, nty,
-                       ntz, LX, nt, *cgd);
-  else
-    hipLaunchKernelGGL((k_sc_tile<TYR, ZS>), dim3(nb), dim3(TYR * NZS * 64), 0, s, g, -2 * mu_0, T, a, f, E, partial, nty, ntz,
-                       LX, nt, ScCgDirection{});
-  FG_HIP_CHECK(hipGetLastError());
-  fold_sum(partial, nb, 6, sumsq6, s);
-  FG_HIP_CHECK(hipGetLastError());
 }
 
 // k_sc_tile for two complementary phases of which at least one has law aniso (MatrixLinearAnisotropicMaterialLaw  F:11087-11156):
@@ -1500,58 +1200,16 @@ template <int TYR, int ZS, bool CGP = false>
 __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_sc_tile_aniso(Grid g, ScAnisoLin K, const double* T, const double* phi1,
                                                                              double* fo, Vec6 E, double* partial, int nty, int ntz,
                                                                              int LX, int nt, ScCgDirection cg) {
-  constexpr bool FULLROW = ZS > 0;
-  constexpr int NZS = ZS ? ZS : 1;
-  constexpr int TYU = TYR - 2;
-  constexpr int TZU = FULLROW ? 64 * NZS : 62;
-  constexpr int RW = NZS * 64;
+  using S = TileShape<TYR, ZS>;
+  constexpr bool FULLROW = S::FULLROW;
+  constexpr int NZS = S::NZS, RW = S::RW;
   __shared__ double2 Tb[2][TYR][RW];
   __shared__ double2 Qb[2][TYR][RW];    // q_y of the plane
   __shared__ double Zb[2][TYR][NZS];    // q_z of the last voxel of every wave (whole rows: the z neighbour across waves)
   constexpr int NA = 3;
   __shared__ double red[TYR * NZS * NA];
 
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int r = wv / NZS, zs = wv % NZS;
-  const int li = zs * 64 + l;
-  const int zprev = (zs + NZS - 1) % NZS, znext = (zs + 1) % NZS;
-  const int nzh = g.nz / 2;
-  int b = blockIdx.x;
-  {
-    const int nb = gridDim.x;
-    if (nb % 8 == 0) b = (b % 8) * (nb / 8) + b / 8;   // one XCD takes a contiguous run of tiles
-  }
-  const int tz = b % ntz;
-  b /= ntz;
-  const int ty = b % nty;
-  const int tx = b / nty;
-  const bool surplus = tx * LX >= g.nx;
-  const int j0 = min(ty * TYU, g.ny - TYU), kp0 = min(tz * TZU, nzh - TZU), x0 = surplus ? 0 : tx * LX;
-  const int jr = j0 - 1 + r;
-  const int j = jr < 0 ? jr + g.ny : (jr >= g.ny ? jr - g.ny : jr);
-  const int kr = FULLROW ? li : kp0 - 1 + l;
-  const int kp = kr < 0 ? kr + nzh : (kr >= nzh ? kr - nzh : kr);
-  const bool own = r >= 1 && r <= TYU && jr >= ty * TYU && (FULLROW || (l >= 1 && l <= TZU && kr >= tz * TZU));
-  const long rowoff = (long)j * g.nzp + 2 * kp;
-  const int rm = r > 0 ? r - 1 : 0, rp = r + 1 < TYR ? r + 1 : TYR - 1;
-  const double hx = g.hx, hy = g.hy, hz = g.hz;
-  const int nsteps = surplus ? 0 : (x0 + LX <= g.nx ? LX : g.nx - x0);
-
-  auto plane = [&](int q) {
-    const int x = q < 0 ? q + g.xw_lo : (q >= g.nx ? q - g.xw_hi : q);
-    return (long)x * g.nyzp + rowoff;
-  };
-  auto store_f = [&](long off, double2 v) {
-    if (nt) {
-      typedef double fg_v2d __attribute__((ext_vector_type(2)));
-      fg_v2d t;
-      t.x = v.x;
-      t.y = v.y;
-      __builtin_nontemporal_store(t, reinterpret_cast<fg_v2d*>(fo + off));
-    } else {
-      st2(fo, off, v);
-    }
-  };
+  FG_TILE_FRAME(TYR, ZS, XWrap::slab, 0, g, nty, ntz, LX, blockIdx.x, gridDim.x, threadIdx.x);
   const double cgb = CGP ? (cg.sc[cg.i_num] / cg.nvox + cg.small) / (cg.sc[cg.i_den] / cg.nvox + cg.small) : 0.0;
   auto load_T = [&](long o, bool keep) {
     double2 v = ld2(T, o);
@@ -1574,7 +1232,7 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_sc_tile_aniso(Grid
   // the forward neighbours in y (image) and z (next lane / next wave's first lane) of the plane held in image `img`
   auto forward = [&](int img, double2 Tc, double2& Tyf, double& Tzf) {
     Tyf = Tb[img][rp][li];
-    Tzf = dpp_move<0x130>(Tc.x);
+    Tzf = lane_next(Tc.x);
     if (FULLROW) {
       if (l == 63) Tzf = Tb[img][r][znext * 64].x;
     }
@@ -1619,7 +1277,7 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_sc_tile_aniso(Grid
       double2 f;
       f.x = fx.x + (qyp.x - qyb.x) * hy + (qzp.x - qzb) * hz;
       f.y = fx.y + (qyp.y - qyb.y) * hy + (qzp.y - qzp.x) * hz;
-      if (own) store_f(op, f);
+      if (own) tile_store(fo, op, f, nt);
     }
     if (live) {
       double2 Tyf;
@@ -1635,7 +1293,7 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_sc_tile_aniso(Grid
       if (FULLROW) {
         if (l == 63) Zb[img][r][zs] = qz.y;
       }
-      qzbp = dpp_move<0x138>(qz.y);
+      qzbp = lane_prev(qz.y);
       if (own) {
         acc[0] += g0x * g0x + g0y * g0y;
         acc[1] += g1x * g1x + g1y * g1y;
@@ -1650,51 +1308,7 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_sc_tile_aniso(Grid
       Tc = Tn; Tn = T2; pc = pn;
     }
   }
-#pragma unroll
-  for (int c = 0; c < NA; ++c) {
-    double v = acc[c];
-    v += dpp_move<0x128>(v);
-    v += dpp_move<0x124>(v);
-    v += dpp_move<0x122>(v);
-    v += dpp_move<0x121>(v);
-    acc[c] = (read_lane(v, 0) + read_lane(v, 16)) + (read_lane(v, 32) + read_lane(v, 48));
-  }
-  if (l == 0) {
-#pragma unroll
-    for (int c = 0; c < NA; ++c) red[wv * NA + c] = acc[c];
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    double v = 0.0;
-    if (threadIdx.x < NA)
-      for (int w = 0; w < TYR * NZS; ++w) v += red[w * NA + threadIdx.x];
-    partial[(long)blockIdx.x * 6 + threadIdx.x] = v;
-  }
-}
-
-template <int TYR, int ZS>
-void launch_sc_tile_aniso_t(const Grid& g, const ScAnisoLin& K, const double* T, const double* phi1, double* f, const Vec6& E,
-                            double* partial, double* sumsq6, hipStream_t s, const ScCgDirection* cgd) {
-  constexpr int NZS = ZS ? ZS : 1;
-  constexpr int TYU = TYR - 2, TZU = ZS ? 64 * ZS : 62;
-  const int nzh = g.nz / 2;
-  const int nty = (g.ny + TYU - 1) / TYU, ntz = (nzh + TZU - 1) / TZU;
-  const int cus = device_cu_count();
-  int LX = march_length(g.nx, (long)nty * ntz, 2 * cus);
-  if (LX > g.nx) LX = g.nx;
-  const int ntx = (g.nx + LX - 1) / LX;
-  int nb = nty * ntz * ntx;
-  if (nb >= 8) nb = ((nb + 7) / 8) * 8;
-  const int nt = (double)g.n * sizeof(double) > 128.0 * 1024 * 1024 ? 1 : 0;
-  if (cgd)
-    hipLaunchKernelGGL((k_sc_tile_aniso<TYR, ZS, true>), dim3(nb), dim3(TYR * NZS * 64), 0, s, g, K, T, phi1, f, E, partial, nty, ntz,
-                       LX, nt, *cgd);
-  else
-    hipLaunchKernelGGL((k_sc_tile_aniso<TYR, ZS>), dim3(nb), dim3(TYR * NZS * 64), 0, s, g, K, T, phi1, f, E, partial, nty, ntz, LX,
-                       nt, ScCgDirection{});
-  FG_HIP_CHECK(hipGetLastError());
-  fold_sum(partial, nb, 6, sumsq6, s);
-  FG_HIP_CHECK(hipGetLastError());
+  tile_reduce<NA, TYR * NZS>(acc, red, partial, 6, wv, l);   // six columns, see k_sc_tile
 }
 
 // K0, K1: the six constants of the two phases (an isotropic phase as mu on the diagonal); cg: the direction update of the
@@ -1707,12 +1321,15 @@ void launch_sc_tile_aniso(const Grid& g, double mu_0, const double* K0, const do
     K.d0[c] = K0[c] - (c < 3 ? 2 * mu_0 : 0.0);
     K.d1[c] = K1[c] - K0[c];
   }
-  const ScCgDirection cg = {cg_r, cg_p_new, sc, i_num, i_den, nvox, small};
-  const ScCgDirection* cgd = cg_r ? &cg : nullptr;
-  const int nzh = g.nz / 2;
-  if (nzh == 64) launch_sc_tile_aniso_t<8, 1>(g, K, T, phi1, f, E, partial, sumsq6, s, cgd);
-  else if (nzh == 128) launch_sc_tile_aniso_t<6, 2>(g, K, T, phi1, f, E, partial, sumsq6, s, cgd);
-  else launch_sc_tile_aniso_t<8, 0>(g, K, T, phi1, f, E, partial, sumsq6, s, cgd);
+  const ScCgDirection cg = cg_r ? ScCgDirection{cg_r, cg_p_new, sc, i_num, i_den, nvox, small} : ScCgDirection{};
+  const int nt = tile_nt(g, 1, 128.0);
+  auto args = [&](const TilePlan& p) { return std::make_tuple(g, K, T, phi1, f, E, partial, p.nty, p.ntz, p.LX, nt, cg); };
+  tile_shape_dispatch(g.nz / 2, [&](auto R, auto Z) {
+    constexpr int TYR = decltype(R)::value, ZS = decltype(Z)::value;
+    const int cus = 2 * device_cu_count();
+    if (cg_r) launch_tile<&k_sc_tile_aniso<TYR, ZS, true>, TYR, ZS>(g, cus, MarchRule::balanced, 0, 6, partial, sumsq6, s, args);
+    else launch_tile<&k_sc_tile_aniso<TYR, ZS>, TYR, ZS>(g, cus, MarchRule::balanced, 0, 6, partial, sumsq6, s, args);
+  });
 }
 
 // Scalar sibling of k_cgu_tile (conjugate gradients in potential space, k_sc_cg_dot / k_sc_cg_axpy of fg_kernels_scalar.hip):
@@ -1725,44 +1342,14 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_sc_cgu_tile(Grid g
                                                                            const double* w, double* ao, double* bo, Vec6 E,
                                                                            const double* sc, int i_num, int i_den, double nvox,
                                                                            double small, double* partial, int nty, int ntz, int LX) {
-  constexpr bool FULLROW = ZS > 0;
-  constexpr int NZS = ZS ? ZS : 1;
-  constexpr int TYU = TYR - 2;
-  constexpr int TZU = FULLROW ? 64 * NZS : 62;
-  constexpr int RW = NZS * 64;
+  using S = TileShape<TYR, ZS>;
+  constexpr bool FULLROW = S::FULLROW;
+  constexpr int NZS = S::NZS, RW = S::RW;
   constexpr int NS = 7;
   __shared__ double2 Xb[2][2][TYR][RW];   // [image][A, B][row][pair]
   __shared__ double red[TYR * NZS * NS];
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int r = wv / NZS, zs = wv % NZS;
-  const int li = zs * 64 + l;
-  const int znext = (zs + 1) % NZS;
-  const int nzh = g.nz / 2;
-  int bi = blockIdx.x;
-  {
-    const int nb = gridDim.x;
-    if (nb % 8 == 0) bi = (bi % 8) * (nb / 8) + bi / 8;
-  }
-  const int tz = bi % ntz;
-  bi /= ntz;
-  const int ty = bi % nty;
-  const int tx = bi / nty;
-  const bool surplus = tx * LX >= g.nx;
-  const int j0 = min(ty * TYU, g.ny - TYU), kp0 = min(tz * TZU, nzh - TZU), x0 = surplus ? 0 : tx * LX;
-  const int jr = j0 - 1 + r;
-  const int j = jr < 0 ? jr + g.ny : (jr >= g.ny ? jr - g.ny : jr);
-  const int kr = FULLROW ? li : kp0 - 1 + l;
-  const int kp = kr < 0 ? kr + nzh : (kr >= nzh ? kr - nzh : kr);
-  const bool own = r >= 1 && r <= TYU && jr >= ty * TYU && (FULLROW || (l >= 1 && l <= TZU && kr >= tz * TZU));
-  const long rowoff = (long)j * g.nzp + 2 * kp;
-  const int rp = r + 1 < TYR ? r + 1 : TYR - 1;
-  const double hx = g.hx, hy = g.hy, hz = g.hz;
-  const int nsteps = surplus ? 0 : (x0 + LX <= g.nx ? LX : g.nx - x0);
+  FG_TILE_FRAME(TYR, ZS, XWrap::slab, 0, g, nty, ntz, LX, blockIdx.x, gridDim.x, threadIdx.x);
   const double al = MODE == 1 ? (sc[i_num] / nvox + small) / (sc[i_den] / nvox + small) : 0.0;
-  auto plane = [&](int q) {
-    const int x = q < 0 ? q + g.xw_lo : (q >= g.nx ? q - g.xw_hi : q);
-    return (long)x * g.nyzp + rowoff;
-  };
   auto fetch = [&](int q, double2& A, double2& B, bool keep) {
     const long o = plane(q);
     A = ld2(a, o);
@@ -1792,7 +1379,7 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_sc_cgu_tile(Grid g
       Xb[img][1][r][li] = Bc;
       __syncthreads();
       const double2 Ayf = Xb[img][0][rp][li], Byf = Xb[img][1][rp][li];
-      double Azf = dpp_move<0x130>(Ac.x), Bzf = dpp_move<0x130>(Bc.x);
+      double Azf = lane_next(Ac.x), Bzf = lane_next(Bc.x);
       if (FULLROW && l == 63) {
         Azf = Xb[img][0][r][znext * 64].x;
         Bzf = Xb[img][1][r][znext * 64].x;
@@ -1821,70 +1408,30 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_sc_cgu_tile(Grid g
       if (st + 1 < nsteps) fetch(x0 + st + 2, An, Bn, st + 2 < nsteps);
     }
   }
-#pragma unroll
-  for (int c = 0; c < NS; ++c) {
-    double v = acc[c];
-    v += dpp_move<0x128>(v);
-    v += dpp_move<0x124>(v);
-    v += dpp_move<0x122>(v);
-    v += dpp_move<0x121>(v);
-    acc[c] = (read_lane(v, 0) + read_lane(v, 16)) + (read_lane(v, 32) + read_lane(v, 48));
-  }
-  if (l == 0) {
-#pragma unroll
-    for (int c = 0; c < NS; ++c) red[wv * NS + c] = acc[c];
-  }
-  __syncthreads();
-  if (threadIdx.x < NS) {
-    double v = 0.0;
-    for (int q = 0; q < TYR * NZS; ++q) v += red[q * NS + threadIdx.x];
-    partial[(long)blockIdx.x * NS + threadIdx.x] = v;
-  }
-}
-
-template <int TYR, int ZS>
-void launch_sc_cgu_tile_t(int mode, const Grid& g, const double* a, const double* b, const double* y, const double* w, double* ao,
-                          double* bo, const Vec6& E, const double* sc, int i_num, int i_den, double nvox, double small,
-                          double* partial, double* out7, hipStream_t s) {
-  constexpr int NZS = ZS ? ZS : 1;
-  constexpr int TYU = TYR - 2, TZU = ZS ? 64 * ZS : 62;
-  const int nzh = g.nz / 2;
-  const int nty = (g.ny + TYU - 1) / TYU, ntz = (nzh + TZU - 1) / TZU;
-  int LX = march_length(g.nx, (long)nty * ntz, 2 * device_cu_count());
-  if (LX > g.nx) LX = g.nx;
-  const int ntx = (g.nx + LX - 1) / LX;
-  int nb = nty * ntz * ntx;
-  if (nb >= 8) nb = ((nb + 7) / 8) * 8;
-  if (mode == 0)
-    hipLaunchKernelGGL((k_sc_cgu_tile<TYR, ZS, 0>), dim3(nb), dim3(TYR * NZS * 64), 0, s, g, a, b, y, w, ao, bo, E, sc, i_num, i_den, nvox,
-                       small, partial, nty, ntz, LX);
-  else
-    hipLaunchKernelGGL((k_sc_cgu_tile<TYR, ZS, 1>), dim3(nb), dim3(TYR * NZS * 64), 0, s, g, a, b, y, w, ao, bo, E, sc, i_num, i_den, nvox,
-                       small, partial, nty, ntz, LX);
-  FG_HIP_CHECK(hipGetLastError());
-  fold_sum(partial, nb, 7, out7, s);
-  FG_HIP_CHECK(hipGetLastError());
+  tile_reduce<NS, TYR * NZS>(acc, red, partial, NS, wv, l);
 }
 
 // the scalar modes' CG vector sweeps in the tiled form (grids of sc_sweep_tiled), see k_sc_cgu_tile
 void launch_sc_cgu_tile(int mode, const Grid& g, const double* a, const double* b, const double* y, const double* w, double* ao,
                         double* bo, const Vec6& E, const double* sc, int i_num, int i_den, double nvox, double small, double* partial,
                         double* out7, hipStream_t s) {
-  const int nzh = g.nz / 2;
-  if (nzh == 64) launch_sc_cgu_tile_t<8, 1>(mode, g, a, b, y, w, ao, bo, E, sc, i_num, i_den, nvox, small, partial, out7, s);
-  else if (nzh == 128) launch_sc_cgu_tile_t<6, 2>(mode, g, a, b, y, w, ao, bo, E, sc, i_num, i_den, nvox, small, partial, out7, s);
-  else launch_sc_cgu_tile_t<8, 0>(mode, g, a, b, y, w, ao, bo, E, sc, i_num, i_den, nvox, small, partial, out7, s);
+  auto args = [&](const TilePlan& p) {
+    return std::make_tuple(g, a, b, y, w, ao, bo, E, sc, i_num, i_den, nvox, small, partial, p.nty, p.ntz, p.LX);
+  };
+  tile_shape_dispatch(g.nz / 2, [&](auto R, auto Z) {
+    constexpr int TYR = decltype(R)::value, ZS = decltype(Z)::value;
+    const int cus = 2 * device_cu_count();
+    if (mode == 0) launch_tile<&k_sc_cgu_tile<TYR, ZS, 0>, TYR, ZS>(g, cus, MarchRule::balanced, 0, 7, partial, out7, s, args);
+    else launch_tile<&k_sc_cgu_tile<TYR, ZS, 1>, TYR, ZS>(g, cus, MarchRule::balanced, 0, 7, partial, out7, s, args);
+  });
 }
 
 // the tiled scalar sweep on the new search direction T_p = T_r + b T_p (b from the device sums), stored to p_new
 void launch_sc_sweep_cg(const Grid& g, double mu_0, const double* p_old, const double* r, double* p_new, const double* a, double* f,
                         const Vec6& E, const double* sc, int i_num, int i_den, double nvox, double small, double* partial,
                         double* sumsq6, hipStream_t s) {
-  ScCgDirection cg = {r, p_new, sc, i_num, i_den, nvox, small};
-  const int nzh = g.nz / 2;
-  if (nzh == 64) launch_sc_tile_t<8, 1>(g, mu_0, p_old, a, f, E, partial, sumsq6, s, nullptr, &cg);
-  else if (nzh == 128) launch_sc_tile_t<6, 2>(g, mu_0, p_old, a, f, E, partial, sumsq6, s, nullptr, &cg);
-  else launch_sc_tile_t<8, 0>(g, mu_0, p_old, a, f, E, partial, sumsq6, s, nullptr, &cg);
+  const ScCgDirection cg = {r, p_new, sc, i_num, i_den, nvox, small};
+  launch_sc_tile(g, mu_0, p_old, a, f, E, partial, sumsq6, s, nullptr, &cg);
 }
 
 bool sc_sweep_tiled(const Grid& g) {
@@ -1894,10 +1441,7 @@ bool sc_sweep_tiled(const Grid& g) {
 bool launch_sc_sweep_fast(const Grid& g, double mu_0, const double* T, const double* a, double* f, const Vec6& E,
                           double* partial, double* sumsq6, hipStream_t s, double* sumtau3) {
   if (sc_sweep_tiled(g)) {
-    const int nzh = g.nz / 2;
-    if (nzh == 64) launch_sc_tile_t<8, 1>(g, mu_0, T, a, f, E, partial, sumsq6, s, sumtau3);
-    else if (nzh == 128) launch_sc_tile_t<6, 2>(g, mu_0, T, a, f, E, partial, sumsq6, s, sumtau3);   // 48 KB of LDS images
-    else launch_sc_tile_t<8, 0>(g, mu_0, T, a, f, E, partial, sumsq6, s, sumtau3);
+    launch_sc_tile(g, mu_0, T, a, f, E, partial, sumsq6, s, sumtau3);
     return sumtau3 != nullptr;
   }
   const int nb = sweep_blocks((long)g.nx * g.ny * g.nzc);
@@ -1908,75 +1452,28 @@ bool launch_sc_sweep_fast(const Grid& g, double mu_0, const double* T, const dou
   return false;   // the untiled sweep carries no sums of tau
 }
 
-template <int TYR, int ZS, int NMOD = 2>
-void launch_eps_tile_t(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<6>& eps, const FieldPtrs<NMOD>& mod,
-                       const FieldPtrs<3>& f, double* partial, double* sum6, hipStream_t s) {
-  constexpr int NZS = ZS ? ZS : 1;
-  constexpr int TYU = TYR - 2, TZU = ZS ? 64 * ZS : 62;
-  const int nzh = g.nz / 2;
-  const int nty = (g.ny + TYU - 1) / TYU, ntz = (nzh + TZU - 1) / TZU;
-  const int cus = device_cu_count();
-  int LX = 32;
-  if ((long)nty * ntz * ((g.nx + 31) / 32) < cus) LX = 16;
-  if (LX > g.nx) LX = g.nx;
-  const int ntx = (g.nx + LX - 1) / LX;
-  int nb = nty * ntz * ntx;
-  if (nb >= 8) nb = ((nb + 7) / 8) * 8;
-  const size_t lds = 6 * TYR * NZS * 64 * sizeof(double2);
-  static PerDeviceOnce configured;
-  if (auto once = configured.first_use()) {
-    FG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_eps_tile<TYR, ZS, NMOD>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  const int nt = 3.0 * (double)g.n * sizeof(double) > 256.0 * 1024 * 1024 ? 1 : 0;
-  hipLaunchKernelGGL((k_eps_tile<TYR, ZS, NMOD>), dim3(nb), dim3(TYR * NZS * 64), lds, s, g, -2 * mu_0, -lambda_0, eps, mod, f,
-                     partial, nty, ntz, LX, nt);
-  FG_HIP_CHECK(hipGetLastError());
-  fold_sum(partial, nb, 6, sum6, s);
-  FG_HIP_CHECK(hipGetLastError());
+// (the strain sweep kept the fixed march lengths of round 1, see march_length_fixed)
+template <int NMOD>
+static void launch_eps_tile_n(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<6>& eps, const FieldPtrs<NMOD>& mod,
+                              const FieldPtrs<3>& f, double* partial, double* sum6, hipStream_t s) {
+  const int nt = tile_nt(g, 3, 256.0);
+  tile_shape_dispatch(g.nz / 2, [&](auto R, auto Z) {
+    constexpr int TYR = decltype(R)::value, ZS = decltype(Z)::value;
+    const size_t lds = 6 * TYR * TileShape<TYR, ZS>::RW * sizeof(double2);
+    launch_tile<&k_eps_tile<TYR, ZS, NMOD>, TYR, ZS>(g, device_cu_count(), MarchRule::fixed, lds, 6, partial, sum6, s, [&](const TilePlan& p) {
+      return std::make_tuple(g, -2 * mu_0, -lambda_0, eps, mod, f, partial, p.nty, p.ntz, p.LX, nt);
+    });
+  });
 }
 
 void launch_eps_tile(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<6>& eps, const FieldPtrs<2>& mod,
                      const FieldPtrs<3>& f, double* partial, double* sum6, hipStream_t s) {
-  const int nzh = g.nz / 2;
-  if (nzh == 64) launch_eps_tile_t<8, 1>(g, mu_0, lambda_0, eps, mod, f, partial, sum6, s);
-  else if (nzh == 128) launch_eps_tile_t<6, 2>(g, mu_0, lambda_0, eps, mod, f, partial, sum6, s);
-  else launch_eps_tile_t<8, 0>(g, mu_0, lambda_0, eps, mod, f, partial, sum6, s);
+  launch_eps_tile_n<2>(g, mu_0, lambda_0, eps, mod, f, partial, sum6, s);
 }
 
 void launch_eps_tile(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<6>& eps, const FieldPtrs<5>& mod,
                      const FieldPtrs<3>& f, double* partial, double* sum6, hipStream_t s) {
-  const int nzh = g.nz / 2;
-  if (nzh == 64) launch_eps_tile_t<8, 1, 5>(g, mu_0, lambda_0, eps, mod, f, partial, sum6, s);
-  else if (nzh == 128) launch_eps_tile_t<6, 2, 5>(g, mu_0, lambda_0, eps, mod, f, partial, sum6, s);
-  else launch_eps_tile_t<8, 0, 5>(g, mu_0, lambda_0, eps, mod, f, partial, sum6, s);
-}
-
-template <int TYR, int ZS, int MODE>
-void launch_cgu_tile_t(const Grid& g, const FieldPtrs<3>& a, const FieldPtrs<3>& b, const FieldPtrs<3>& y, const FieldPtrs<3>& w,
-                       const FieldPtrs<3>& ao, const FieldPtrs<3>& bo, const Vec6& E, const double* sc, int i_num, int i_den,
-                       double nvox, double small, double* partial, double* out7, hipStream_t s) {
-  constexpr int NZS = ZS ? ZS : 1;
-  constexpr int TYU = TYR - 2, TZU = ZS ? 64 * ZS : 62;
-  const int nzh = g.nz / 2;
-  const int nty = (g.ny + TYU - 1) / TYU, ntz = (nzh + TZU - 1) / TZU;
-  int LX = march_length(g.nx, (long)nty * ntz, device_cu_count());
-  if (LX > g.nx) LX = g.nx;
-  const int ntx = (g.nx + LX - 1) / LX;
-  int nb = nty * ntz * ntx;
-  if (nb >= 8) nb = ((nb + 7) / 8) * 8;
-  const size_t lds = 6 * TYR * NZS * 64 * sizeof(double2);
-  static PerDeviceOnce configured;
-  if (auto once = configured.first_use()) {
-    FG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cgu_tile<TYR, ZS, MODE>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  const int nt = (MODE == 1 && 3.0 * (double)g.n * sizeof(double) > 256.0 * 1024 * 1024) ? 1 : 0;
-  hipLaunchKernelGGL((k_cgu_tile<TYR, ZS, MODE>), dim3(nb), dim3(TYR * NZS * 64), lds, s, g, a, b, y, w, ao, bo, E, sc, i_num, i_den,
-                     nvox, small, partial, nty, ntz, LX, nt);
-  FG_HIP_CHECK(hipGetLastError());
-  fold_sum(partial, nb, 7, out7, s);
-  FG_HIP_CHECK(hipGetLastError());
+  launch_eps_tile_n<5>(g, mu_0, lambda_0, eps, mod, f, partial, sum6, s);
 }
 
 // mode 0: out7[0] = a : (a - b) in the gradient inner product (y, w, ao, bo, sc unused); mode 1: the update
@@ -1984,16 +1481,17 @@ void launch_cgu_tile_t(const Grid& g, const FieldPtrs<3>& a, const FieldPtrs<3>&
 void launch_cgu_tile(int mode, const Grid& g, const FieldPtrs<3>& a, const FieldPtrs<3>& b, const FieldPtrs<3>& y,
                      const FieldPtrs<3>& w, const FieldPtrs<3>& ao, const FieldPtrs<3>& bo, const Vec6& E, const double* sc,
                      int i_num, int i_den, double nvox, double small, double* partial, double* out7, hipStream_t s) {
-  const int nzh = g.nz / 2;
-#define FG_CGT(R, Z)                                                                                                          \
-  do {                                                                                                                        \
-    if (mode == 0) launch_cgu_tile_t<R, Z, 0>(g, a, b, y, w, ao, bo, E, sc, i_num, i_den, nvox, small, partial, out7, s);       \
-    else launch_cgu_tile_t<R, Z, 1>(g, a, b, y, w, ao, bo, E, sc, i_num, i_den, nvox, small, partial, out7, s);                 \
-  } while (0)
-  if (nzh == 64) FG_CGT(8, 1);
-  else if (nzh == 128) FG_CGT(6, 2);
-  else FG_CGT(8, 0);
-#undef FG_CGT
+  const int nt = mode == 1 ? tile_nt(g, 3, 256.0) : 0;   // mode 0 stores nothing
+  auto args = [&](const TilePlan& p) {
+    return std::make_tuple(g, a, b, y, w, ao, bo, E, sc, i_num, i_den, nvox, small, partial, p.nty, p.ntz, p.LX, nt);
+  };
+  tile_shape_dispatch(g.nz / 2, [&](auto R, auto Z) {
+    constexpr int TYR = decltype(R)::value, ZS = decltype(Z)::value;
+    const size_t lds = 6 * TYR * TileShape<TYR, ZS>::RW * sizeof(double2);
+    const int cus = device_cu_count();
+    if (mode == 0) launch_tile<&k_cgu_tile<TYR, ZS, 0>, TYR, ZS>(g, cus, MarchRule::balanced, lds, 7, partial, out7, s, args);
+    else launch_tile<&k_cgu_tile<TYR, ZS, 1>, TYR, ZS>(g, cus, MarchRule::balanced, lds, 7, partial, out7, s, args);
+  });
 }
 
 }  // namespace fg

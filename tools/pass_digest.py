@@ -3,6 +3,7 @@ maxiter = 5: every run makes the same five passes whatever it computes).  Two bu
 arithmetic on every path the list reaches: the check for a change that must leave every iterate bit-identical.
 
     python tools/pass_digest.py > profiles/pass_digest_<build>.txt
+    python tools/pass_digest.py tiles > profiles/pass_digest_tiles_<build>.txt     (a second list: the tiled marching sweeps)
 
 One line per run: grid, name, the digest of the residuals, the digest of the field and the iteration count -- or the solver's
 error text where a combination is refused (a refusal is part of the behaviour that is compared)."""
@@ -26,6 +27,7 @@ S_MIXED = np.array([0.1, 0, 0, 0, 0, 0.0])
 P3_MIXED = np.diag([0.0, 1.0, 1.0, 0.5, 0.5, 0.5])   # heat: flux component 1 prescribed
 E3_MIXED = np.array([0.0, -0.5, 0.25])
 S3_MIXED = np.array([0.2, 0.0, 0.0])
+COUNTERS = ()   # solver counters printed behind a line where they are non-zero (the tiles list: the anisotropic tile kernels)
 
 
 def geometry(grid):
@@ -78,7 +80,8 @@ def report(name, grid, E=E6, mixed=False, **kw):
             s.set_bc_projector(P_MIXED)
             E = E3_MIXED if len(E) == 3 else E_MIXED
         s.run(E, (S3_MIXED if len(E) == 3 else S_MIXED) if mixed else None)
-        print("%s: %s %s %d" % (tag, digest(s.residuals), digest(s.get_field("epsilon")), s.iterations))
+        reached = "".join(" %s=%d" % (c, s.counter(c)) for c in COUNTERS if s.counter(c) > 0)
+        print("%s: %s %s %d%s" % (tag, digest(s.residuals), digest(s.get_field("epsilon")), s.iterations, reached))
         s.close()
     except Exception as exc:   # noqa: BLE001
         print("%s: ERROR %s" % (tag, str(exc).splitlines()[0] if str(exc) else type(exc).__name__))
@@ -182,5 +185,32 @@ def main():
             report(name, grid, **o)
 
 
+def tiles():
+    """the tiled marching sweeps (grids with nz/2 >= 40, ny >= 14, nx >= 4), which the list above does not reach: every one of
+    the six kernels on the three tile shapes -- general tiles of 62 pairs, one wave per row, two waves per row"""
+    global COUNTERS
+    COUNTERS = ("u_tile_aniso", "sc_tile_aniso")
+    for grid in ((4, 16, 80), (6, 14, 128), (4, 14, 256)):
+        report("default", grid)                                   # k_u_tile PHI2
+        report("laminate", grid, **LAM)
+        report("mixed bc", grid, mixed=True)                      # SUMT
+        report("phi_sweep=0", grid, phi_sweep=0)                  # the precomputed moduli instead of PHI2
+        for ul in (0, 2):                                         # NMOD = 5; u_loop 0: k_eps_tile
+            report("full_staggered u_loop=%d" % ul, grid, gamma_scheme="full_staggered", fine=True, u_loop=ul)
+        report("viscosity", grid, **VISC)                         # k_eps_tile, NMOD = 2
+        report("general", grid, general=True)                     # ANISO (4x14x256: the general tiles)
+        report("general mixed bc", grid, mixed=True, general=True)
+        for cf in (0, 1):                                         # CGP, k_cgu_tile modes 0 and 1
+            report("cg cg_fused=%d" % cf, grid, method="cg", cg_fused=cf)
+            report("cg general cg_fused=%d" % cf, grid, method="cg", cg_fused=cf, general=True)
+        report("cg full_staggered", grid, method="cg", gamma_scheme="full_staggered", fine=True)
+        # k_sc_tile (plain, SUMT, CGP), k_sc_tile_aniso, k_sc_cgu_tile.  (aniso=1 with mixed bc does not reach k_sc_tile_aniso
+        # -- that kernel has no sums of tau and the solver takes another sweep: those lines show no sc_tile_aniso counter)
+        for an in (0, 1):
+            report("heat aniso=%d" % an, grid, aniso=an, **HEAT)
+            report("heat aniso=%d mixed bc" % an, grid, mixed=True, aniso=an, **HEAT)
+            report("heat aniso=%d cg" % an, grid, aniso=an, method="cg", **HEAT)
+
+
 if __name__ == "__main__":
-    main()
+    tiles() if sys.argv[1:] == ["tiles"] else main()
