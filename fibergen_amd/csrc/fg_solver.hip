@@ -673,8 +673,9 @@ long Solver::counter(const std::string& name) const {
     if (axis >= 0 && name == std::string("fft_path_") + c) return f->path(axis);
     if (axis >= 0 && name == std::string("fft_bluestein_m_") + c) return f->bluestein_m(axis);
   }
-  if (name == "interface_voxels") return (long)mixed_n_;
-  if (name == "affected_voxels") return (long)aff_n_;
+  // lists held from an earlier geometry (mixed_dirty_) are not this geometry's: they are rebuilt before a pass uses them
+  if (name == "interface_voxels") return mixed_dirty_ ? 0 : (long)mixed_n_;
+  if (name == "affected_voxels") return mixed_dirty_ ? 0 : (long)aff_n_;
   if (name == "phase_uploads") return phase_uploads_;
   if (name == "u_tile_aniso") return u_tile_aniso_;
   if (name == "sc_tile_aniso") return sc_tile_aniso_;

@@ -69,3 +69,43 @@ void emu_polar2_batch(long n, const double* in, double* out) {
 }
 
 }  // extern "C"
+
+// emu_polarn_*: the NPH = 4 .. 7 instantiations (launch_polarize has one kernel per phase count) on nph phases:
+// in[40 nph + 7] = law[nph], mu[nph], lambda[nph], C[nph][36], phi[nph], F[6], mu_0; out[13] as emu_polar2_case.
+template <int NPH>
+static void polarn_case(const double* in, double* out) {
+  PhaseTable pt;
+  pt.n = NPH;
+  for (int p = 0; p < kMaxPhases; ++p) {
+    pt.law[p] = kLawIso;
+    pt.mu[p] = pt.lambda[p] = 0.0;
+    for (int k = 0; k < 36; ++k) pt.C[p][k] = 0.0;
+  }
+  double phi[NPH];
+  for (int p = 0; p < NPH; ++p) {
+    pt.law[p] = in[p] != 0.0 ? kLawGeneral : kLawIso;
+    pt.mu[p] = in[NPH + p];
+    pt.lambda[p] = in[2 * NPH + p];
+    for (int k = 0; k < 36; ++k) pt.C[p][k] = in[3 * NPH + 36 * p + k];
+    phi[p] = in[39 * NPH + p];
+  }
+  const double* F = in + 40 * NPH;
+  const double mu_0 = in[40 * NPH + 6];
+  const bool generic = polarize_voxel<NPH>(F, phi, pt, mu_0, false, out);
+  polarize_voxel<NPH>(F, phi, pt, mu_0, true, out + 6);
+  out[12] = generic ? 1.0 : 0.0;
+}
+
+extern "C" int emu_polarn_batch(int nph, long n, const double* in, double* out) {
+  const long stride = 40 * nph + 7;
+  for (long i = 0; i < n; ++i) {
+    switch (nph) {
+      case 4: polarn_case<4>(in + stride * i, out + 13 * i); break;
+      case 5: polarn_case<5>(in + stride * i, out + 13 * i); break;
+      case 6: polarn_case<6>(in + stride * i, out + 13 * i); break;
+      case 7: polarn_case<7>(in + stride * i, out + 13 * i); break;
+      default: return 1;
+    }
+  }
+  return 0;
+}

@@ -56,11 +56,16 @@ def pack(cases):
 
 
 @pytest.fixture(scope="module")
-def results(tmp_path_factory):
-    cases = make_cases()
+def emu_lib(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("emu") / "emu_polar.so")
     subprocess.check_call(["g++"] + emulation_build_flags() + ["-o", out, SRC])
-    lib = ctypes.CDLL(out)
+    return ctypes.CDLL(out)
+
+
+@pytest.fixture(scope="module")
+def results(emu_lib):
+    cases = make_cases()
+    lib = emu_lib
     dp = ctypes.POINTER(ctypes.c_double)
     lib.emu_polar_batch.restype = None
     lib.emu_polar_batch.argtypes = [ctypes.c_long, dp, dp]
@@ -89,6 +94,67 @@ def two_phase_cases(cases):
             phi2 = np.array([0.0, 1.0, 0.0])
         out.append((np.roll(law, -1), np.roll(mu, -1), np.roll(lam, -1), np.roll(C, -1, axis=0), phi2, F, mu_0))
     return out
+
+
+def n_phase_cases(cases, nph):
+    """the same draws as nph-phase voxels: record i gives phases 0 .. 2, the records after it the rest (laws, moduli,
+    stiffnesses and fractions in that order); the fractions are scaled to sum 1.  Every eighth voxel is pure in its last
+    phase (the dispatch walks past nph - 1 zeros), the next has a fraction below the threshold there and phase 0 at zero,
+    the next is pure in its last isotropic phase (the closed form)"""
+    out = []
+    for i, (law, mu, lam, C, phi, F, mu_0) in enumerate(cases):
+        take = [cases[(i + j) % len(cases)] for j in range((nph + 2) // 3)]
+        cat = lambda k: np.concatenate([t[k] for t in take])[:nph]   # noqa: E731
+        phin = cat(4) / cat(4).sum() if cat(4).sum() > 0 else np.eye(nph)[0]
+        pure = np.eye(nph)
+        if i % 8 == 0:
+            phin = pure[nph - 1]
+        elif i % 8 == 1:
+            phin = np.concatenate([[0.0], phin[1:nph - 1], [1e-15]])
+            phin[1] += 1.0 - phin.sum()
+        elif i % 8 == 2:
+            phin = pure[max(p for p in range(nph) if cat(0)[p] == 0)]
+        out.append((cat(0), cat(1), cat(2), cat(3), phin, F, mu_0))
+    return out
+
+
+@pytest.mark.parametrize("nph", [4, 5, 6, 7])
+def test_four_to_seven_phase_instantiations(results, emu_lib, nph):
+    """polarize_voxel<NPH> for NPH = 4 .. 7 (one kernel per phase count in launch_polarize; 2 and kMaxPhases are held above):
+    the unrolled phase loops on nph-phase voxels, same bounds as the two-phase instantiation"""
+    cases, lib = results[0], emu_lib
+    many = n_phase_cases(cases, nph)
+    data = np.ascontiguousarray(np.concatenate([np.concatenate([law, mu, lam, C.ravel(), phi, F, [mu_0]])
+                                                for law, mu, lam, C, phi, F, mu_0 in many]))
+    assert data.size == len(many) * (40 * nph + 7)
+    res = np.zeros((len(many), 13))
+    dp = ctypes.POINTER(ctypes.c_double)
+    lib.emu_polarn_batch.restype = ctypes.c_int
+    lib.emu_polarn_batch.argtypes = [ctypes.c_int, ctypes.c_long, dp, dp]
+    assert lib.emu_polarn_batch(nph, len(many), data.ctypes.data_as(dp), res.ctypes.data_as(dp)) == 0
+    check_instantiation(many, res, nph)
+
+
+def check_instantiation(cases, res, nph):
+    """polarize_voxel<NPH> on nph-phase records against the restatement: the branch taken, then the strain and the polarisation
+    at 64 eps cond(A) (6 x 6 solve) or 4 eps (closed form), as the module docstring derives"""
+    ngeneric = 0
+    for k, (law, mu, lam, C, phi, F, mu_0) in enumerate(cases):
+        mats = [C[p] if law[p] else (mu[p], lam[p]) for p in range(nph)]
+        phis = [np.full((1, 1, 1), phi[p]) for p in range(nph)]
+        Fv = F.reshape(6, 1, 1, 1)
+        M = pr.tangent_full(phis, mats)[0, 0, 0]
+        generic = bool(pr.generic_mask(phis, mats)[0, 0, 0])
+        assert res[k, 12] == float(generic), (k, phi)
+        ngeneric += generic
+        Q = pr.calc_polarization(Fv, phis, mats, mu_0).ravel()
+        R = pr.calc_polarization(Fv, phis, mats, mu_0, inv=True).ravel()
+        bound = 64 * EPS * np.linalg.cond(M + 2 * mu_0 * np.eye(6)) if generic else 4 * EPS
+        sR = np.abs(R).max()
+        sQ = (np.abs(M).sum(axis=1).max() + 2 * mu_0) * sR if generic else np.abs(Q).max()
+        assert np.abs(res[k, 6:12] - R).max() <= bound * sR, (k, "inv")
+        assert np.abs(res[k, :6] - Q).max() <= bound * sQ, (k, "forward")
+    assert 0 < ngeneric < len(cases)
 
 
 def restate(case):
@@ -141,21 +207,4 @@ def test_inverse_undoes_forward(results):
 def test_two_phase_instantiation(results):
     """polarize_voxel<2>, the instantiation of every two-phase run: same bounds as above"""
     two, res2 = results[2]
-    ngeneric = 0
-    for k, case in enumerate(two):
-        law, mu, lam, C, phi, F, mu_0 = case
-        mats = [C[p] if law[p] else (mu[p], lam[p]) for p in range(2)]
-        phis = [np.full((1, 1, 1), phi[p]) for p in range(2)]
-        Fv = F.reshape(6, 1, 1, 1)
-        M = pr.tangent_full(phis, mats)[0, 0, 0]
-        generic = bool(pr.generic_mask(phis, mats)[0, 0, 0])
-        assert res2[k, 12] == float(generic), (k, phi)
-        ngeneric += generic
-        Q = pr.calc_polarization(Fv, phis, mats, mu_0).ravel()
-        R = pr.calc_polarization(Fv, phis, mats, mu_0, inv=True).ravel()
-        bound = 64 * EPS * np.linalg.cond(M + 2 * mu_0 * np.eye(6)) if generic else 4 * EPS
-        sR = np.abs(R).max()
-        sQ = (np.abs(M).sum(axis=1).max() + 2 * mu_0) * sR if generic else np.abs(Q).max()
-        assert np.abs(res2[k, 6:12] - R).max() <= bound * sR, (k, "inv")
-        assert np.abs(res2[k, :6] - Q).max() <= bound * sQ, (k, "forward")
-    assert 0 < ngeneric < len(two)
+    check_instantiation(two, res2, 2)
