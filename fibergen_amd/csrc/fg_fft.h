@@ -9,10 +9,13 @@
 #include <hip/hip_runtime.h>
 
 #include "fg_common.h"
-#include "fg_fft_bluestein.h"
-#include "fg_fft_smooth.h"
+#include "fg_fft_route.h"
 
 namespace fg {
+
+namespace fft {
+struct StridedArgs;   // fg_fft_kernels.h
+}
 
 // Green-operator inputs of the fused pass: separable k tables (kpm[a], kp[a]; for the axis that is
 // transformed the table index is the frequency, tables 1 and 2 are indexed by ky / kz) and c10, c20.
@@ -49,7 +52,7 @@ class Fft3 {
   void c2c_y(double* data, int ncomp, long comp_stride, int dir, double scale, const PlaneWindow* w = nullptr);
   void c2c_x(double* data, int ncomp, long comp_stride, int dir, double scale);
   void c2r_z(double* data, int ncomp, long comp_stride, const PlaneWindow* w = nullptr);
-  bool can_window() const { return fast_[1] && fast_[2]; }   // the passes that take a PlaneWindow
+  bool can_window() const { return pow2(1) && pow2(2); }   // the passes that take a PlaneWindow
   void scale(double* data, int ncomp, long comp_stride, double scale);
   // Slab decomposition (x-slab side): the y pass with the all-to-all layout on one side.  Plain layout
   // [nx][ny][nzc]; blocked layout [q][nx][ny/P][nzc] (block q = what peer q receives / sent), see StridedArgs.
@@ -80,45 +83,52 @@ class Fft3 {
 
   // exchange planes in LDS of the power-of-two y, x and (mirrored) z passes: 2 = real and imaginary plane side by side, 1 = one
   // plane that the two parts cross in turn (half the LDS per workgroup, two more barriers per exchange), -1 = the measured
-  // default per pass and length (images_for).  Bit-identical results.  Per Fft3, not per process; other lengths: no effect.
+  // default (images_for).  Bit-identical results.  Per Fft3, not per process; other lengths: no effect.
   void set_images(int images) { images_ = images; }
-  int images_for(int axis, int n) const;
+  int images_for() const { return images_ == 1 ? 1 : 2; }
 
   // lengths with a prime factor above 13, from fft::kBluesteinMin points on: Bluestein's algorithm on the tile kernels
   // (fg_fft_bluestein.h; default) or the O(n^2) sums every such length took before.  Per Fft3, not per process.
   void set_bluestein(bool on) { bluestein_ = on; }
   // how an axis is transformed: 0 length 1, 1 power of two, 2 sub-lines p * 2^k, 3 tile kernels, 4 Bluestein, 5 O(n^2)
-  int path(int axis) const;
-  int bluestein_m(int axis) const { return path(axis) == 4 ? blue_[axis].m() : 0; }   // the padded length, 0: not on Bluestein
+  // (the six-way summary of the route's family, fg_fft_route.h)
+  int path(int axis) const { return fft::path_of(route_[axis].resolved(bluestein_)); }
+  int bluestein_m(int axis) const { return path(axis) == 4 ? route_[axis].blue.m() : 0; }   // the padded length, 0: not on Bluestein
+  const fft::AxisRoute& route(int axis) const { return route_[axis]; }
 
-  bool fast_x() const { return fast_[0]; }
-  bool fast_y() const { return fast_[1]; }
-  bool fast_z() const { return fast_[2]; }
+  bool fast_x() const { return pow2(0); }
+  bool fast_y() const { return pow2(1); }
+  bool fast_z() const { return pow2(2); }
   const cplx* x_twiddles() const { return tw_[0]; }
   const cplx* z_twiddles() const { return tw_[2]; }  // pass twiddles of M = nz/2 (fast z path)
   const cplx* z_roots() const { return wz_; }        // e^{-2 pi i k/nz}, k = 0..nz/2
 
  private:
   void strided(double* data, int ncomp, long comp_stride, int axis, int dir, double scale, const PlaneWindow* w = nullptr);
+  void strided_sublines(const fft::StridedArgs& a, int nouter, int ncomp, long comp_stride, int axis, int dir);
+  void z_pass(double* data, int ncomp, long comp_stride, bool fwd, const PlaneWindow* w);
+  void z_sublines(double* data, long nrows, int ncomp, long comp_stride, bool fwd);
+  // a pass over lines `axis` of the whole field, in place: geometry, pass twiddles, exchange planes (axis 2: the p sub-rows of
+  // the packed z rows as columns)
+  fft::StridedArgs strided_args(double* data, int axis, double scale, int nt) const;
+  fft::BluesteinTables blue_tables(int axis) const { return {blue_tab_[axis][0], blue_tab_[axis][1], blue_tab_[axis][2]}; }
+  bool pow2(int axis) const { return route_[axis].family == fft::Family::Pow2; }
+  int nt_stream() const { return stream_stores_ ? 3 : 0; }   // bit 0 stores, bit 1 loads
+  void route_fused();
   Grid g_;
   hipStream_t stream_;
-  bool fast_[3];
-  int odd_[3];       // odd p <= 25: the axis length (z: nz/2) is that factor times a fast power of two; 0 otherwise
-  fft::SmoothPlan smooth_[3];   // n != 0: the axis (z: nz/2, odd nz: nz) runs the Stockham tile kernels of fg_fft_smooth.h
-  bool zodd_ = false;           // odd nz with a plan: the rows are transformed as nz complex points
-  fft::SmoothPlan xfused_plan_[2];   // fused x pass of the tile kernels: [0] one component, [1] three (n = 0: none)
+  fft::AxisRoute route_[3];        // the family of each axis with its plan, chosen once (fg_fft_route.h)
+  fft::FusedXRoute fused_[2][2];   // fused pass along x / y (a y-slab's x lines): [axis][0] one component, [axis][1] three
   bool joint_x_ = true;
   int images_ = -1;
-  bool blue_on(int axis) const { return bluestein_ && blue_[axis].n != 0; }
-  fft::BluesteinPlan blue_[3];   // n != 0: the axis has neither of the faster passes and a Bluestein plan (z: of nz / 2, odd nz: of nz)
-  cplx* blue_tab_[3][3];         // per axis: chirp c[k], k < n; filter B^[p], p < M; roots of M
+  cplx* blue_tab_[3][3] = {};      // per axis: chirp c[k], k < n; filter B^[p], p < M; roots of M
   bool bluestein_ = true;
-  int stream_stores_ = 0;  // FFT passes use cache-bypassing stores (fields larger than the Infinity Cache)
-  cplx* tw_[3];      // per-axis pass twiddles (fast path) ; z: for M = nz/2
-  cplx* half_root_[2];  // e^{-i pi j/n}, j < n/8, of x and y (fused Green-operator pass)
-  cplx* wz_;         // w^k = e^{-2 pi i k/nz}, k = 0..nz/2   (fast z path)
-  cplx* wgen_[3];    // e^{-2 pi i k/n}, k = 0..n-1           (generic path)
-  double* scratch_;  // one padded component (generic path)
+  int stream_stores_ = 0;  // FFT passes use cache-bypassing accesses (fields larger than the Infinity Cache)
+  cplx* tw_[3] = {};       // per-axis pass twiddles (power of two: of the line; sub-lines: of m)
+  cplx* half_root_[2] = {};  // e^{-i pi j/n}, j < n/8, of x and y (fused Green-operator pass)
+  cplx* wz_ = nullptr;     // w^k = e^{-2 pi i k/nz}, k = 0..nz/2   (power-of-two z pass)
+  cplx* wgen_[3] = {};     // e^{-2 pi i k/n}, k = 0..n-1           (every other family)
+  double* scratch_ = nullptr;  // one padded component (scratch combine, O(n^2) sums)
 };
 
 }  // namespace fg

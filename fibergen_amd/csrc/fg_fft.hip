@@ -5,17 +5,17 @@
 //   y : lines nzc complex apart, tiles of C adjacent kz columns (C*16 B contiguous segments)
 //   x : lines ny*nzc apart, tiles of C adjacent (ky,kz) columns
 // Butterflies live in registers (8 points/thread), exchanges go through padded LDS.
-// Axes that are not a power of two in [8,1024] use O(n^2) DFT kernels via a scratch
-// component (correctness path for the odd grids of the reference's self tests).
+// Which kernels run an axis -- power of two, p * 2^k sub-lines, tile plans, Bluestein, O(n^2) sums through a scratch
+// component -- is the route of fg_fft_route.h, chosen once per axis; every entry point below is a switch on its family.
 #include "fg_fft.h"
 
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 #include "fg_fft_kernels.h"
 #include "fg_fft_plane.h"
-#include "fg_fft_smooth.h"
 #include "fg_fft_bluestein_dev.h"
 #include "fg_fft_smooth_dev.h"
 #include "fg_fft_tables.h"
@@ -183,11 +183,28 @@ __global__ void k_scale(double* x, long n, double s) {
 // lengths with factors 2, 3, 5, 7, 11, 13: the Stockham tile kernels live in fg_fft_smooth_yz.hip / fg_fft_smooth_x.hip
 // (translation units of their own: their many instances compile beside this file)
 
-int nt_loads_env() {
-  return 15;   // streaming loads in r2c, the strided passes, the fused x pass and the mirrored c2r (bits 1, 2, 4, 8)
+// The one-kernel sub-line launchers are reached through a route that promised them (fg_fft_route.h): they test the route's own
+// predicate, and what it excludes is an error, never a silent fall-through to another family.
+[[noreturn]] void no_launcher(const char* what) {
+  throw std::runtime_error(std::string("fft: the route names a sub-line kernel that is not built: ") + what);
 }
 
-bool fast_len(int n) { return is_pow2(n) && n >= 8 && n <= 1024; }
+// f(std::integral_constant<int, P>) for the entry of Ps that equals p; a last entry 0 (the kernels with a run-time p) takes
+// every other p.  Each call site names the P its kernels are built for: the unrolled and the run-time forms need not round alike.
+template <int... Ps, class F>
+void dispatch_p(int p, F&& f) {
+  if (!((p == Ps || Ps == 0 ? (f(std::integral_constant<int, Ps>{}), true) : false) || ...)) no_launcher("p");
+}
+// f(std::integral_constant<int, M>) for the sub-line lengths the one-kernel passes are built for (fft::sub_one_m)
+template <class F>
+void dispatch_sub_m(int m, F&& f) {
+  switch (m) {
+#define FG_CASE(M) case M: return f(std::integral_constant<int, M>{});
+    FG_CASE(8) FG_CASE(16) FG_CASE(32) FG_CASE(64) FG_CASE(128) FG_CASE(256)
+#undef FG_CASE
+    default: no_launcher("sub-line length");
+  }
+}
 
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wpass-failed"   // the run-time-p instances keep their loops rolled
@@ -197,15 +214,7 @@ bool fast_len(int n) { return is_pow2(n) && n >= 8 && n <= 1024; }
 // sweep forms  X[k + M s] = sum_r w_N^{r k} w_p^{r s} Y_r[k]  (out of place, through the scratch component).
 // Inverse: the combine sweep first,  Z_r[k] = conj(w_N^{r k}) sum_s X[k + M s] conj(w_p^{r s})  to point p k + r,
 // then the M-point inverse kernels on the sub-lines.  3x the traffic of a native pass instead of an O(N^2) DFT.
-constexpr int kMaxOddFactor = 25;   // 25: the decimal sizes 200, 400, 800
-
-int mixed_factor(int n) {   // p if n = p * 2^k with 2^k a fast length, else 0
-  for (int p = 3; p <= kMaxOddFactor; p += 2)
-    if (n % p == 0 && fast_len(n / p)) return p;
-  return 0;
-}
-
-
+// (p <= fft::kMaxOddFactor; which lengths take this family: fg_fft_route.h)
 
 // w: e^{-2 pi i j / N}, j < N
 template <int DIR, int P>   // P = 0: run-time p (indexed local arrays); 3, 5, 7: unrolled, everything in registers
@@ -403,11 +412,10 @@ __global__ __launch_bounds__(M * P) void k_strided_mixed(StridedArgs a, long com
 }
 
 template <int M, int P>
-bool launch_strided_mixed(const StridedArgs& a0, int nouter, int dir, int ncomp, long cs, const cplx* wN, hipStream_t s) {
-  constexpr int PN = M + M / 8;
-  constexpr size_t lds = 2 * PN * P * 8 * sizeof(double);
-  if constexpr (M * P > 1024 || lds > 144 * 1024) {
-    return false;
+void launch_strided_mixed(const StridedArgs& a0, int nouter, int dir, int ncomp, long cs, const cplx* wN, hipStream_t s) {
+  constexpr size_t lds = sub_tile_lds(M, P);
+  if constexpr (!sub_one_strided_fits(M, P)) {
+    no_launcher("y / x pass");
   } else {
     StridedArgs a = a0;
     a.tiles_per_outer = (a.ncols + 7) / 8;
@@ -422,7 +430,6 @@ bool launch_strided_mixed(const StridedArgs& a0, int nouter, int dir, int ncomp,
     if (dir < 0) hipLaunchKernelGGL((k_strided_mixed<M, P, -1>), grid, dim3(M * P), lds, s, a, cs, wN);
     else hipLaunchKernelGGL((k_strided_mixed<M, P, +1>), grid, dim3(M * P), lds, s, a, cs, wN);
     FG_HIP_CHECK(hipGetLastError());
-    return true;
   }
 }
 
@@ -518,15 +525,12 @@ __global__ __launch_bounds__((MP / 8) * P * LINES) void k_z_mixed(double* data, 
 }
 
 template <int MP, int P>
-bool launch_z_mixed(double* data, long nrows, int nzp, int ncomp, long comp_stride, bool fwd, const cplx* tw, const cplx* wn,
+void launch_z_mixed(double* data, long nrows, int nzp, int ncomp, long comp_stride, bool fwd, const cplx* tw, const cplx* wn,
                     hipStream_t s) {
-  constexpr int LINES = (2048 / (MP * P)) > 1 ? (2048 / (MP * P)) : 1;
-  constexpr int THREADS = (MP / 8) * P * LINES;
-  constexpr int PN = MP + MP / 8;
-  constexpr size_t ex = 2 * PN * P * LINES * sizeof(double), im = (size_t)LINES * P * MP * sizeof(cplx);
-  constexpr size_t lds = ex > im ? ex : im;
-  if constexpr (THREADS > 1024 || lds > 144 * 1024) {
-    return false;
+  constexpr int LINES = sub_z_lines(MP, P), THREADS = sub_z_threads(MP, P);
+  constexpr size_t lds = sub_z_lds(MP, P);
+  if constexpr (!sub_one_z_fits(MP, P)) {
+    no_launcher("z pass");
   } else {
     const dim3 grid((unsigned)((nrows + LINES - 1) / LINES), ncomp);
     static PerDeviceOnce configured;
@@ -539,21 +543,6 @@ bool launch_z_mixed(double* data, long nrows, int nzp, int ncomp, long comp_stri
     if (fwd) hipLaunchKernelGGL((k_z_mixed<MP, P, LINES, true>), grid, dim3(THREADS), lds, s, data, nrows, nzp, comp_stride, tw, wn);
     else hipLaunchKernelGGL((k_z_mixed<MP, P, LINES, false>), grid, dim3(THREADS), lds, s, data, nrows, nzp, comp_stride, tw, wn);
     FG_HIP_CHECK(hipGetLastError());
-    return true;
-  }
-}
-
-template <int P>
-bool z_mixed_p(int mp, double* data, long nrows, int nzp, int ncomp, long cs, bool fwd, const cplx* tw, const cplx* wn,
-               hipStream_t s) {
-  switch (mp) {
-    case 8: return launch_z_mixed<8, P>(data, nrows, nzp, ncomp, cs, fwd, tw, wn, s);
-    case 16: return launch_z_mixed<16, P>(data, nrows, nzp, ncomp, cs, fwd, tw, wn, s);
-    case 32: return launch_z_mixed<32, P>(data, nrows, nzp, ncomp, cs, fwd, tw, wn, s);
-    case 64: return launch_z_mixed<64, P>(data, nrows, nzp, ncomp, cs, fwd, tw, wn, s);
-    case 128: return launch_z_mixed<128, P>(data, nrows, nzp, ncomp, cs, fwd, tw, wn, s);
-    case 256: return launch_z_mixed<256, P>(data, nrows, nzp, ncomp, cs, fwd, tw, wn, s);
-    default: return false;
   }
 }
 
@@ -690,14 +679,11 @@ __global__ __launch_bounds__(M * P) void k_xfused_mixed(XFusedArgs a, const cplx
 }
 
 template <int M, int P>
-bool launch_xfused_mixed(XFusedArgs a, int nouter, const cplx* wN, hipStream_t s, bool probe_only) {
-  constexpr int PN = M + M / 8;
-  constexpr size_t lds = 2 * PN * P * 8 * sizeof(double);
-  // N <= 512 like the power-of-two fused pass: 640 and 768 need 0.9-1.3 KB of scratch per lane
-  if constexpr (M * P > 512 || lds > 144 * 1024) {
-    return false;
+void launch_xfused_mixed(XFusedArgs a, int nouter, const cplx* wN, hipStream_t s) {
+  constexpr size_t lds = sub_tile_lds(M, P);
+  if constexpr (!sub_one_fused_fits(M, P)) {   // (N <= 512: fg_fft_route.h)
+    no_launcher("fused pass");
   } else {
-    if (probe_only) return true;
     a.tiles_per_outer = (a.ncols + 7) / 8;
     static PerDeviceOnce configured;
     if (auto once = configured.first_use()) {
@@ -706,33 +692,6 @@ bool launch_xfused_mixed(XFusedArgs a, int nouter, const cplx* wN, hipStream_t s
     }
     hipLaunchKernelGGL((k_xfused_mixed<M, P>), dim3((unsigned)((long)a.tiles_per_outer * nouter)), dim3(M * P), lds, s, a, wN);
     FG_HIP_CHECK(hipGetLastError());
-    return true;
-  }
-}
-
-template <int P>
-bool xfused_mixed_p(int m, const XFusedArgs& a, int nouter, const cplx* wN, hipStream_t s, bool probe_only) {
-  switch (m) {
-    case 8: return launch_xfused_mixed<8, P>(a, nouter, wN, s, probe_only);
-    case 16: return launch_xfused_mixed<16, P>(a, nouter, wN, s, probe_only);
-    case 32: return launch_xfused_mixed<32, P>(a, nouter, wN, s, probe_only);
-    case 64: return launch_xfused_mixed<64, P>(a, nouter, wN, s, probe_only);
-    case 128: return launch_xfused_mixed<128, P>(a, nouter, wN, s, probe_only);
-    case 256: return launch_xfused_mixed<256, P>(a, nouter, wN, s, probe_only);
-    default: return false;
-  }
-}
-
-template <int P>
-bool strided_mixed_p(int m, const StridedArgs& a, int nouter, int dir, int ncomp, long cs, const cplx* wN, hipStream_t s) {
-  switch (m) {
-    case 8: return launch_strided_mixed<8, P>(a, nouter, dir, ncomp, cs, wN, s);
-    case 16: return launch_strided_mixed<16, P>(a, nouter, dir, ncomp, cs, wN, s);
-    case 32: return launch_strided_mixed<32, P>(a, nouter, dir, ncomp, cs, wN, s);
-    case 64: return launch_strided_mixed<64, P>(a, nouter, dir, ncomp, cs, wN, s);
-    case 128: return launch_strided_mixed<128, P>(a, nouter, dir, ncomp, cs, wN, s);
-    case 256: return launch_strided_mixed<256, P>(a, nouter, dir, ncomp, cs, wN, s);
-    default: return false;
   }
 }
 
@@ -829,6 +788,40 @@ __global__ __launch_bounds__(256) void k_mixed_c2r_start(double* data, long nrow
   }
 }
 #pragma clang diagnostic pop
+
+// the sweeps of the sub-lines + combine family on one component (P = 0: p at run time)
+template <int DIR, int P>
+void launch_combine_tile(cplx* d, long ls, long os, int ncols, int nouter, int m, int p, double scale, const cplx* w, hipStream_t s) {
+  static PerDeviceOnce configured;
+  if (auto once = configured.first_use()) {
+    FG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mixed_combine_tile<DIR, P>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  }
+  const int tiles = (ncols + 7) / 8;
+  hipLaunchKernelGGL((k_mixed_combine_tile<DIR, P>), dim3((unsigned)((long)tiles * nouter)), dim3(256),
+                     (size_t)p * m * 8 * sizeof(cplx), s, d, ls, os, ncols, tiles, m, p, scale, w);
+}
+template <int DIR, int P>
+void launch_combine_scratch(const cplx* src, cplx* dst, long ls, long os, int ncols, int nouter, int m, int p, double scale,
+                            const cplx* w, hipStream_t s) {
+  const unsigned nb = (unsigned)(((long)nouter * m * ncols + 255) / 256);
+  hipLaunchKernelGGL((k_mixed_combine<DIR, P>), dim3(nb), dim3(256), 0, s, src, dst, ls, os, ncols, nouter, m, p, scale, w);
+}
+// r2c finish (FWD) / c2r start of the z rows: `rows` rows per workgroup in 48 KB of LDS
+template <bool FWD, int P>
+void launch_z_sweep(double* data, long nrows, int nzp, int M, int p, const cplx* wn, hipStream_t s) {
+  constexpr auto kernel = FWD ? &k_mixed_r2c_finish<P> : &k_mixed_c2r_start<P>;
+  static PerDeviceOnce configured;
+  if (auto once = configured.first_use()) {
+    FG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  }
+  int rows = (int)(48 * 1024 / ((M + 1) * sizeof(cplx)));
+  if (rows < 1) rows = 1;
+  const size_t lds = (size_t)rows * (M + 1) * sizeof(cplx);
+  const dim3 grid((unsigned)((nrows + rows - 1) / rows));
+  if constexpr (FWD) hipLaunchKernelGGL(k_mixed_r2c_finish<P>, grid, dim3(256), lds, s, data, nrows, nzp, M, p, rows, wn);
+  else hipLaunchKernelGGL(k_mixed_c2r_start<P>, grid, dim3(256), lds, s, data, nrows, nzp, M, p, rows, wn);
+}
 
 cplx* upload(const std::vector<cplx>& v) {
   cplx* d = nullptr;
@@ -1018,102 +1011,59 @@ void strided_pow2(int n, const StridedArgs& a, int nouter, int dir, int ncomp, l
   }
 }
 
+// power-of-two z pass, K = R2CKernel / C2RKernel.  64 ... 512 packed points: the mirrored value of the real split / merge comes
+// from the lane that holds it (wave shuffle) instead of a round trip of the spectrum through LDS / a second global load --
+// r2c 512^3 1.30 -> 1.16 ms, 256^3 0.158 -> 0.155 ms; c2r 256^3 0.164 -> 0.151 ms, 512^3 1.38 -> 1.19 ms
+template <template <int, int, bool, int> class K>
+void z_pow2(int m, const ZArgs& a, int ncomp, long cs, hipStream_t s) {
+  switch (m) {
+#define FG_CASE(M) case M: return launch_z<K<M, ZLines<M>::value, false, 2>>(a, ncomp, cs, ZLines<M>::value, s);
+    FG_CASE(8) FG_CASE(16) FG_CASE(32) FG_CASE(1024)
+#undef FG_CASE
+#define FG_CASE(M)                                                                                              \
+  case M:                                                                                                       \
+    return a.images == 1 ? launch_z<K<M, ZLines<M>::value, true, 1>>(a, ncomp, cs, ZLines<M>::value, s)         \
+                         : launch_z<K<M, ZLines<M>::value, true, 2>>(a, ncomp, cs, ZLines<M>::value, s);
+    FG_CASE(64) FG_CASE(128) FG_CASE(256) FG_CASE(512)
+#undef FG_CASE
+    default: throw std::runtime_error("fft: unsupported fast z length");
+  }
+}
+
 }  // namespace
 
-Fft3::Fft3(const Grid& g, hipStream_t stream) : g_(g), stream_(stream), wz_(nullptr), scratch_(nullptr) {
+Fft3::Fft3(const Grid& g, hipStream_t stream) : g_(g), stream_(stream) {
   const int len[3] = {g.nx, g.ny, g.nz};
-  for (int a = 0; a < 3; ++a) {
-    tw_[a] = nullptr;
-    wgen_[a] = nullptr;
-    for (int k = 0; k < 3; ++k) blue_tab_[a][k] = nullptr;
-  }
-  half_root_[0] = half_root_[1] = nullptr;
-  fast_[0] = fast_len(g.nx);
-  fast_[1] = fast_len(g.ny);
-  fast_[2] = (g.nz % 2 == 0) && fast_len(g.nz / 2);
   bool need_scratch = false;
   for (int a = 0; a < 3; ++a) {
-    odd_[a] = 0;
-    if (fast_[a]) {
-      tw_[a] = upload(make_pass_twiddles(a == 2 ? len[a] / 2 : len[a]));
-      if (a < 2) half_root_[a] = upload(make_unit_roots(2 * len[a], len[a] / 8));
-    } else {
-      // p * 2^k: power-of-two kernels on the interleaved sub-lines + a combine sweep; anything else: O(n^2) DFT
-      const int m = a == 2 ? (len[a] % 2 == 0 ? len[a] / 2 : 0) : len[a];
-      if (a == 2 && len[a] % 2 == 1 && len[a] > 1) {   // odd nz: no packed-real trick, the rows as nz complex points
-        SmoothPlan so;
-        if (smooth_plan_z(len[a], &so)) smooth_[2] = so, zodd_ = true;
-      }
-      odd_[a] = m ? mixed_factor(m) : 0;
-      if (odd_[a]) tw_[a] = upload(make_pass_twiddles(m / odd_[a]));
-      // lengths with small prime factors that the one-kernel p * 2^k passes (p = 3, 5, 7, 9) do not cover -- 100, 120, 200, 300,
-      // 400, 500 ...: the Stockham tile kernels of fg_fft_smooth.h.  (Where a p * 2^k kernel exists it stays: measured in one job
-      // with the tile kernels forced on, 96^3 9 160 against 5 510 it/s, 192^3 2 030 / 1 270, 384^3 240 / 174, 448^3 123 / 91.)
-      SmoothPlan sp;
-      // ... and, since the tile kernels are built per plan (fg_fft_smooth_plans.h), from 100 points on (z: nz / 2 >= 72): sub-line
-      // kernels / tile kernels in one job 144^3 3 034 / 4 452 it/s, 160^3 3 119 / 3 647, 192^3 2 050 / 2 190, 224^3 965 / 1 237,
-      // 288^3 432 / 657, 320^3 409 / 481, 448^3 121 / 148; 96^3 9 281 / 9 295 (kept on the sub-line kernels)
-      const bool one_kernel_mixed = (odd_[a] == 3 || odd_[a] == 5 || odd_[a] == 7 || odd_[a] == 9) && m <= 1024 && m < (a == 2 ? 72 : 100);
-      if (m > 1 && !one_kernel_mixed && (a == 2 ? smooth_plan_z(m, &sp) : smooth_plan_strided(m, &sp))) smooth_[a] = sp;
-      wgen_[a] = upload(make_unit_roots(len[a], len[a]));
-      need_scratch = true;
-      // what is left -- a prime factor above 13 -- from kBluesteinMin points on: Bluestein on the tile kernels of a padded length
-      if (!smooth_[a].n && !odd_[a]) {
-        const int line = a == 2 ? (len[a] % 2 ? len[a] : len[a] / 2) : len[a];
-        BluesteinPlan bp;
-        if (a == 2 ? bluestein_plan_z(line, &bp) : bluestein_plan_strided(line, &bp)) {
-          blue_[a] = bp;
-          blue_tab_[a][0] = upload(make_bluestein_chirp(line));
-          blue_tab_[a][1] = upload(make_bluestein_filter(line, bp.m()));
-          blue_tab_[a][2] = upload(make_unit_roots(bp.m(), bp.m()));
-        }
-      }
+    const AxisRoute& r = route_[a] = route_axis(a, len[a]);
+    if (r.pass_twiddles) tw_[a] = upload(make_pass_twiddles(r.pass_twiddles));
+    if (r.half_roots) half_root_[a] = upload(make_unit_roots(2 * len[a], len[a] / 8));
+    if (r.z_roots) wz_ = upload(make_unit_roots(g.nz, g.nz / 2 + 1));
+    if (r.unit_roots) wgen_[a] = upload(make_unit_roots(len[a], len[a]));
+    if (r.blue.n) {
+      blue_tab_[a][0] = upload(make_bluestein_chirp(r.line));
+      blue_tab_[a][1] = upload(make_bluestein_filter(r.line, r.blue.m()));
+      blue_tab_[a][2] = upload(make_unit_roots(r.blue.m(), r.blue.m()));
     }
+    need_scratch |= r.scratch;
   }
-  if (smooth_[0].n) {   // plans of the tile kernels' fused x pass (one / three components)
-    smooth_plan_xfused(g.nx, 1, &xfused_plan_[0]);
-    smooth_plan_xfused(g.nx, 3, &xfused_plan_[1]);
-    // an x length whose three components have no joint image plan (384 = 3 * 2^7: 9 216 points of a tile against 512 threads x 20
-    // values) keeps the sub-line kernels' fused x pass where there is one: 384^3 fused x 1 114 us against 1 732 us in the
-    // R <= 32 class kernel, y and z on the tile kernels either way (238 -> 263 it/s)
-    if (xfused_plan_[1].joint != 3 && (odd_[0] == 3 || odd_[0] == 5)) {
-      XFusedArgs probe = {};
-      const bool mixed_fused = odd_[0] == 3 ? xfused_mixed_p<3>(g.nx / 3, probe, 0, nullptr, stream_, true)
-                                            : xfused_mixed_p<5>(g.nx / 5, probe, 0, nullptr, stream_, true);
-      if (mixed_fused) smooth_[0] = xfused_plan_[0] = xfused_plan_[1] = SmoothPlan();
-    }
-  }
-  if (fast_[2]) wz_ = upload(make_unit_roots(g.nz, g.nz / 2 + 1));
+  route_fused();
   if (need_scratch) FG_HIP_CHECK(hipMalloc(&scratch_, g.n * sizeof(double)));
   // three components larger than the 256 MB Infinity Cache: nothing a pass writes is still cached when the next reads it
   stream_stores_ = 3.0 * (double)g.n * sizeof(double) > 256.0 * 1024 * 1024 ? 1 : 0;
 }
 
+void Fft3::route_fused() {
+  const int len[2] = {g_.nx, g_.ny};
+  for (int a = 0; a < 2; ++a)
+    for (int three = 0; three < 2; ++three) fused_[a][three] = route_fused_x(len[a], three ? 3 : 1, joint_x_, a);
+}
+
 void Fft3::set_joint_x(bool on) {
   if (on == joint_x_) return;
   joint_x_ = on;
-  if (smooth_[0].n) {
-    smooth_plan_xfused(g_.nx, 1, &xfused_plan_[0], on);
-    smooth_plan_xfused(g_.nx, 3, &xfused_plan_[1], on);
-  }
-}
-
-// Exchange planes of the power-of-two y / x pass (axis 1 / 0) and of the mirrored z passes (axis 2, n = nz / 2 packed points).
-// The sub-line, plane, tile-plan, slab and fused-x kernels instantiate Line<N> with its default of two planes and are not asked.
-int Fft3::images_for(int axis, int n) const {
-  if (images_ == 1 || images_ == 2) return images_;
-  (void)axis;
-  (void)n;
-  return 2;
-}
-
-int Fft3::path(int axis) const {
-  const int len = axis == 0 ? g_.nx : (axis == 1 ? g_.ny : g_.nz);
-  if (len == 1) return 0;
-  if (fast_[axis]) return 1;
-  if (smooth_[axis].n) return 3;
-  if (odd_[axis]) return 2;
-  return blue_on(axis) ? 4 : 5;
+  route_fused();
 }
 
 Fft3::~Fft3() {
@@ -1128,202 +1078,115 @@ Fft3::~Fft3() {
   if (scratch_) (void)hipFree(scratch_);
 }
 
+StridedArgs Fft3::strided_args(double* data, int axis, double scale, int nt) const {
+  const long plane = (long)g_.ny * g_.nzc;
+  StridedArgs a;
+  a.data = reinterpret_cast<cplx*>(data);
+  a.ls = axis == 0 ? plane : axis == 1 ? g_.nzc : route_[2].p;
+  a.os = axis == 0 ? 0 : axis == 1 ? plane : g_.nzc;
+  a.ncols = axis == 0 ? (int)plane : axis == 1 ? g_.nzc : route_[2].p;
+  a.tiles_per_outer = 0;
+  a.scale = scale;
+  a.tw = tw_[axis];
+  a.nt = nt;
+  a.xcd_order = 0;   // (measured for the y passes: 512^3 -1..2 %, 256^3 +2 %)
+  // one or two exchange planes: the power-of-two y / x passes only (sub-line, slab and tile-plan kernels keep two)
+  a.images = pow2(axis) ? images_for() : 2;
+  return a;
+}
+
 void Fft3::strided(double* data, int ncomp, long comp_stride, int axis, int dir, double scale, const PlaneWindow* w) {
+  const AxisRoute& r = route_[axis];
   const int n = axis == 0 ? g_.nx : g_.ny;
-  const long ls = axis == 0 ? (long)g_.ny * g_.nzc : g_.nzc;
-  const int ncols = axis == 0 ? g_.ny * g_.nzc : g_.nzc;
   int nouter = axis == 0 ? 1 : g_.nx;
-  const long os = axis == 0 ? 0 : (long)g_.ny * g_.nzc;
+  const long cs = comp_stride / 2;
   const bool windowed = w && w->np >= 0;
-  if (windowed && (axis != 1 || !fast_[1] || w->x0 < 0 || w->x0 + w->np > g_.nx))
+  if (windowed && (axis != 1 || !pow2(1) || w->x0 < 0 || w->x0 + w->np > g_.nx))
     throw std::runtime_error("fft: plane windows need a power-of-two y pass");
-  if (n == 1) return;  // identity; forward() never folds the scale into a length-1 axis
-  if (fast_[axis]) {
-    StridedArgs a;
-    a.data = reinterpret_cast<cplx*>(data);
-    if (windowed) a.data += (long)w->x0 * os, nouter = w->np;
-    if (nouter == 0) return;
-    a.ls = ls;
-    a.os = os;
-    a.ncols = ncols;
-    a.tiles_per_outer = 0;
-    a.scale = scale;
-    a.tw = tw_[axis];
-    a.nt = stream_stores_ ? (1 | ((nt_loads_env() & 1) ? 2 : 0)) : 0;
-    if (w && w->nt >= 0) a.nt = w->nt;
-    a.xcd_order = 0;   // (measured for the y passes: 512^3 -1..2 %, 256^3 +2 %)
-    a.images = images_for(axis, n);
-    strided_pow2(n, a, nouter, dir, ncomp, comp_stride / 2, stream_);
-    return;
+  StridedArgs a = strided_args(data, axis, scale, nt_stream());
+  switch (r.resolved(bluestein_)) {
+    case Family::Len1: return;   // identity; forward() never folds the scale into a length-1 axis
+    case Family::Pow2:
+      if (windowed) a.data += (long)w->x0 * a.os, nouter = w->np;
+      if (nouter == 0) return;
+      if (w && w->nt >= 0) a.nt = w->nt;
+      return strided_pow2(n, a, nouter, dir, ncomp, cs, stream_);
+    case Family::Tile:
+      return launch_smooth_strided(SmoothArgs{a.data, a.ls, a.os, a.ncols, 0, scale, wgen_[axis], a.nt, r.plan}, nouter, dir, ncomp, cs, stream_);
+    case Family::SubOne:
+      return dispatch_p<3, 5, 7, 9>(r.p, [&](auto P) {
+        dispatch_sub_m(r.m, [&](auto M) {
+          launch_strided_mixed<decltype(M)::value, decltype(P)::value>(a, nouter, dir, ncomp, cs, wgen_[axis], stream_);
+        });
+      });
+    case Family::SubLds:
+    case Family::SubScratch: return strided_sublines(a, nouter, ncomp, comp_stride, axis, dir);
+    case Family::Bluestein:
+      return launch_bluestein_strided(BluesteinArgs{a.data, a.ls, a.os, a.ncols, 0, scale, a.nt, dir, n, blue_tables(axis), r.blue.pass},
+                                      nouter, ncomp, cs, stream_);
+    case Family::Quadratic: break;
   }
-  if (smooth_[axis].n) {
-    SmoothArgs a;
-    a.data = reinterpret_cast<cplx*>(data);
-    a.ls = ls;
-    a.os = os;
-    a.ncols = ncols;
-    a.tiles_per_outer = 0;
-    a.scale = scale;
-    a.w = wgen_[axis];
-    a.nt = stream_stores_ ? 3 : 0;
-    a.plan = smooth_[axis];
-    launch_smooth_strided(a, nouter, dir, ncomp, comp_stride / 2, stream_);
-    return;
-  }
-  if (odd_[axis]) {
-    // n = p * m: m-point kernels on the p interleaved sub-lines, combine sweep through the scratch component
-    const int p = odd_[axis], m = n / p;
-    if (p == 3 || p == 5 || p == 7 || p == 9) {
-      StridedArgs a;
-      a.data = reinterpret_cast<cplx*>(data);
-      a.ls = ls;
-      a.os = os;
-      a.ncols = ncols;
-      a.tiles_per_outer = 0;
-      a.scale = scale;
-      a.tw = tw_[axis];
-      a.nt = stream_stores_ ? 3 : 0;
-      a.xcd_order = 0;
-      const long cs2 = comp_stride / 2;
-      const bool done = p == 3   ? strided_mixed_p<3>(m, a, nouter, dir, ncomp, cs2, wgen_[axis], stream_)
-                        : p == 5 ? strided_mixed_p<5>(m, a, nouter, dir, ncomp, cs2, wgen_[axis], stream_)
-                        : p == 7 ? strided_mixed_p<7>(m, a, nouter, dir, ncomp, cs2, wgen_[axis], stream_)
-                                 : strided_mixed_p<9>(m, a, nouter, dir, ncomp, cs2, wgen_[axis], stream_);
-      if (done) return;
-    }
-    const long total = (long)nouter * m * ncols;
-    const unsigned nb = (unsigned)((total + 255) / 256);
-    auto subs = [&]() {
-      for (int r = 0; r < p; ++r) {
-        StridedArgs a;
-        a.data = reinterpret_cast<cplx*>(data) + r * ls;
-        a.ls = ls * p;
-        a.os = os;
-        a.ncols = ncols;
-        a.tiles_per_outer = 0;
-        a.scale = 1.0;
-        a.tw = tw_[axis];
-        a.nt = 0;
-        a.xcd_order = 0;
-        strided_pow2(m, a, nouter, dir, ncomp, comp_stride / 2, stream_);
-      }
-    };
-    const size_t tile_lds = (size_t)n * 8 * sizeof(cplx);
-    auto combine_tile = [&]() {
-      const int tiles = (ncols + 7) / 8;
-      const dim3 grid((unsigned)((long)tiles * nouter));
-      for (int c = 0; c < ncomp; ++c) {
-        cplx* d = reinterpret_cast<cplx*>(data + c * comp_stride);
-#define FG_TILE_COMBINE(D, PP)                                                                                         \
-  do {                                                                                                                 \
-    static PerDeviceOnce configured;                                                                                    \
-    if (auto once = configured.first_use()) {                                                                                                 \
-      FG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mixed_combine_tile<D, PP>),                    \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                       \
-    }                                                                                                                  \
-    hipLaunchKernelGGL((k_mixed_combine_tile<D, PP>), grid, dim3(256), tile_lds, stream_, d, ls, os, ncols, tiles, m, p, \
-                       scale, wgen_[axis]);                                                                            \
-  } while (0)
-        if (dir < 0) {
-          if (p == 3) FG_TILE_COMBINE(-1, 3);
-          else if (p == 5) FG_TILE_COMBINE(-1, 5);
-          else if (p == 7) FG_TILE_COMBINE(-1, 7);
-          else if (p == 9) FG_TILE_COMBINE(-1, 9);
-          else if (p == 15) FG_TILE_COMBINE(-1, 15);
-          else if (p == 25) FG_TILE_COMBINE(-1, 25);
-          else FG_TILE_COMBINE(-1, 0);
-        } else {
-          if (p == 3) FG_TILE_COMBINE(+1, 3);
-          else if (p == 5) FG_TILE_COMBINE(+1, 5);
-          else if (p == 7) FG_TILE_COMBINE(+1, 7);
-          else if (p == 9) FG_TILE_COMBINE(+1, 9);
-          else if (p == 15) FG_TILE_COMBINE(+1, 15);
-          else if (p == 25) FG_TILE_COMBINE(+1, 25);
-          else FG_TILE_COMBINE(+1, 0);
-        }
-#undef FG_TILE_COMBINE
-        FG_HIP_CHECK(hipGetLastError());
-      }
-    };
-    auto combine_scratch = [&]() {
-      for (int c = 0; c < ncomp; ++c) {
-        cplx* src = reinterpret_cast<cplx*>(data + c * comp_stride);
-#define FG_COMBINE(D, PP)                                                                                              \
-  hipLaunchKernelGGL((k_mixed_combine<D, PP>), dim3(nb), dim3(256), 0, stream_, src, reinterpret_cast<cplx*>(scratch_), ls, \
-                     os, ncols, nouter, m, p, scale, wgen_[axis])
-        if (dir < 0) {
-          if (p == 3) FG_COMBINE(-1, 3);
-          else if (p == 5) FG_COMBINE(-1, 5);
-          else if (p == 7) FG_COMBINE(-1, 7);
-          else FG_COMBINE(-1, 0);
-        } else {
-          if (p == 3) FG_COMBINE(+1, 3);
-          else if (p == 5) FG_COMBINE(+1, 5);
-          else if (p == 7) FG_COMBINE(+1, 7);
-          else FG_COMBINE(+1, 0);
-        }
-#undef FG_COMBINE
-        FG_HIP_CHECK(hipGetLastError());
-        FG_HIP_CHECK(hipMemcpyAsync(src, scratch_, g_.n * sizeof(double), hipMemcpyDeviceToDevice, stream_));
-      }
-    };
-    auto combine = [&]() {
-      if (tile_lds <= 144 * 1024) combine_tile();   // whole lines in LDS: in place
-      else combine_scratch();
-    };
-    if (dir < 0) {
-      subs();
-      combine();
-    } else {
-      combine();
-      subs();
-    }
-    return;
-  }
-  if (blue_on(axis)) {
-    BluesteinArgs a;
-    a.data = reinterpret_cast<cplx*>(data);
-    a.ls = ls;
-    a.os = os;
-    a.ncols = ncols;
-    a.tiles_per_outer = 0;
-    a.scale = scale;
-    a.nt = stream_stores_ ? 3 : 0;
-    a.dir = dir;
-    a.n = n;
-    a.t = BluesteinTables{blue_tab_[axis][0], blue_tab_[axis][1], blue_tab_[axis][2]};
-    a.plan = blue_[axis].pass;
-    launch_bluestein_strided(a, nouter, ncomp, comp_stride / 2, stream_);
-    return;
-  }
-  // generic: component by component through the scratch buffer
-  const long total = (long)nouter * n * ncols;
-  const int bs = 256;
+  // O(n^2) sums: component by component through the scratch buffer
+  const long total = (long)nouter * n * a.ncols;
   for (int c = 0; c < ncomp; ++c) {
     cplx* src = reinterpret_cast<cplx*>(data + c * comp_stride);
-    hipLaunchKernelGGL(k_dft_strided_generic, dim3((unsigned)((total + bs - 1) / bs)), dim3(bs), 0, stream_, src,
-                       reinterpret_cast<cplx*>(scratch_), ls, os, ncols, nouter, n, dir, scale, wgen_[axis]);
+    hipLaunchKernelGGL(k_dft_strided_generic, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream_, src,
+                       reinterpret_cast<cplx*>(scratch_), a.ls, a.os, a.ncols, nouter, n, dir, scale, wgen_[axis]);
     FG_HIP_CHECK(hipGetLastError());
     FG_HIP_CHECK(hipMemcpyAsync(src, scratch_, g_.n * sizeof(double), hipMemcpyDeviceToDevice, stream_));
   }
 }
 
+// n = p * m: m-point kernels on the p interleaved sub-lines and one combine sweep -- in place through LDS while whole lines of
+// an 8-column tile fit (n * 128 bytes), else out of place through the scratch component.  Forward: sub-lines, then combine.
+void Fft3::strided_sublines(const StridedArgs& a, int nouter, int ncomp, long comp_stride, int axis, int dir) {
+  const AxisRoute& r = route_[axis];
+  const int p = r.p, m = r.m;
+  const cplx* const w = wgen_[axis];
+  auto subs = [&]() {
+    for (int q = 0; q < p; ++q) {
+      StridedArgs s = a;
+      s.data += q * a.ls;
+      s.ls = a.ls * p;
+      s.scale = 1.0;
+      s.nt = 0;
+      strided_pow2(m, s, nouter, dir, ncomp, comp_stride / 2, stream_);
+    }
+  };
+  auto combine = [&]() {
+    for (int c = 0; c < ncomp; ++c) {
+      cplx* d = a.data + c * (comp_stride / 2);
+      cplx* const tmp = reinterpret_cast<cplx*>(scratch_);
+      if (r.family == Family::SubLds) {
+        dispatch_p<3, 5, 7, 9, 15, 25, 0>(p, [&](auto P) {
+          if (dir < 0) launch_combine_tile<-1, decltype(P)::value>(d, a.ls, a.os, a.ncols, nouter, m, p, a.scale, w, stream_);
+          else launch_combine_tile<+1, decltype(P)::value>(d, a.ls, a.os, a.ncols, nouter, m, p, a.scale, w, stream_);
+        });
+        FG_HIP_CHECK(hipGetLastError());
+      } else {
+        dispatch_p<3, 5, 7, 0>(p, [&](auto P) {
+          if (dir < 0) launch_combine_scratch<-1, decltype(P)::value>(d, tmp, a.ls, a.os, a.ncols, nouter, m, p, a.scale, w, stream_);
+          else launch_combine_scratch<+1, decltype(P)::value>(d, tmp, a.ls, a.os, a.ncols, nouter, m, p, a.scale, w, stream_);
+        });
+        FG_HIP_CHECK(hipGetLastError());
+        FG_HIP_CHECK(hipMemcpyAsync(d, scratch_, g_.n * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+      }
+    }
+  };
+  if (dir < 0) subs(), combine();
+  else combine(), subs();
+}
+
 // forward transform along `axis` (0 = x of [nx][ny][nzc], 1 = y, used for the x lines of a y-slab),
 // scale, Green operator, inverse transform -- one kernel for the three components.
 bool Fft3::can_fuse(int axis, int ncomp) const {
-  const int n = axis == 0 ? g_.nx : g_.ny;
-  if (fast_[axis]) return n <= 1024;
-  if (axis == 0 && smooth_[0].n && (ncomp == 1 || ncomp == 3))   // the tile kernels' fused x pass: ncomp images in LDS
-    return xfused_plan_[ncomp == 3].n != 0;
-  // p * 2^k with p = 3, 5: the three-component form only
-  if (ncomp != 3 || (odd_[axis] != 3 && odd_[axis] != 5)) return false;
-  XFusedArgs a = {};
-  return odd_[axis] == 3 ? xfused_mixed_p<3>(n / 3, a, 0, nullptr, stream_, true) : xfused_mixed_p<5>(n / 5, a, 0, nullptr, stream_, true);
+  if (axis > 1) return false;
+  if (ncomp == 1 || ncomp == 3) return fused_[axis][ncomp == 3].kind != Fused::None;
+  return pow2(axis);   // (fused_g0 refuses other component counts)
 }
 
 bool Fft3::can_plane() const {
-  if (!fast_[1] || !fast_[2] || g_.nz % 2) return false;
-  return plane_dispatch(g_.ny, g_.nz / 2, true, PlaneArgs{}, 0, 0, 0, 0, stream_);
+  return pow2(1) && pow2(2) && plane_dispatch(g_.ny, g_.nz / 2, true, PlaneArgs{}, 0, 0, 0, 0, stream_);
 }
 
 void Fft3::zy_plane(double* data, int ncomp, long comp_stride, int dir) {
@@ -1333,7 +1196,7 @@ void Fft3::zy_plane(double* data, int ncomp, long comp_stride, int dir) {
 }
 
 bool Fft3::can_xlayout() const {
-  return fast_[0] && fast_[1] && g_.nx >= 8 && g_.nx <= 512 && g_.nzc % 8 == 0 && g_.ny >= 8;
+  return pow2(0) && pow2(1) && g_.nx >= 8 && g_.nx <= 512 && g_.nzc % 8 == 0 && g_.ny >= 8;
 }
 
 void Fft3::c2c_y_xlayout(double* in, long in_cs, double* out, long out_cs, int ncomp, int dir, double scale, const PlaneWindow* w) {
@@ -1342,22 +1205,12 @@ void Fft3::c2c_y_xlayout(double* in, long in_cs, double* out, long out_cs, int n
   if (windowed && (w->x0 < 0 || w->x0 + w->np > g_.nx)) throw std::runtime_error("fft: plane window out of range");
   const int x0 = windowed ? w->x0 : 0, np = windowed ? w->np : g_.nx;
   if (np == 0) return;
-  StridedArgs a;
-  a.data = reinterpret_cast<cplx*>(in);
+  StridedArgs a = strided_args(in, 1, scale, w && w->nt >= 0 ? w->nt : nt_stream());
   a.out = reinterpret_cast<cplx*>(out);
   a.out_cs = out_cs / 2;
-  a.ncols = g_.nzc;
-  a.tiles_per_outer = 0;
-  a.scale = scale;
-  a.tw = tw_[1];
-  a.nt = stream_stores_ ? (1 | ((nt_loads_env() & 1) ? 2 : 0)) : 0;
-  if (w && w->nt >= 0) a.nt = w->nt;
-  a.xcd_order = 0;
-  const long plain_ls = g_.nzc, plain_os = (long)g_.ny * g_.nzc;
+  const long plain_ls = a.ls, plain_os = a.os;
   const long xl_ls = (long)g_.nx * 8, xl_os = 8, xl_ts = (long)g_.ny * g_.nx * 8;
   if (dir < 0) {
-    a.ls = plain_ls;
-    a.os = plain_os;
     a.ls_out = xl_ls;
     a.os_out = xl_os;
     a.ts_out = xl_ts;
@@ -1372,7 +1225,6 @@ void Fft3::c2c_y_xlayout(double* in, long in_cs, double* out, long out_cs, int n
     a.data += (long)x0 * xl_os;
     a.out += (long)x0 * plain_os;
   }
-  a.images = images_for(1, g_.ny);
   strided_pow2_narrow(g_.ny, a, np, dir, ncomp, in_cs / 2, stream_);   // 8-column tiles: the layout's inner dimension
 }
 
@@ -1380,13 +1232,15 @@ void Fft3::fused_g0(double* data, long comp_stride, int axis, double scale, cons
                     long xjump, bool xlayout) {
   if (ncomp != 1 && ncomp != 3) throw std::runtime_error("fft: fused Green-operator pass takes 1 or 3 components");
   if (!can_fuse(axis, ncomp)) throw std::runtime_error("fft: fused Green-operator pass not available for this length");
+  const FusedXRoute& f = fused_[axis][ncomp == 3];
   const int n = axis == 0 ? g_.nx : g_.ny;
+  const StridedArgs geo = strided_args(data, axis, scale, nt_stream());
   XFusedArgs a;
-  a.data = reinterpret_cast<cplx*>(data);
+  a.data = geo.data;
   a.comp_stride = comp_stride / 2;
-  a.ls = axis == 0 ? (long)g_.ny * g_.nzc : g_.nzc;
-  a.os = axis == 0 ? 0 : (long)g_.ny * g_.nzc;
-  a.ncols = axis == 0 ? g_.ny * g_.nzc : g_.nzc;
+  a.ls = geo.ls;
+  a.os = geo.os;
+  a.ncols = geo.ncols;
   a.tiles_per_outer = 0;
   a.flat_cols = axis == 0 ? 1 : 0;
   a.nzc = g_.nzc;
@@ -1395,16 +1249,16 @@ void Fft3::fused_g0(double* data, long comp_stride, int axis, double scale, cons
   a.scale = scale;
   a.c10 = gp.c10;
   a.c20 = gp.c20;
-  a.tw = tw_[axis];
+  a.tw = geo.tw;
   a.half_root = half_root_[axis];
   a.inv_h = gp.inv_h0;
-  a.nt = stream_stores_ ? (1 | ((nt_loads_env() & 2) ? 2 : 0)) : 0;
+  a.nt = geo.nt;
   for (int k = 0; k < 3; ++k) {
     a.kpm[k] = gp.kpm[k];
     a.kp[k] = gp.kp[k];
   }
   if (xjump != 0) {
-    if (!fast_[axis] || axis != 0 || ncomp != 3) throw std::runtime_error("fft: interleaved layout needs the radix x pass");
+    if (f.kind != Fused::Pow2 || axis != 0 || ncomp != 3) throw std::runtime_error("fft: interleaved layout needs the radix x pass");
     a.xsplit = xsplit;
     a.xjump = xjump / 2;
   }
@@ -1416,36 +1270,27 @@ void Fft3::fused_g0(double* data, long comp_stride, int axis, double scale, cons
     a.ncols = g_.ny * g_.nzc;   // (tiles = ncols / 8 = (nzc / 8) * ny)
   }
   const int nouter = axis == 0 ? 1 : g_.nx;
-  if (!fast_[axis] && axis == 0 && smooth_[0].n) {
-    if (xjump != 0 || xlayout) throw std::runtime_error("fft: the tile kernels' fused x pass takes the plain layout");
-    SmoothXArgs x;
-    x.base.plan = xfused_plan_[ncomp == 3];
-    if (!x.base.plan.n) throw std::runtime_error("fft: fused Green-operator pass not available for this length");
-    x.base.data = reinterpret_cast<cplx*>(data);
-    x.base.ls = (long)g_.ny * g_.nzc;
-    x.base.os = 0;
-    x.base.ncols = g_.ny * g_.nzc;
-    x.base.tiles_per_outer = 0;
-    x.base.scale = scale;
-    x.base.w = wgen_[0];
-    x.base.nt = stream_stores_ ? 3 : 0;
-    x.comp_stride = comp_stride / 2;
-    x.ncomp = ncomp;
-    x.nzc = g_.nzc;
-    x.nzf = g_.nzf;
-    x.jj0 = jj0;
-    x.c10 = gp.c10;
-    x.c20 = gp.c20;
-    for (int k = 0; k < 3; ++k) x.kpm[k] = gp.kpm[k], x.kp[k] = gp.kp[k];
-    launch_smooth_xfused(x, stream_);
-    return;
-  }
-  if (!fast_[axis]) {
-    a.nt = stream_stores_ ? 3 : 0;
-    const bool ok = odd_[axis] == 3 ? xfused_mixed_p<3>(n / 3, a, nouter, wgen_[axis], stream_, false)
-                                    : xfused_mixed_p<5>(n / 5, a, nouter, wgen_[axis], stream_, false);
-    if (!ok) throw std::runtime_error("fft: fused Green-operator pass not available for this length");
-    return;
+  switch (f.kind) {
+    case Fused::Tile: {   // ncomp images in LDS
+      if (xjump != 0 || xlayout) throw std::runtime_error("fft: the tile kernels' fused x pass takes the plain layout");
+      SmoothXArgs x;
+      x.base = SmoothArgs{geo.data, geo.ls, geo.os, geo.ncols, 0, scale, wgen_[0], geo.nt, f.plan};
+      x.comp_stride = comp_stride / 2;
+      x.ncomp = ncomp;
+      x.nzc = g_.nzc;
+      x.nzf = g_.nzf;
+      x.jj0 = jj0;
+      x.c10 = gp.c10;
+      x.c20 = gp.c20;
+      for (int k = 0; k < 3; ++k) x.kpm[k] = gp.kpm[k], x.kp[k] = gp.kp[k];
+      return launch_smooth_xfused(x, stream_);
+    }
+    case Fused::Sub:   // p * 2^k with p = 3, 5: the three-component form only
+      return dispatch_p<3, 5>(f.p, [&](auto P) {
+        dispatch_sub_m(f.m, [&](auto M) { launch_xfused_mixed<decltype(M)::value, decltype(P)::value>(a, nouter, wgen_[axis], stream_); });
+      });
+    case Fused::None:   // (refused above)
+    case Fused::Pow2: break;
   }
   switch (n) {
     case 8: xfused_n<8>(a, nouter, ncomp, stream_); break;
@@ -1462,8 +1307,7 @@ void Fft3::fused_g0(double* data, long comp_stride, int axis, double scale, cons
 
 bool Fft3::can_block_y(int nranks) const {
   if (nranks < 1 || g_.ny % nranks) return false;
-  const int nyl = g_.ny / nranks;
-  return fast_[1] && is_pow2(nyl);
+  return pow2(1) && is_pow2(g_.ny / nranks);
 }
 
 void Fft3::c2c_y_blocked(double* in, long in_cs, double* out, long out_cs, int ncomp, int dir, double scale, int nranks,
@@ -1472,23 +1316,15 @@ void Fft3::c2c_y_blocked(double* in, long in_cs, double* out, long out_cs, int n
   const int nyl = g_.ny / nranks;
   int sh = 0;
   while ((1 << sh) < nyl) ++sh;
-  const long plain_os = (long)g_.ny * g_.nzc, blocked_os = (long)nyl * g_.nzc;
   // interleave = 3: a peer's block holds its three components one after the other ([q][c][nx][ny/P][nzc]; the component
   // stride of the blocked side is then ONE block) -- one message per peer
   const long jump = (long)interleave * g_.nx * nyl * g_.nzc - (long)nyl * g_.nzc;
-  StridedArgs a;
-  a.data = reinterpret_cast<cplx*>(in);
+  StridedArgs a = strided_args(in, 1, scale, nt_stream());
+  a.images = 2;   // (set_images never reached the slab's y passes)
   a.out = reinterpret_cast<cplx*>(out);
   a.out_cs = out_cs / 2;
-  a.ls = g_.nzc;
-  a.ncols = g_.nzc;
-  a.tiles_per_outer = 0;
-  a.scale = scale;
-  a.tw = tw_[1];
-  a.nt = stream_stores_ ? (1 | ((nt_loads_env() & 1) ? 2 : 0)) : 0;
-  a.xcd_order = 0;
+  const long plain_os = a.os, blocked_os = (long)nyl * g_.nzc;
   if (dir < 0) {
-    a.os = plain_os;
     a.os_out = blocked_os;
     a.split_out = sh;
     a.jump_out = jump;
@@ -1507,210 +1343,70 @@ void Fft3::c2c_y(double* data, int ncomp, long comp_stride, int dir, double scal
 void Fft3::c2c_x(double* data, int ncomp, long comp_stride, int dir, double scale) {
   strided(data, ncomp, comp_stride, 0, dir, scale);
 }
+void Fft3::r2c_z(double* data, int ncomp, long comp_stride, const PlaneWindow* w) { z_pass(data, ncomp, comp_stride, true, w); }
+void Fft3::c2r_z(double* data, int ncomp, long comp_stride, const PlaneWindow* w) { z_pass(data, ncomp, comp_stride, false, w); }
 
-void Fft3::r2c_z(double* data, int ncomp, long comp_stride, const PlaneWindow* w) {
+// r2c (fwd) / c2r along z: the two directions differ in the kernels the family launches, not in how it is chosen
+void Fft3::z_pass(double* data, int ncomp, long comp_stride, bool fwd, const PlaneWindow* w) {
+  const AxisRoute& r = route_[2];
   long nrows = (long)g_.nx * g_.ny;
   if (w && w->np >= 0) {
-    if (!fast_[2] || w->x0 < 0 || w->x0 + w->np > g_.nx) throw std::runtime_error("fft: plane windows need a power-of-two z pass");
+    if (!pow2(2) || w->x0 < 0 || w->x0 + w->np > g_.nx) throw std::runtime_error("fft: plane windows need a power-of-two z pass");
     data += (long)w->x0 * g_.ny * g_.nzp;
     nrows = (long)w->np * g_.ny;
     if (nrows == 0) return;
   }
-  if (fast_[2]) {
-    ZArgs a = {data, nrows, g_.nzp, tw_[2], wz_, stream_stores_ ? (1 | ((nt_loads_env() & 4) ? 2 : 0)) : 0};
-    if (w && w->nt >= 0) a.nt = w->nt;
-    a.images = images_for(2, g_.nz / 2);
-    // the real split right after the last pass, mirrored values by wave shuffle instead of a round trip of the spectrum
-    // through LDS (R2CKernel<.., MIRROR>): 512^3 1.30 -> 1.16 ms, 256^3 0.158 -> 0.155 ms
-    {
-      switch (g_.nz / 2) {
-#define FG_CASE(m) case m:                                                                                         \
-    if (a.images == 1) launch_z<R2CKernel<m, ZLines<m>::value, true, 1>>(a, ncomp, comp_stride, ZLines<m>::value, stream_); \
-    else launch_z<R2CKernel<m, ZLines<m>::value, true>>(a, ncomp, comp_stride, ZLines<m>::value, stream_);                \
-    return;
-        FG_CASE(64) FG_CASE(128) FG_CASE(256) FG_CASE(512)
-#undef FG_CASE
-        default: break;
-      }
+  switch (r.resolved(bluestein_)) {
+    case Family::Pow2: {
+      ZArgs a = {data, nrows, g_.nzp, tw_[2], wz_, w && w->nt >= 0 ? w->nt : nt_stream()};
+      a.images = images_for();
+      return fwd ? z_pow2<R2CKernel>(r.line, a, ncomp, comp_stride, stream_) : z_pow2<C2RKernel>(r.line, a, ncomp, comp_stride, stream_);
     }
-    switch (g_.nz / 2) {
-#define FG_CASE(m) case m: launch_z<R2CKernel<m, ZLines<m>::value>>(a, ncomp, comp_stride, ZLines<m>::value, stream_); break;
-      FG_CASE(8) FG_CASE(16) FG_CASE(32) FG_CASE(64) FG_CASE(128) FG_CASE(256) FG_CASE(512) FG_CASE(1024)
-#undef FG_CASE
-      default: throw std::runtime_error("fft: unsupported fast z length");
-    }
-    return;
+    case Family::Tile:
+      return launch_smooth_z(SmoothZArgs{data, nrows, g_.nzp, wgen_[2], nt_stream(), r.plan, r.zodd ? 1 : 0}, fwd, ncomp, comp_stride, stream_);
+    case Family::SubOne:
+      return dispatch_p<3, 5, 7, 9>(r.p, [&](auto P) {
+        dispatch_sub_m(r.m, [&](auto M) {
+          launch_z_mixed<decltype(M)::value, decltype(P)::value>(data, nrows, g_.nzp, ncomp, comp_stride, fwd, tw_[2], wgen_[2], stream_);
+        });
+      });
+    case Family::SubLds:
+    case Family::SubScratch: return z_sublines(data, nrows, ncomp, comp_stride, fwd);
+    case Family::Bluestein:
+      return launch_bluestein_z(BluesteinZArgs{data, nrows, g_.nzp, nt_stream(), fwd ? 1 : 0, g_.nz % 2, r.blue.n, blue_tables(2), wgen_[2], r.blue.pass},
+                                ncomp, comp_stride, stream_);
+    case Family::Len1:
+    case Family::Quadratic: break;
   }
-  if (smooth_[2].n) {
-    SmoothZArgs a = {data, nrows, g_.nzp, wgen_[2], stream_stores_ ? 3 : 0, smooth_[2], zodd_ ? 1 : 0};
-    launch_smooth_z(a, true, ncomp, comp_stride, stream_);
-    return;
-  }
-  if (odd_[2]) {
-    // nz = 2 M, M = p m: m-point kernels on the sub-rows of the packed real rows ([m][p] complex, line stride p), then
-    // combine + real split per row through the scratch component
-    const int M = g_.nz / 2, p = odd_[2], m = M / p;
-    if ((p == 3 && z_mixed_p<3>(m, data, nrows, g_.nzp, ncomp, comp_stride, true, tw_[2], wgen_[2], stream_)) ||
-        (p == 5 && z_mixed_p<5>(m, data, nrows, g_.nzp, ncomp, comp_stride, true, tw_[2], wgen_[2], stream_)) ||
-        (p == 7 && z_mixed_p<7>(m, data, nrows, g_.nzp, ncomp, comp_stride, true, tw_[2], wgen_[2], stream_)) ||
-        (p == 9 && z_mixed_p<9>(m, data, nrows, g_.nzp, ncomp, comp_stride, true, tw_[2], wgen_[2], stream_)))
-      return;
-    StridedArgs a;
-    a.data = reinterpret_cast<cplx*>(data);
-    a.ls = p;
-    a.os = g_.nzc;
-    a.ncols = p;
-    a.tiles_per_outer = 0;
-    a.scale = 1.0;
-    a.tw = tw_[2];
-    a.nt = 0;
-    a.xcd_order = 0;
-    strided_pow2_narrow(m, a, (int)nrows, -1, ncomp, comp_stride / 2, stream_);
-    if ((size_t)(M + 1) * sizeof(cplx) > 144 * 1024) throw std::runtime_error("fft: z length too large for the sub-line path");
-    int rows = (int)(48 * 1024 / ((M + 1) * sizeof(cplx)));   // rows per workgroup: 48 KB of LDS
-    if (rows < 1) rows = 1;
-    const size_t lds = (size_t)rows * (M + 1) * sizeof(cplx);
-    const unsigned nb = (unsigned)((nrows + rows - 1) / rows);
-    for (int c = 0; c < ncomp; ++c) {
-      double* src = data + c * comp_stride;
-#define FG_FINISH(PP)                                                                                             \
-  do {                                                                                                            \
-    static PerDeviceOnce configured;                                                                               \
-    if (auto once = configured.first_use()) {                                                                                            \
-      FG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mixed_r2c_finish<PP>),                    \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                  \
-    }                                                                                                             \
-    hipLaunchKernelGGL(k_mixed_r2c_finish<PP>, dim3(nb), dim3(256), lds, stream_, src, nrows, g_.nzp, M, p, rows, \
-                       wgen_[2]);                                                                                 \
-  } while (0)
-      if (p == 3) FG_FINISH(3);
-      else if (p == 5) FG_FINISH(5);
-      else if (p == 7) FG_FINISH(7);
-      else if (p == 9) FG_FINISH(9);
-      else if (p == 15) FG_FINISH(15);
-      else if (p == 25) FG_FINISH(25);
-      else FG_FINISH(0);
-#undef FG_FINISH
-      FG_HIP_CHECK(hipGetLastError());
-    }
-    return;
-  }
-  if (blue_on(2)) {
-    BluesteinZArgs a = {data, nrows, g_.nzp, stream_stores_ ? 3 : 0, 1, g_.nz % 2, blue_[2].n,
-                        BluesteinTables{blue_tab_[2][0], blue_tab_[2][1], blue_tab_[2][2]}, wgen_[2], blue_[2].pass};
-    launch_bluestein_z(a, ncomp, comp_stride, stream_);
-    return;
-  }
-  const long total = nrows * g_.nzc;
-  const int bs = 256;
+  const dim3 grid((unsigned)((nrows * (fwd ? g_.nzc : g_.nz) + 255) / 256));
   for (int c = 0; c < ncomp; ++c) {
     double* src = data + c * comp_stride;
-    hipLaunchKernelGGL(k_r2c_generic, dim3((unsigned)((total + bs - 1) / bs)), dim3(bs), 0, stream_, src, scratch_,
-                       nrows, g_.nz, g_.nzp, wgen_[2]);
+    if (fwd) hipLaunchKernelGGL(k_r2c_generic, grid, dim3(256), 0, stream_, src, scratch_, nrows, g_.nz, g_.nzp, wgen_[2]);
+    else hipLaunchKernelGGL(k_c2r_generic, grid, dim3(256), 0, stream_, src, scratch_, nrows, g_.nz, g_.nzp, wgen_[2]);
     FG_HIP_CHECK(hipGetLastError());
     FG_HIP_CHECK(hipMemcpyAsync(src, scratch_, g_.n * sizeof(double), hipMemcpyDeviceToDevice, stream_));
   }
 }
 
-void Fft3::c2r_z(double* data, int ncomp, long comp_stride, const PlaneWindow* w) {
-  long nrows = (long)g_.nx * g_.ny;
-  if (w && w->np >= 0) {
-    if (!fast_[2] || w->x0 < 0 || w->x0 + w->np > g_.nx) throw std::runtime_error("fft: plane windows need a power-of-two z pass");
-    data += (long)w->x0 * g_.ny * g_.nzp;
-    nrows = (long)w->np * g_.ny;
-    if (nrows == 0) return;
-  }
-  if (fast_[2]) {
-    ZArgs a = {data, nrows, g_.nzp, tw_[2], wz_, stream_stores_ ? (1 | ((nt_loads_env() & 8) ? 2 : 0)) : 0};
-    if (w && w->nt >= 0) a.nt = w->nt;
-    a.images = images_for(2, g_.nz / 2);
-    // every coefficient read once: the mirrored one comes from the neighbouring lane (C2RKernel<.., MIRROR>); 256^3
-    // 0.164 -> 0.151 ms, 512^3 1.38 -> 1.19 ms
-    {
-      switch (g_.nz / 2) {
-#define FG_CASE(m) case m:                                                                                         \
-    if (a.images == 1) launch_z<C2RKernel<m, ZLines<m>::value, true, 1>>(a, ncomp, comp_stride, ZLines<m>::value, stream_); \
-    else launch_z<C2RKernel<m, ZLines<m>::value, true>>(a, ncomp, comp_stride, ZLines<m>::value, stream_);                \
-    return;
-        FG_CASE(64) FG_CASE(128) FG_CASE(256) FG_CASE(512)
-#undef FG_CASE
-        default: break;
-      }
-    }
-    switch (g_.nz / 2) {
-#define FG_CASE(m) case m: launch_z<C2RKernel<m, ZLines<m>::value>>(a, ncomp, comp_stride, ZLines<m>::value, stream_); break;
-      FG_CASE(8) FG_CASE(16) FG_CASE(32) FG_CASE(64) FG_CASE(128) FG_CASE(256) FG_CASE(512) FG_CASE(1024)
-#undef FG_CASE
-      default: throw std::runtime_error("fft: unsupported fast z length");
-    }
-    return;
-  }
-  if (smooth_[2].n) {
-    SmoothZArgs a = {data, nrows, g_.nzp, wgen_[2], stream_stores_ ? 3 : 0, smooth_[2], zodd_ ? 1 : 0};
-    launch_smooth_z(a, false, ncomp, comp_stride, stream_);
-    return;
-  }
-  if (odd_[2]) {
-    const int M = g_.nz / 2, p = odd_[2], m = M / p;
-    if ((p == 3 && z_mixed_p<3>(m, data, nrows, g_.nzp, ncomp, comp_stride, false, tw_[2], wgen_[2], stream_)) ||
-        (p == 5 && z_mixed_p<5>(m, data, nrows, g_.nzp, ncomp, comp_stride, false, tw_[2], wgen_[2], stream_)) ||
-        (p == 7 && z_mixed_p<7>(m, data, nrows, g_.nzp, ncomp, comp_stride, false, tw_[2], wgen_[2], stream_)) ||
-        (p == 9 && z_mixed_p<9>(m, data, nrows, g_.nzp, ncomp, comp_stride, false, tw_[2], wgen_[2], stream_)))
-      return;
-    int rows = (int)(48 * 1024 / ((M + 1) * sizeof(cplx)));
-    if (rows < 1) rows = 1;
-    const size_t lds = (size_t)rows * (M + 1) * sizeof(cplx);
-    const unsigned nb = (unsigned)((nrows + rows - 1) / rows);
+// nz = 2 M, M = p m: m-point kernels on the sub-rows of the packed real rows ([m][p] complex, line stride p) and one sweep per
+// row in place through LDS -- forward: sub-rows, then combine + real split; inverse: merge + inverse combine, then sub-rows
+void Fft3::z_sublines(double* data, long nrows, int ncomp, long comp_stride, bool fwd) {
+  const int M = g_.nz / 2, p = route_[2].p, m = route_[2].m;
+  if (fwd && (size_t)(M + 1) * sizeof(cplx) > kSubLdsMax) throw std::runtime_error("fft: z length too large for the sub-line path");
+  auto subs = [&]() {
+    strided_pow2_narrow(m, strided_args(data, 2, 1.0, 0), (int)nrows, fwd ? -1 : +1, ncomp, comp_stride / 2, stream_);
+  };
+  auto sweep = [&]() {
     for (int c = 0; c < ncomp; ++c) {
-      double* src = data + c * comp_stride;
-#define FG_START(PP)                                                                                             \
-  do {                                                                                                           \
-    static PerDeviceOnce configured;                                                                              \
-    if (auto once = configured.first_use()) {                                                                                           \
-      FG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mixed_c2r_start<PP>),                    \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                 \
-    }                                                                                                            \
-    hipLaunchKernelGGL(k_mixed_c2r_start<PP>, dim3(nb), dim3(256), lds, stream_, src, nrows, g_.nzp, M, p, rows, \
-                       wgen_[2]);                                                                                \
-  } while (0)
-      if (p == 3) FG_START(3);
-      else if (p == 5) FG_START(5);
-      else if (p == 7) FG_START(7);
-      else if (p == 9) FG_START(9);
-      else if (p == 15) FG_START(15);
-      else if (p == 25) FG_START(25);
-      else FG_START(0);
-#undef FG_START
+      dispatch_p<3, 5, 7, 9, 15, 25, 0>(p, [&](auto P) {
+        if (fwd) launch_z_sweep<true, decltype(P)::value>(data + c * comp_stride, nrows, g_.nzp, M, p, wgen_[2], stream_);
+        else launch_z_sweep<false, decltype(P)::value>(data + c * comp_stride, nrows, g_.nzp, M, p, wgen_[2], stream_);
+      });
       FG_HIP_CHECK(hipGetLastError());
     }
-    StridedArgs a;
-    a.data = reinterpret_cast<cplx*>(data);
-    a.ls = p;
-    a.os = g_.nzc;
-    a.ncols = p;
-    a.tiles_per_outer = 0;
-    a.scale = 1.0;
-    a.tw = tw_[2];
-    a.nt = 0;
-    a.xcd_order = 0;
-    strided_pow2_narrow(m, a, (int)nrows, +1, ncomp, comp_stride / 2, stream_);
-    return;
-  }
-  if (blue_on(2)) {
-    BluesteinZArgs a = {data, nrows, g_.nzp, stream_stores_ ? 3 : 0, 0, g_.nz % 2, blue_[2].n,
-                        BluesteinTables{blue_tab_[2][0], blue_tab_[2][1], blue_tab_[2][2]}, wgen_[2], blue_[2].pass};
-    launch_bluestein_z(a, ncomp, comp_stride, stream_);
-    return;
-  }
-  const long total = nrows * g_.nz;
-  const int bs = 256;
-  for (int c = 0; c < ncomp; ++c) {
-    double* src = data + c * comp_stride;
-    hipLaunchKernelGGL(k_c2r_generic, dim3((unsigned)((total + bs - 1) / bs)), dim3(bs), 0, stream_, src, scratch_,
-                       nrows, g_.nz, g_.nzp, wgen_[2]);
-    FG_HIP_CHECK(hipGetLastError());
-    FG_HIP_CHECK(hipMemcpyAsync(src, scratch_, g_.n * sizeof(double), hipMemcpyDeviceToDevice, stream_));
-  }
+  };
+  if (fwd) subs(), sweep();
+  else sweep(), subs();
 }
 
 void Fft3::forward(double* data, int ncomp, long comp_stride, double scale) {
@@ -1739,3 +1435,4 @@ void Fft3::inverse(double* data, int ncomp, long comp_stride) {
 }
 
 }  // namespace fg
+

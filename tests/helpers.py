@@ -76,3 +76,25 @@ def emulation_build_flags():
     if os.environ.get("FG_EMU_SANITIZE") == "1":
         return ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + flags
     return ["-O2"] + flags
+
+
+def fft_route_grids():
+    """The grids of the FFT route checks (tests/test_gpu_fft_routes.py, tools/pass_digest.py fft), from the golden table
+    tests/golden/fft_routes.txt.gz: per axis the shortest length of every family and both sides of the thresholds (96 / 100 points
+    in x and y, nz = 112 / 144, the fused-x override at 384; nz = 134: Bluestein on the packed rows), the other axes at 8 x 8 (x 16 along z).
+    Returns [(grid, axis, family, path)]."""
+    import gzip
+    import os
+    table = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fft_routes.txt.gz")
+    rows = [ln.split() for ln in gzip.open(table, "rt") if not ln.startswith("#")]
+    route = {(int(r[0]), int(r[1])): (r[2], int(r[3])) for r in rows}
+    grids = []
+    for axis in range(3):
+        first = {}
+        for n in range(1, 2049):
+            first.setdefault(route[(axis, n)][0], n)
+        for n in sorted(set(first.values()) | ({112, 134, 144} if axis == 2 else {96, 100, 384})):
+            grid = [8, 8, 16]
+            grid[axis] = n
+            grids.append((tuple(grid), axis) + route[(axis, n)])
+    return grids

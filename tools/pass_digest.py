@@ -4,6 +4,7 @@ arithmetic on every path the list reaches: the check for a change that must leav
 
     python tools/pass_digest.py > profiles/pass_digest_<build>.txt
     python tools/pass_digest.py tiles > profiles/pass_digest_tiles_<build>.txt     (a second list: the tiled marching sweeps)
+    python tools/pass_digest.py fft > profiles/pass_digest_fft_<build>.txt         (a third: every transform family per axis)
 
 One line per run: grid, name, the digest of the residuals, the digest of the field and the iteration count -- or the solver's
 error text where a combination is refused (a refusal is part of the behaviour that is compared)."""
@@ -14,6 +15,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 
 from fibergen_amd import LSSolver  # noqa: E402
 
@@ -212,5 +214,25 @@ def tiles():
             report("heat aniso=%d cg" % an, grid, aniso=an, method="cg", **HEAT)
 
 
+def fft():
+    """every transform family on every axis (fg_fft_route.h): per axis the shortest length of each family and both sides of the
+    thresholds (tests/helpers.py fft_route_grids), thin on the other axes.  Three components with the fused x pass, without
+    it (the x passes on their own), and one component (heat); Bluestein against the O(n^2) sums on a prime length, the joint
+    and the per-component image of the tile kernels' fused x pass"""
+    from helpers import fft_route_grids
+    global COUNTERS
+    COUNTERS = ("fft_path_x", "fft_path_y", "fft_path_z")
+    for grid in sorted({g[0] for g in fft_route_grids()}):
+        report("stag", grid)
+        report("stag fuse_x=0", grid, fuse_x=0)
+        report("heat", grid, **HEAT)
+    for b in (0, 1):
+        for grid in ((67, 8, 16), (8, 67, 16), (8, 8, 134)):
+            report("stag bluestein=%d" % b, grid, bluestein=b)
+    for j in (0, 1):
+        report("stag joint_x=%d" % j, (100, 8, 16), joint_x=j)
+        report("heat joint_x=%d" % j, (100, 8, 16), joint_x=j, **HEAT)
+
+
 if __name__ == "__main__":
-    tiles() if sys.argv[1:] == ["tiles"] else main()
+    {"tiles": tiles, "fft": fft}.get((sys.argv[1:] or [""])[0], main)()
