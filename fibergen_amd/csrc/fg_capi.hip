@@ -253,7 +253,8 @@ int fg_set_option_i(fg_solver* s, const char* key, long value) {
     fg::SolverOptions& o = v.options();
     if (k == "maxiter") o.maxiter = value;
     else if (k == "mixing_rule") {
-      if (value != FG_MIXING_VOIGT && value != FG_MIXING_LAMINATE) throw std::runtime_error("Unknown mixing rule");
+      if (value != FG_MIXING_VOIGT && value != FG_MIXING_LAMINATE && value != FG_MIXING_REUSS) throw std::runtime_error("Unknown mixing rule");
+      if (value == FG_MIXING_REUSS && v.is_slab()) throw std::runtime_error("mixing_rule reuss is not available on slab-decomposed solvers");
       o.mixing = (int)value;
     } else if (k == "update_ref") o.update_ref = value != 0;
     else if (k == "mode") {
@@ -275,6 +276,7 @@ int fg_set_option_i(fg_solver* s, const char* key, long value) {
     else if (k == "fuse_x") o.fuse_x = value != 0;
     else if (k == "phi_sweep") o.phi_sweep = value != 0;
     else if (k == "aniso_tile") o.aniso_tile = value != 0;
+    else if (k == "reuss_sweep") o.reuss_sweep = value != 0;
     else if (k == "aniso_sc_tile") o.aniso_sc_tile = value != 0;
     else if (k == "laminate_overlap") o.laminate_overlap = value != 0;
     else if (k == "slab_loopback") o.slab_loopback = value != 0;

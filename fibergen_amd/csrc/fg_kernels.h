@@ -62,6 +62,7 @@ struct ScalarParams {
   double alpha, beta;
   int law[kMaxPhases];
   double K[kMaxPhases][6];
+  int mixing = kMixVoigt;   // kMixReuss: the harmonic mean of the isotropic phases (aniso phases are refused with it)
 };
 
 inline bool any_aniso_phase(const ScalarParams& sp) {
@@ -90,8 +91,10 @@ void launch_stress_div_voigt(const Grid& g, const StressParams& sp, const FieldP
 void launch_u_stress_div_voigt(const Grid& g, const StressParams& sp, const FieldPtrs<3>& u,
                                const FieldPtrs<kMaxPhases>& phi, const FieldPtrs<3>& f, const Vec6& E, double* partial,
                                double* sumsq6, hipStream_t s);
+// mixing = kMixVoigt: A = sum phi 2 mu, B = sum phi lambda; kMixReuss: A = 2 mu_bar, B = lambda_bar of the harmonic means
+// (reuss_moduli, fg_stage_math.h)
 void launch_effective_moduli(const Grid& g, const PhaseTable& pt, const FieldPtrs<kMaxPhases>& phi, const FieldPtrs<2>& mod,
-                             hipStream_t s);
+                             hipStream_t s, int mixing = kMixVoigt);
 void launch_u_fast(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& u, const FieldPtrs<2>& mod,
                    const FieldPtrs<3>& f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s);
 // tiled variant (every strain / polarisation value computed once; y neighbours through LDS, x by marching)
@@ -101,9 +104,10 @@ bool u_tile_supported(const Grid& g);
 void launch_eps_tile(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<6>& eps, const FieldPtrs<2>& mod,
                      const FieldPtrs<3>& f, double* partial, double* sum6, hipStream_t s);
 // two_phase != nullptr: mod.p[0] is phi_1 of two complementary phases (launch_complement_check), the sweep forms the moduli
+// -- the arithmetic means, or with reuss (two_phase required) the harmonic means from one division per voxel
 void launch_u_tile(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& u, const FieldPtrs<2>& mod,
                    const FieldPtrs<3>& f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s, bool sum_tau = false,
-                   const PhaseTable* two_phase = nullptr);
+                   const PhaseTable* two_phase = nullptr, bool reuss = false);
 // the tiled sweep on the NEW search direction of the conjugate gradients, formed on the fly: p_new = r + b p_old with
 // b = (sc[i_num] / nvox + small) / (sc[i_den] / nvox + small), stored to p_new (a buffer of its own), f = div((C - C0) : grad_s p_new)
 void launch_u_tile_cg(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& p_old, const FieldPtrs<3>& r,

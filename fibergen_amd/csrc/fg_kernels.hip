@@ -25,7 +25,8 @@ namespace {
 // REDUCE = 2: per-block partial sums of the energy density 1/2 P:eps (meanW  F:12239-12262 with the mixing rule's W: for
 // Voigt mixing sum_p phi_p 1/2 (C_p eps):eps = 1/2 P:eps; for laminate mixing c1 W1(F1) + c2 W2(F2) = 1/2 P:eps as well, the
 // cross term c1 c2 a.(sigma_1 - sigma_2) n vanishing with the traction jump the interface solve removes), in component 0.
-// MIX / NPH are compile-time so the Voigt two-phase sweep keeps a small register footprint.
+// MIX / NPH are compile-time so the Voigt two-phase sweep keeps a small register footprint.  MIX says whether the normals are
+// read: the Reuss rule (sp.mixing == kMixReuss, a branch of stress_voxel) reads none and runs the kMixVoigt instantiations.
 template <int REDUCE, int MIX, int NPH>
 __global__ __launch_bounds__(kBlock) void k_stress(Grid g, StressParams sp, FieldPtrs<6> eps, FieldPtrs<kMaxPhases> phi,
                                                    FieldPtrs<3> normals, FieldPtrs<6> tau, double* partial,

@@ -7,6 +7,7 @@
 #include "fg_kernels.h"
 
 #include <cstdlib>
+#include <stdexcept>
 #include <tuple>
 #include <type_traits>
 
@@ -204,6 +205,11 @@ __device__ unsigned long long g_k1_probe[kK1ProbeBlocks][kK1ProbeSlots];
 // forms the effective moduli itself, A = 2 mu_0 + phi_1 (2 mu_1 - 2 mu_0), B likewise -- 8 bytes per voxel less than the two
 // precomputed arrays (64 -> 56 B/voxel, the algorithmic figure).  lin = {2 mu_0 + beta, 2 (mu_1 - mu_0), lambda_0 + gamma,
 // lambda_1 - lambda_0} of the two phases.
+//
+// REUSS (with PHI2): the harmonic means of the same two phases (mixing_rule reuss, reuss_moduli in fg_stage_math.h), formed in
+// the sweep as well.  lin = {1 / 2 mu_0, 1 / 2 mu_1 - 1 / 2 mu_0, 1 / 3 K_0, 1 / 3 K_1 - 1 / 3 K_0} (3 K = 2 mu + 3 lambda): the
+// reciprocals are wave-uniform arguments, the voxel takes sa = a0 + phi_1 da, sk = b0 + phi_1 db and ONE division,
+// r = 1 / (sa sk):  A = sk r = 1 / sa,  3 K = sa r = 1 / sk,  B = (3 K - A) / 3; beta and gamma carry the reference material.
 struct PhaseLin {
   double a0, da, b0, db;
 };
@@ -237,13 +243,14 @@ constexpr int aniso_idx(int i, int j) {   // entry (i, j) of a packed symmetric 
 // NMOD = 5: gamma_scheme full_staggered (doubly fine grid): mod = {A_n, B_n, A_23, A_13, A_12}, the moduli of the normal
 // components and of each shear component from its own staggered phase fractions (see fg_kernels_dfg.hip); 3 more 16-byte
 // loads per plane.  NMOD = 2 is the staggered sweep, unchanged.
-template <int TYR, int ZS, bool SUMT, bool PHI2, bool CGP = false, int NMOD = 2, bool ANISO = false>
+template <int TYR, int ZS, bool SUMT, bool PHI2, bool CGP = false, int NMOD = 2, bool ANISO = false, bool REUSS = false>
 __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, double beta, double gamma, FieldPtrs<3> u,
                                                                       FieldPtrs<NMOD> mod, FieldPtrs<3> fo, Vec6 E, double* partial,
                                                                       int nty, int ntz, int LX, int nt,
                                                                       std::conditional_t<ANISO, AnisoLin, PhaseLin> lin,
                                                                       CgDirection cg) {
   static_assert(!ANISO || (PHI2 && NMOD == 2), "the anisotropic form reads phi_1 like PHI2");
+  static_assert(!REUSS || (PHI2 && NMOD == 2 && !ANISO), "the harmonic form reads phi_1 like PHI2");
   using S = TileShape<TYR, ZS>;
   constexpr bool FULLROW = S::FULLROW;
   constexpr int NZS = S::NZS, RW = S::RW;
@@ -396,8 +403,18 @@ __global__ __launch_bounds__(TYR * (ZS ? ZS : 1) * 64) void k_u_tile(Grid g, dou
       t0 = tt[0]; t1 = tt[1]; t2 = tt[2]; t3 = tt[3]; t4 = tt[4]; t5 = tt[5];
     } else {
     // ---- polarisation  tau = (A - 2 mu0) eps + (B - lambda0) tr(eps) I
-    const double ax = PHI2 ? lin.a0 + Ac.x * lin.da : Ac.x + beta, ay = PHI2 ? lin.a0 + Ac.y * lin.da : Ac.y + beta;
-    const double bx = PHI2 ? lin.b0 + Bc.x * lin.db : Bc.x + gamma, by = PHI2 ? lin.b0 + Bc.y * lin.db : Bc.y + gamma;
+    double ax, ay, bx, by;
+    if constexpr (REUSS) {
+      const double sax = lin.a0 + Ac.x * lin.da, say = lin.a0 + Ac.y * lin.da;
+      const double skx = lin.b0 + Ac.x * lin.db, sky = lin.b0 + Ac.y * lin.db;
+      const double rx = 1.0 / (sax * skx), ry = 1.0 / (say * sky);
+      const double Ax = skx * rx, Ay = sky * ry;
+      ax = Ax + beta; ay = Ay + beta;
+      bx = (sax * rx - Ax) * (1.0 / 3.0) + gamma; by = (say * ry - Ay) * (1.0 / 3.0) + gamma;
+    } else {
+      ax = PHI2 ? lin.a0 + Ac.x * lin.da : Ac.x + beta; ay = PHI2 ? lin.a0 + Ac.y * lin.da : Ac.y + beta;
+      bx = PHI2 ? lin.b0 + Bc.x * lin.db : Bc.x + gamma; by = PHI2 ? lin.b0 + Bc.y * lin.db : Bc.y + gamma;
+    }
     const double trx = e0.x + e1.x + e2.x, try_ = e0.y + e1.y + e2.y;
     t0.x = e0.x * ax + bx * trx; t0.y = e0.y * ay + by * try_;
     t1.x = e1.x * ax + bx * trx; t1.y = e1.y * ay + by * try_;
@@ -806,12 +823,30 @@ __global__ __launch_bounds__(kBlock) void k_sc_sweep_fast(Grid g, double beta, c
   }
 }
 
-// A = sum_p phi_p 2 mu_p, B = sum_p phi_p lambda_p with the Voigt rule's threshold (F:12736)
+// A = sum_p phi_p 2 mu_p, B = sum_p phi_p lambda_p with the Voigt rule's threshold (F:12736).
+// REUSS: A = 2 mu_bar, B = lambda_bar = (3 K_bar - 2 mu_bar) / 3 of the harmonic means (reuss_moduli: phi == 0 skipped, the first
+// phi == 1 alone, no threshold); a pair without a phase (the z padding) stores zeros.
+template <bool REUSS>
 __global__ __launch_bounds__(kBlock) void k_effective_moduli(long n2, PhaseTable pt, FieldPtrs<kMaxPhases> phi,
                                                              FieldPtrs<2> mod) {
   const double threshold = 10 * 2.220446049250313e-16;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long)gridDim.x * blockDim.x) {
     double2 A = make_double2(0.0, 0.0), B = make_double2(0.0, 0.0);
+    if constexpr (REUSS) {
+      double fx[kMaxPhases], fy[kMaxPhases];
+#pragma unroll
+      for (int p = 0; p < kMaxPhases; ++p) {
+        const double2 f = p < pt.n ? ld2(phi.p[p], 2 * i) : make_double2(0.0, 0.0);
+        fx[p] = f.x;
+        fy[p] = f.y;
+      }
+      double k3;
+      if (reuss_moduli<kMaxPhases>(fx, pt, &A.x, &k3)) B.x = (k3 - A.x) / 3;
+      if (reuss_moduli<kMaxPhases>(fy, pt, &A.y, &k3)) B.y = (k3 - A.y) / 3;
+      st2(mod.p[0], 2 * i, A);
+      st2(mod.p[1], 2 * i, B);
+      continue;
+    }
     for (int p = 0; p < pt.n; ++p) {
       const double2 f = ld2(phi.p[p], 2 * i);
       if (f.x > threshold) { A.x += 2 * f.x * pt.mu[p]; B.x += f.x * pt.lambda[p]; }
@@ -825,11 +860,12 @@ __global__ __launch_bounds__(kBlock) void k_effective_moduli(long n2, PhaseTable
 }  // namespace
 
 void launch_effective_moduli(const Grid& g, const PhaseTable& pt, const FieldPtrs<kMaxPhases>& phi, const FieldPtrs<2>& mod,
-                             hipStream_t s) {
+                             hipStream_t s, int mixing) {
   const long n2 = g.n / 2;
   long nb = (n2 + kBlock - 1) / kBlock;
   if (nb > 65536) nb = 65536;
-  hipLaunchKernelGGL(k_effective_moduli, dim3((unsigned)nb), dim3(kBlock), 0, s, n2, pt, phi, mod);
+  if (mixing == kMixReuss) hipLaunchKernelGGL(k_effective_moduli<true>, dim3((unsigned)nb), dim3(kBlock), 0, s, n2, pt, phi, mod);
+  else hipLaunchKernelGGL(k_effective_moduli<false>, dim3((unsigned)nb), dim3(kBlock), 0, s, n2, pt, phi, mod);
   FG_HIP_CHECK(hipGetLastError());
 }
 
@@ -882,7 +918,7 @@ void launch_tile(const Grid& g, int march_cus, MarchRule rule, size_t lds, int n
   FG_HIP_CHECK(hipGetLastError());
 }
 
-template <int TYR, int ZS, bool SUMT, bool PHI2 = false, bool CGP = false, int NMOD = 2, bool ANISO = false>
+template <int TYR, int ZS, bool SUMT, bool PHI2 = false, bool CGP = false, int NMOD = 2, bool ANISO = false, bool REUSS = false>
 void launch_u_tile_t(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& u, const FieldPtrs<NMOD>& mod,
                      const FieldPtrs<3>& f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s,
                      const std::conditional_t<ANISO, AnisoLin, PhaseLin>& lin = std::conditional_t<ANISO, AnisoLin, PhaseLin>{},
@@ -890,7 +926,7 @@ void launch_u_tile_t(const Grid& g, double mu_0, double lambda_0, const FieldPtr
   const size_t lds = (6 * TYR + (ANISO ? 6 : 0)) * TileShape<TYR, ZS>::RW * sizeof(double2);   // ANISO: two more rows of u per component
   const int nt = tile_nt(g, 3, 256.0);
   // (a sweep of fixed march lengths 3 ... 10 at 100^3 - 150^3: none beats march_length)
-  launch_tile<&k_u_tile<TYR, ZS, SUMT, PHI2, CGP, NMOD, ANISO>, TYR, ZS>(
+  launch_tile<&k_u_tile<TYR, ZS, SUMT, PHI2, CGP, NMOD, ANISO, REUSS>, TYR, ZS>(
       g, device_cu_count(), MarchRule::balanced, lds, SUMT ? 12 : 6, partial, sumsq6, s, [&](const TilePlan& p) {
         return std::make_tuple(g, -2 * mu_0, -lambda_0, u, mod, f, E, partial, p.nty, p.ntz, p.LX, nt, lin, cg);
       });
@@ -898,6 +934,13 @@ void launch_u_tile_t(const Grid& g, double mu_0, double lambda_0, const FieldPtr
 
 static PhaseLin make_phase_lin(const PhaseTable& pt, double mu_0, double lambda_0) {
   return PhaseLin{2 * pt.mu[0] - 2 * mu_0, 2 * (pt.mu[1] - pt.mu[0]), pt.lambda[0] - lambda_0, pt.lambda[1] - pt.lambda[0]};
+}
+
+// the reciprocals of the harmonic form (k_u_tile REUSS)
+static PhaseLin make_phase_lin_reuss(const PhaseTable& pt) {
+  const double a0 = 1 / (2 * pt.mu[0]), a1 = 1 / (2 * pt.mu[1]);
+  const double b0 = 1 / (2 * pt.mu[0] + 3 * pt.lambda[0]), b1 = 1 / (2 * pt.mu[1] + 3 * pt.lambda[1]);
+  return PhaseLin{a0, a1 - a0, b0, b1 - b0};
 }
 
 static CgDirection make_cg_direction(const FieldPtrs<3>& r, const FieldPtrs<3>& p_new, const double* sc, int i_num, int i_den,
@@ -916,10 +959,15 @@ static CgDirection make_cg_direction(const FieldPtrs<3>& r, const FieldPtrs<3>& 
 // of two complementary phases
 void launch_u_tile(const Grid& g, double mu_0, double lambda_0, const FieldPtrs<3>& u, const FieldPtrs<2>& mod,
                    const FieldPtrs<3>& f, const Vec6& E, double* partial, double* sumsq6, hipStream_t s,
-                   bool sum_tau, const PhaseTable* two_phase) {
+                   bool sum_tau, const PhaseTable* two_phase, bool reuss) {
+  if (reuss && !two_phase) throw std::logic_error("launch_u_tile: the harmonic form is the two-phase form");
   tile_shape_dispatch(g.nz / 2, [&](auto R, auto Z) {
     constexpr int TYR = decltype(R)::value, ZS = decltype(Z)::value;
-    if (two_phase) {
+    if (two_phase && reuss) {
+      const PhaseLin lin = make_phase_lin_reuss(*two_phase);
+      if (sum_tau) launch_u_tile_t<TYR, ZS, true, true, false, 2, false, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s, lin);
+      else launch_u_tile_t<TYR, ZS, false, true, false, 2, false, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s, lin);
+    } else if (two_phase) {
       const PhaseLin lin = make_phase_lin(*two_phase, mu_0, lambda_0);
       if (sum_tau) launch_u_tile_t<TYR, ZS, true, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s, lin);
       else launch_u_tile_t<TYR, ZS, false, true>(g, mu_0, lambda_0, u, mod, f, E, partial, sumsq6, s, lin);

@@ -18,7 +18,32 @@ constexpr double kVoigtThreshold = 10 * 2.220446049250313e-16;  // VoigtMixedMat
 
 // VoigtMixedMaterialLaw<.,.,3>::PK1  F:12752-12761 over ScalarLinearIsotropicMaterialLaw::PK1  F:11182-11198
 // for one component:  S (+)= E * ((phi * alpha) * mu), then  + beta * E  (calcStress  F:18160-18164).
+//
+// sp.mixing == kMixReuss: ReussMixedMaterialLaw<.,.,3>::PK1  F:12663-12689 over the same law (the scalar sibling of pk1_reuss,
+// fg_stage_math.h): a phase with phi == 0 is skipped, the first with phi == 1 (exact) answers alone, S = E * (alpha * mu), else
+// S = E * (alpha / sum_p (phi_p / mu_p)) over all phases with phi != 0 (no threshold); the 3 x 3 matrices the reference inverts
+// are multiples of the identity.
+__device__ __forceinline__ double sc_flux_reuss(const ScalarParams& sp, const double* ph, double g) {
+  double s = 0.0, mu_bar = 0.0;
+  bool any = false, pure = false;
+  for (int p = 0; p < sp.n; ++p) {
+    if (ph[p] == 0) continue;
+    if (ph[p] == 1) {
+      mu_bar = sp.mu[p];
+      pure = true;
+      break;
+    }
+    s += ph[p] / sp.mu[p];
+    any = true;
+  }
+  if (!pure) mu_bar = any ? 1 / s : 0.0;   // no phase: only padding gets here
+  double P = g * (sp.alpha * mu_bar);
+  if (sp.beta != 0) P += sp.beta * g;
+  return P;
+}
+
 __device__ __forceinline__ double sc_flux(const ScalarParams& sp, const double* ph, double g) {
+  if (sp.mixing == kMixReuss) return sc_flux_reuss(sp, ph, g);
   double P = 0.0;
   bool first = true;
   for (int p = 0; p < sp.n; ++p) {

@@ -607,6 +607,7 @@ void Solver::slab_reset_state() {
 void SlabGroup::check_members() const {
   if (m_.empty()) throw std::runtime_error("empty slab group");
   const Solver& a = *m_[0];
+  for (Solver* s : m_) s->reuss_check();   // mixing_rule reuss is refused on slabs
   if (a.opt_.gamma_scheme != 0) throw std::runtime_error("slab-decomposed solvers run the staggered Green operator");
   if (a.opt_.mode == 2 && (a.opt_.mixing != kMixVoigt || a.opt_.bc_relax != 1.0))
     throw std::runtime_error("viscosity mode supports Voigt mixing and bc_relax = 1 only");

@@ -99,6 +99,9 @@ struct SolverOptions {
   int phi_sweep = 1;            // two complementary phases: the tiled sweep reads phi_1 instead of the two moduli arrays
   int aniso_tile = 1;           // general (6 x 6 stiffness) phases, two complementary phases: the displacement loop on the tiled sweep's
                                 // anisotropic form (1) or the strain-state pass everywhere (0; also what every other case runs)
+  int reuss_sweep = 1;          // mixing_rule reuss, two complementary phases: the tiled sweep forms the harmonic means from phi_1
+                                // itself (1; 8 B per voxel less, one division per voxel more: the faster form) or
+                                // reads the two moduli arrays (0; also what every other case reads)
   int aniso_sc_tile = 1;        // heat / porous, two complementary phases with an aniso (3 x 3) phase: the potential loop on the tiled
                                 // sweep's aniso form (1) or the exact-order 13-point sweep everywhere (0; also what every other case runs)
   int laminate_overlap = 1;     // displacement loop with laminate mixing: interface kernels on a second stream beside the sweep
@@ -242,7 +245,8 @@ class Solver {
   double event_bias_ms() const { return event_bias_ms_; }
   // fg_get_counter: "interface_voxels" / "affected_voxels" = lengths of the laminate correction's lists (0 before they are
   // built); "sc_tile_aniso" = launches of k_sc_tile_aniso; "phase_uploads" = host arrays received by set_phase_field / set_phase_field_fine / set_normals; "u_tile_aniso" =
-  // launches of the tiled sweep's anisotropic form; "polarization_generic_voxels" = voxels that took the 6 x 6 solve in the last
+  // launches of the tiled sweep's anisotropic form; "u_tile_reuss" = launches of its in-sweep harmonic form (mixing_rule reuss, option
+  // reuss_sweep); "polarization_generic_voxels" = voxels that took the 6 x 6 solve in the last
   // forward launch of the polarisation kernel (waits for the stream); -1 = unknown name
   long counter(const std::string& name) const;
 
@@ -304,6 +308,8 @@ class Solver {
   void sc_aniso_constants(double* K0, double* K1) const;   // the six constants of phases 0 and 1 (isotropic: mu on the diagonal)
   bool two_phase_complementary(bool scalar = false);       // phi_0 == 1 - phi_1 everywhere (checked once per geometry)
   void general_check() const;           // throws for the combinations general phases do not cover
+  void reuss_check() const;             // throws for the combinations mixing_rule reuss does not cover, each naming the option
+  bool reuss_sweep_ok();                // Reuss mixing: the tiled sweep forms the moduli from phi_1 (k_u_tile REUSS)
   // method polarization (fg_solver.hip, "the polarisation loop")
   void polar_check() const;             // throws for the combinations the method does not cover, each naming the option
   void polar_start(const double* E6);   // P = 4 mu_0 E, the constant field the loop starts from  F:21828
@@ -457,6 +463,7 @@ class Solver {
   double *lam_phic_ = nullptr, *lam_nrmc_ = nullptr, *lam_epsc_ = nullptr;
   double* mod_ = nullptr;      // 2: per-voxel effective moduli (sum phi 2 mu, sum phi lambda) of the fast sweep
   bool mod_dirty_ = true;
+  int mod_rule_ = kMixVoigt;   // the rule mod_ was filled with (kMixVoigt / kMixReuss): another one refills it
   double* phis_ = nullptr;     // gamma_scheme 2: [nphase][3] shear-group fractions phi^(23), phi^(13), phi^(12)
   unsigned fine_set_ = 0;      // phases whose phis_ came from a fine image (the others are built from phi_ as replicas)
   long phase_uploads_ = 0;     // host-array phase / normal uploads (voxelize_into adds none)
@@ -467,6 +474,7 @@ class Solver {
   double sc_K_[kMaxPhases][6];     // and the six constants of an aniso phase
   long sc_tile_aniso_ = 0;  // launches of the tiled scalar sweep's aniso form (fg_get_counter "sc_tile_aniso")
   long u_tile_aniso_ = 0;   // launches of the tiled sweep's anisotropic form (fg_get_counter "u_tile_aniso")
+  long u_tile_reuss_ = 0;   // launches of the tiled sweep's in-sweep harmonic form (fg_get_counter "u_tile_reuss")
   double* fu_alt_ = nullptr;   // 3: second f/u buffer of the displacement-based loop (swapped with fu_)
   double* phi_ = nullptr;      // nphase
   double* normals_ = nullptr;  // 3 (allocated on demand)

@@ -590,7 +590,7 @@ void Solver::fetch_norms_and_errors(const char* where) {
   static_assert(kSlotMean == kSlotSumSq + 6, "the displacement sweep writes norms and tau sums as one block of 12");
   const bool mixed_u = pending_back_ && mixed_bc();
   const int nfetch = mixed_u ? 12 : 6;
-  const int n2 = (mixed_u && opt_.mixing != kMixVoigt) ? 6 : 0;   // mixed BC + laminate: + sums of the interface differences
+  const int n2 = (mixed_u && opt_.mixing == kMixLaminate) ? 6 : 0;   // mixed BC + laminate: + sums of the interface differences
   {
     // one tiny kernel publishes sums + error flag + sequence number in pinned host memory; the host spins on the number
     const unsigned seq = ++publish_seq_;
@@ -678,6 +678,7 @@ long Solver::counter(const std::string& name) const {
   if (name == "affected_voxels") return mixed_dirty_ ? 0 : (long)aff_n_;
   if (name == "phase_uploads") return phase_uploads_;
   if (name == "u_tile_aniso") return u_tile_aniso_;
+  if (name == "u_tile_reuss") return u_tile_reuss_;
   if (name == "sc_tile_aniso") return sc_tile_aniso_;
   if (name == "polarization_generic_voxels") {   // left on the device by the last forward launch of k_polarize
     double v = 0.0;
@@ -716,6 +717,7 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
   if (nranks_ != 1) throw std::runtime_error("basic_scheme: slab solvers run under the slab driver (fg_slab.hip)");
   if (pt_.n < 1) throw std::runtime_error("No materials specified");
   if (opt_.mixing == kMixLaminate && !normals_) throw std::runtime_error("laminate mixing needs interface normals");
+  reuss_check();
   if (dfg()) dfg_check();
   if (willot()) willot_check();
   general_check();
@@ -727,7 +729,7 @@ void Solver::basic_scheme(const double* E6, double* src, double* dst) {
   }
   if (opt_.mode == 2) {
     if (opt_.gamma_scheme == 1) throw std::runtime_error("viscosity mode supports gamma_scheme staggered, full_staggered and willot only");
-    if (opt_.mixing != kMixVoigt) throw std::runtime_error("viscosity mode supports Voigt mixing only");
+    if (opt_.mixing == kMixLaminate) throw std::runtime_error("viscosity mode supports Voigt and Reuss mixing only");
     if (opt_.bc_relax != 1.0) throw std::runtime_error("viscosity mode supports bc_relax = 1 only");
   }
   if (willot()) willot_scheme(E6, src, dst);
@@ -774,7 +776,8 @@ void Solver::pass_viscosity(const double* E6, double* src, double* dst) {
   const double m = 1 / (4 * opt_.mu_0);
   const StressParams sp = stress_params(opt_.mu_0, opt_.lambda_0, 1.0);
   // full_staggered: the fused form exists as the tiled sweep only (other grids store the polarisation)
-  const bool fused = opt_.fuse_stress_div != 0 && (!dfg() || (opt_.u_loop >= 2 && u_tile_supported(g_)));
+  // (Reuss mixing: the fused forms re-evaluate the Voigt rule from the phase fractions in their tail sweep -- the stored form)
+  const bool fused = opt_.fuse_stress_div != 0 && opt_.mixing != kMixReuss && (!dfg() || (opt_.u_loop >= 2 && u_tile_supported(g_)));
   if (fused) {
     // the polarisation is a point-wise function of the strain: it is evaluated inside the divergence sweep (with its
     // six sums) and again in the tail sweep, and never stored
@@ -888,7 +891,8 @@ void Solver::pass_staggered(const double* E6, double* src, double* dst) {
   const bool fuse_sd = opt_.fuse_stress_div && opt_.mixing == kMixVoigt && !mixed && !dfg() && !general_phase();
   // with the fast kernels allowed (u_loop = 2) the LDS-tiled form takes over where the grid fits; it also delivers
   // the sums of tau, so mixed boundary conditions keep the fused sweep
-  const bool tile_sd = opt_.fuse_stress_div && opt_.mixing == kMixVoigt && opt_.u_loop >= 2 && u_tile_supported(g_) && !general_phase();
+  // (the tiled form reads the moduli arrays: it serves the Reuss rule as well, fuse_sd evaluates the Voigt rule from the phases)
+  const bool tile_sd = opt_.fuse_stress_div && opt_.mixing != kMixLaminate && opt_.u_loop >= 2 && u_tile_supported(g_) && !general_phase();
   if (tile_sd) {
     time_begin(0);
     if (dfg())
@@ -1086,6 +1090,7 @@ ScalarParams Solver::scalar_params(double mu_0, double alpha) const {
   }
   sp.alpha = alpha;
   sp.beta = -alpha * 2 * mu_0;  // calcStress  F:18138
+  sp.mixing = opt_.mixing;
   return sp;
 }
 
@@ -1105,7 +1110,7 @@ bool Solver::u_loop_eligible(bool allow_mixed_bc) {
   if (opt_.mode == 1) {
     // the scalar modes only have the potential-based loop
     if (nranks_ != 1) throw std::runtime_error("heat / porous mode is not available on slab-decomposed solvers");
-    if (opt_.mixing != kMixVoigt) throw std::runtime_error("heat / porous mode supports Voigt mixing only");
+    if (opt_.mixing == kMixLaminate) throw std::runtime_error("heat / porous mode supports Voigt and Reuss mixing only");
     if (opt_.bc_relax != 1.0) throw std::runtime_error("heat / porous mode does not support bc_relax != 1");
     if (mixed_bc() && !allow_mixed_bc)
       throw std::runtime_error("heat / porous mode: mixed boundary conditions run with method=basic (fg_run_load_case) only");
@@ -1118,12 +1123,12 @@ bool Solver::u_loop_eligible(bool allow_mixed_bc) {
   const bool scheme_ok = opt_.gamma_scheme == 0 ||
                          (dfg() && opt_.mixing == kMixVoigt && opt_.u_loop >= 2 && opt_.u_tile && u_tile_supported(g_));
   if (!(opt_.u_loop && opt_.mode == 0 && scheme_ok && nranks_ == 1 && pt_.n >= 1 &&
-        (opt_.mixing == kMixVoigt || (opt_.mixing == kMixLaminate && normals_)) && opt_.bc_relax == 1.0))
+        (opt_.mixing != kMixLaminate || normals_) && opt_.bc_relax == 1.0))
     return false;
   if (!mixed_bc()) return true;
   // mixed boundary conditions: <tau> of every pass corrects the prescribed mean of the next one; the tiled Voigt sweep
   // delivers it with the norms (run() only: the correction needs the host between passes)
-  return allow_mixed_bc && opt_.u_loop >= 2 && opt_.u_tile && u_tile_supported(g_);   // Voigt, or laminate as its correction
+  return allow_mixed_bc && opt_.u_loop >= 2 && opt_.u_tile && u_tile_supported(g_);   // Voigt / Reuss, or laminate as the Voigt sweep's correction
 }
 
 // Two phases whose fractions are complementary bit for bit (phi_0 == 1 - phi_1: what normalizePhi leaves for two
@@ -1144,7 +1149,8 @@ bool Solver::two_phase_complementary(bool scalar) {
   return complementary_;
 }
 
-// A = sum_p phi_p 2 mu_p, B = sum_p phi_p lambda_p per voxel (k_effective_moduli), computed once per geometry
+// A = sum_p phi_p 2 mu_p, B = sum_p phi_p lambda_p per voxel (k_effective_moduli; Reuss mixing: 2 mu_bar, lambda_bar of the harmonic
+// means), computed once per geometry and rule
 FieldPtrs<2> Solver::effective_moduli() {
   if (general_phase() || aniso_phase())
     throw std::logic_error("effective moduli (sum phi 2 mu, sum phi lambda) do not exist with a general or an aniso phase");
@@ -1155,12 +1161,15 @@ FieldPtrs<2> Solver::effective_moduli() {
   FieldPtrs<2> mod;
   mod.p[0] = mod_;
   mod.p[1] = mod_ + g_.n;
+  const int rule = opt_.mixing == kMixReuss ? kMixReuss : kMixVoigt;   // (laminate: the Voigt sweep + its correction)
+  if (rule != mod_rule_) mod_dirty_ = true;   // the rule changed on a live solver
   if (mod_dirty_) {
     PhaseTable t = phase_table();
-    if (opt_.mode == 1)   // scalar modes: k_effective_moduli stores sum phi 2 mu, the sweep wants sum phi mu
+    if (opt_.mode == 1)   // scalar modes: k_effective_moduli stores sum phi 2 mu (its harmonic mean), the sweep wants that of mu
       for (int q = 0; q < kMaxPhases; ++q) t.mu[q] = 0.5 * pt_.mu[q], t.lambda[q] = 0.0;
-    launch_effective_moduli(g_, t, phase_ptrs(), mod, stream_);
+    launch_effective_moduli(g_, t, phase_ptrs(), mod, stream_, rule);
     mod_dirty_ = false;
+    mod_rule_ = rule;
   }
   return mod;
 }
@@ -1178,6 +1187,38 @@ void Solver::general_check() const {
     throw std::runtime_error("general (anisotropic) phases support Voigt mixing only (the laminate split is written for isotropic phases)");
   if (dfg()) throw std::runtime_error("general (anisotropic) phases are not available with gamma_scheme full_staggered / half_staggered");
   if (nranks_ != 1 || slab_layout_) throw std::runtime_error("general (anisotropic) phases are not available on slab-decomposed solvers");
+}
+
+// mixing_rule reuss (ReussMixedMaterialLaw F:12651-12724): isotropic phases in all four modes, gamma_scheme staggered /
+// collocated / willot, methods basic and cg, estimators epsilon / residual / sigma / none, one GPU
+void Solver::reuss_check() const {
+  if (opt_.mixing != kMixReuss) return;
+  if (general_phase())
+    throw std::runtime_error("general (anisotropic) phases support Voigt mixing only (the laminate split is written for isotropic phases)");
+  if (aniso_phase())
+    throw std::runtime_error("mixing_rule reuss is not available with aniso (3 x 3 conductivity) phases (the harmonic mean is "
+                             "written for isotropic phases)");
+  if (dfg())
+    throw std::runtime_error("mixing_rule reuss is not available with gamma_scheme full_staggered / half_staggered (the five "
+                             "moduli of the doubly fine grid are arithmetic means)");
+  if (opt_.method == 2) throw std::runtime_error("method polarization supports mixing_rule voigt only (not laminate)");
+  if (opt_.error_estimator == 3)
+    throw std::runtime_error("error_estimator energy is not available with mixing_rule reuss (Reuss MaterialLaw energy not implemented)");
+  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("mixing_rule reuss is not available on slab-decomposed solvers");
+  for (int p = 0; p < pt_.n; ++p) {
+    const bool bad = opt_.mode == 0 ? !(2 * pt_.mu[p] > 0 && 2 * pt_.mu[p] + 3 * pt_.lambda[p] > 0) : !(pt_.mu[p] > 0);
+    if (bad)
+      throw std::runtime_error(opt_.mode == 0 ? "mixing_rule reuss needs 2 mu > 0 and 2 mu + 3 lambda > 0 in every phase (the "
+                                                "inversion of the phase stiffness fails otherwise)"
+                                              : "mixing_rule reuss needs mu > 0 in every phase (the inversion of the phase "
+                                                "constant fails otherwise)");
+  }
+}
+
+// the tiled sweep of two complementary phases forms the harmonic means itself (k_u_tile REUSS); option reuss_sweep = 0: the
+// two moduli arrays (A/B runs)
+bool Solver::reuss_sweep_ok() {
+  return opt_.reuss_sweep && opt_.mixing == kMixReuss && opt_.mode == 0 && two_phase_complementary();
 }
 
 bool Solver::aniso_tile_ok() {
@@ -1300,7 +1341,7 @@ void Solver::u_pass_front(const double* E6) {
       launch_sc_sweep(g_, scalar_params(opt_.mu_0, 1.0), fu_, phase_ptrs(), fu_alt_, E, partial_, dscal_ + kSlotSumSq, stream_);
     }
   } else if (opt_.mixing != kMixVoigt && opt_.u_loop < 2) {
-    // laminate mixing, exact order: strain + polarisation from u in one sweep (tau stored), divergence as its own sweep
+    // laminate / Reuss mixing, exact order: strain + polarisation from u in one sweep (tau stored), divergence as its own sweep
     launch_u_stress(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs3(fu_), phi, normal_ptrs(), ptrs6(tau_), E, partial_,
                     dscal_ + kSlotSumSq, derr_, stream_);
     time_end(0);
@@ -1312,7 +1353,7 @@ void Solver::u_pass_front(const double* E6) {
   } else if (opt_.u_loop >= 2) {
     // fast variant: per-voxel effective moduli instead of the per-phase accumulation (computed once per geometry, on
     // first use: the tiled sweep of two complementary phases does without them)
-    const bool laminate = opt_.mixing != kMixVoigt;
+    const bool laminate = opt_.mixing == kMixLaminate;
     if (laminate) {
       build_laminate_lists();
       if (opt_.laminate_overlap) {   // fork: u_k is complete, the previous pass is done with d
@@ -1335,14 +1376,16 @@ void Solver::u_pass_front(const double* E6) {
         launch_u_tile_aniso(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), phi_ + g_.n, ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq,
                             stream_, sum_tau, phase_table());
         ++u_tile_aniso_;
-      } else if (two_phase_complementary()) {
+      } else if (opt_.mixing == kMixReuss ? reuss_sweep_ok() : two_phase_complementary()) {
         // two phases with phi_0 = 1 - phi_1: the sweep reads phi_1 and forms the moduli itself (8 B per voxel less)
         FieldPtrs<2> ph;
         ph.p[0] = phi_ + g_.n;
         ph.p[1] = nullptr;
         const PhaseTable t = phase_table();
+        const bool reuss = opt_.mixing == kMixReuss;
         launch_u_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), ph, ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq, stream_, sum_tau,
-                      &t);
+                      &t, reuss);
+        if (reuss) ++u_tile_reuss_;
       } else {
         launch_u_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), effective_moduli(), ptrs3(fu_alt_), E, partial_,
                       dscal_ + kSlotSumSq, stream_, sum_tau);
@@ -1403,6 +1446,7 @@ void Solver::ensure_eps() {
 
 void Solver::iterate(const double* E6, int n) {
   FG_HIP_CHECK(hipSetDevice(device_));
+  reuss_check();
   if (dfg()) dfg_check();
   if (willot()) willot_check();
   general_check();
@@ -1467,6 +1511,7 @@ double Solver::mean_energy() {
   ensure_eps();
   if (pt_.n < 1) throw std::runtime_error("No materials specified");
   if (opt_.mode == 1) throw std::runtime_error("the energy error estimator is not available in heat / porous mode");
+  if (opt_.mixing == kMixReuss) throw std::runtime_error("Reuss MaterialLaw energy not implemented");   // F:12657-12661
   if (dfg())
     launch_dfg_stress(2, g_, stress_params(0.0, 0.0, 1.0), ptrs6(eps_), dfg_moduli(), FieldPtrs<6>{}, partial_, dscal_ + kSlotMean,
                       stream_);
@@ -1522,6 +1567,7 @@ double Solver::volume_fraction(int p) {
 void Solver::calc_ref_material() {
   FG_HIP_CHECK(hipSetDevice(device_));
   if (pt_.n < 1) throw std::runtime_error("No materials specified");
+  reuss_check();
   general_check();
   if (opt_.mode == 1)
     launch_sc_minmax(g_, scalar_params(0.0, 1.0), phase_ptrs(), partial_, dscal_ + kSlotMinMax, stream_);
@@ -1752,6 +1798,7 @@ bool Solver::run_load_steps(const double* E6, const double* S6, const double* pa
 
 // runSolver  F:21400-21433 for one load step
 bool Solver::run_one_step(const double* E0, const double* S0) {
+  reuss_check();
   if (dfg()) dfg_check();
   if (willot()) willot_check();
   general_check();
@@ -1843,7 +1890,7 @@ bool Solver::run_one_step(const double* E0, const double* S0) {
       for (int c = 0; c < 6; ++c) F0[c] = hscal_[kSlotMean + c] / (double)nglobal_;
       if (opt_.mode == 1)   // components 3..5 do not exist; the flux-mean sweep has divided by N already, the tiled sweep has not
         for (int c = 0; c < 6; ++c) F0[c] = c < 3 ? hscal_[kSlotMean + c] / (sc_tau_sums_ ? (double)nglobal_ : 1.0) : 0.0;
-      if (opt_.mixing != kMixVoigt)
+      if (opt_.mixing == kMixLaminate)
         for (int c = 0; c < 6; ++c) F0[c] += hscal_[kSlotScratch + c] / (double)nglobal_;
       voigt_mv(BC_MQ_, F0, t1);
       for (int c = 0; c < 6; ++c) E_next_[c] = E[c] - t1[c];   // alpha = -1  (F:20575)
@@ -1990,7 +2037,7 @@ bool Solver::run_cg_u(const double* E0, double prev0) {
     const size_t need = (cg_p_ ? 0 : 2 * f3) + (fu_cg_ ? 0 : f3);
     if (free_b < need + (size_t)(0.02 * (double)total_b)) fused = false;
   }
-  const bool fused_dir = fused && opt_.mixing == kMixVoigt;   // laminate mixing: the interface kernels read u_p as a stored field
+  const bool fused_dir = fused && opt_.mixing != kMixLaminate;   // laminate mixing: the interface kernels read u_p as a stored field
   double *r_alt = nullptr, *p_alt = nullptr;
   if (fused) {
     if (!cg_p_) FG_HIP_CHECK(hipMalloc(&cg_p_, 2 * f3));
@@ -2030,7 +2077,7 @@ bool Solver::run_cg_u(const double* E0, double prev0) {
       std::swap(u_p, p_alt);
       return;
     }
-    const bool two = two_phase_complementary();
+    const bool two = opt_.mixing != kMixReuss && two_phase_complementary();   // (Reuss mixing: the CG sweep reads the moduli arrays)
     if (two) {
       m.p[0] = phi_ + g_.n;
       m.p[1] = nullptr;

@@ -34,7 +34,7 @@ FG_HD bool any_general_phase(const PhaseTable& pt) {
   return g;
 }
 
-enum MixingRule { kMixVoigt = 0, kMixLaminate = 1 };
+enum MixingRule { kMixVoigt = 0, kMixLaminate = 1, kMixReuss = 2 };
 
 // LinearIsotropicMaterialLaw::PK1  F:11375-11396  (gamma = accumulate)
 FG_HD void hooke6(const double* E, double mu, double lambda, double alpha, bool accumulate, double* S) {
@@ -84,6 +84,63 @@ FG_HD void pk1_voigt(const double* F, const double* phi, const PhaseTable& pt, d
   if (!any) {
     for (int i = 0; i < 6; ++i) P[i] = 0.0;  // reference leaves P untouched; only padding gets here
   }
+}
+
+// ReussMixedMaterialLaw::PK1  F:12663-12689 for isotropic phases: a phase with phi == 0 is skipped, the first phase with
+// phi == 1 (exact) answers alone with its own law (the bits of a pure voxel under the Voigt rule), otherwise
+// P = alpha (sum_p phi_p C_p^-1)^-1 F over all phases with phi != 0 -- no 10 eps threshold, that is the Voigt rule's.  The
+// reference inverts the 6 x 6 matrices with gesv; isotropic tensors share their eigenspaces, so the inverse sum is taken on the
+// two eigenvalues: 2 mu_bar = 1 / sum(phi_p / 2 mu_p), 3 K_bar = 1 / sum(phi_p / (2 mu_p + 3 lambda_p)) (equal to rounding).
+// reuss_moduli returns false when no phase takes part (padding).
+template <int NPH>
+FG_HD bool reuss_moduli(const double* phi, const PhaseTable& pt, double* two_mu, double* three_k) {
+  double sa = 0.0, sk = 0.0;
+  bool any = false;
+#pragma unroll
+  for (int p = 0; p < NPH; ++p) {
+    if (p >= pt.n) break;
+    const double f = phi[p];
+    if (f == 0) continue;
+    const double tm = 2 * pt.mu[p], tk = 2 * pt.mu[p] + 3 * pt.lambda[p];
+    if (f == 1) {
+      *two_mu = tm;
+      *three_k = tk;
+      return true;
+    }
+    sa += f / tm;
+    sk += f / tk;
+    any = true;
+  }
+  if (!any) return false;
+  *two_mu = 1 / sa;
+  *three_k = 1 / sk;
+  return true;
+}
+
+template <int NPH>
+FG_HD void pk1_reuss(const double* F, const double* phi, const PhaseTable& pt, double alpha, bool gamma, double* P) {
+  double sa = 0.0, sk = 0.0;
+  bool any = false;
+#pragma unroll
+  for (int p = 0; p < NPH; ++p) {
+    if (p >= pt.n) break;
+    const double f = phi[p];
+    if (f == 0) continue;
+    if (f == 1) {
+      hooke6(F, pt.mu[p], pt.lambda[p], alpha, gamma, P);
+      return;
+    }
+    sa += f / (2 * pt.mu[p]);
+    sk += f / (2 * pt.mu[p] + 3 * pt.lambda[p]);
+    any = true;
+  }
+  if (!any) {
+    if (!gamma)
+      for (int i = 0; i < 6; ++i) P[i] = 0.0;  // only padding gets here
+    return;
+  }
+  const double two_mu = 1 / sa, three_k = 1 / sk;
+  hooke6(F, 0.5 * two_mu, (three_k - two_mu) / 3, alpha, gamma, P);
 }
 
 // 9-component index maps  F:13186-13188  (11,22,33,23,13,12,32,31,21)
@@ -246,6 +303,7 @@ template <int NPH>
 FG_HD int stress_voxel(const double* F, const double* phi, const double* normal, const StressParams& sp, double* P) {
   int err = 0;
   if (sp.mixing == kMixLaminate) err = pk1_laminate<NPH>(F, phi, normal, sp.pt, sp.alpha, false, sp.eps_g, sp.eps_a, P);
+  else if (sp.mixing == kMixReuss) pk1_reuss<NPH>(F, phi, sp.pt, sp.alpha, false, P);
   else pk1_voigt<NPH>(F, phi, sp.pt, sp.alpha, false, P);
   const double beta = -sp.alpha * 2 * sp.mu_0;
   const double gamma = -sp.alpha * sp.lambda_0;
@@ -309,7 +367,8 @@ FG_HD double voigt_tau_shear(double Ec, const double* phi, const StressParams& s
 // (getRefMaterial/eig  F:12153-12236, F:12472-12559).  For isotropic phases the
 // Voigt tangent (F:12763-12771) and the laminate tangent="approx" (F:13611-13624)
 // are isotropic: diag block 2mu I + lam 11^T, shear block 2mu I, eigenvalues
-// {2mu (x5), 2mu + 3 lam}.  (The reference obtains them with LAPACK dsyev.)
+// {2mu (x5), 2mu + 3 lam}.  (The reference obtains them with LAPACK dsyev.)  The Reuss tangent (F:12691-12718) is isotropic as
+// well, with the harmonic means of the two eigenvalues (reuss_moduli).
 //
 // GENERAL (a phase with a constant stiffness is present, Voigt mixing): the tangent sum_p phi_p C_p is no longer isotropic.
 // The reference hands dsyev the 6 x 6 matrix dPK1 fills from the identity rows (F:12518-12522, F:9068-9075, F:11274-11298):
@@ -320,6 +379,13 @@ FG_HD void jacobi_minmax6(double (&A)[6][6], double* emin, double* emax);
 template <int NPH, bool GENERAL = false>
 FG_HD int tangent_eigs(const double* phi, const PhaseTable& pt, int mixing, double* emin, double* emax) {
   double two_mu = 0.0, lam = 0.0;
+  if (mixing == kMixReuss) {
+    double e1 = 0.0, e2 = 0.0;   // a voxel without a phase scans as zero, as under the Voigt rule
+    (void)reuss_moduli<NPH>(phi, pt, &e1, &e2);
+    *emin = e1 < e2 ? e1 : e2;
+    *emax = e1 < e2 ? e2 : e1;
+    return 0;
+  }
   if (mixing == kMixLaminate) {
     LaminateMix m;
     if (laminate_select<NPH>(phi, pt.n, m) != 0) return 1;

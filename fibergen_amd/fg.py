@@ -28,7 +28,7 @@ import os
 import numpy as np
 
 from . import materials as _materials
-from .solver import METHODS, POLARIZATION_ERRORS, LSSolver
+from .solver import METHODS, MIXING, POLARIZATION_ERRORS, REUSS_ERRORS, LSSolver
 from .xmlproject import XMLProject
 
 log = logging.getLogger("fibergen_amd")
@@ -296,10 +296,12 @@ class FG:
                 raise RuntimeError("error estimator 'div_sigma' is not available (a stub in the reference: it stops after one iteration)")
             raise RuntimeError("Unknown error estimator '%s'" % est)
         mixing = self._child_value(solver, "mixing_rule", "voigt", str)
-        if mixing not in ("voigt", "laminate"):
+        if mixing not in MIXING:
             raise RuntimeError("Unknown mixing rule '%s'" % mixing)
-        if scalar and mixing != "voigt":
-            raise RuntimeError("mixing rule '%s' is not available in %s mode (voigt only)" % (mixing, mode))
+        if scalar and mixing == "laminate":
+            raise RuntimeError("mixing rule '%s' is not available in %s mode (voigt and reuss only)" % (mixing, mode))
+        if mixing == "reuss":
+            self._check_reuss(solver, mode, method, dfg, est)
         if dfg and mixing != "voigt":
             raise RuntimeError("gamma scheme '%s' is not available with mixing rule '%s' on the MI355X path (voigt only: the "
                                "laminate split is not linear in phi)" % (scheme, mixing))
@@ -430,6 +432,35 @@ class FG:
         self._matrix_mat = matrix_mat
         self._mixing = mixing
         self._solver_valid = True
+
+    def _check_reuss(self, solver, mode, method, dfg, est):
+        """mixing_rule reuss (ReussMixedMaterialLaw F:12651-12724): what it does not cover is refused before a solver exists, in
+        the wording of the solver library (Solver::reuss_check)"""
+        mats = solver.find("materials") if solver is not None else None
+        phases = [m for m in (mats if mats is not None else []) if isinstance(m.tag, str) and m.tag != "ref"]
+        laws = [m.attrib.get("law", "iso") for m in phases]
+        if "general" in laws:
+            raise RuntimeError(REUSS_ERRORS["general"])
+        if "aniso" in laws and mode in ("heat", "porous"):
+            raise RuntimeError(REUSS_ERRORS["aniso"])
+        if dfg:
+            raise RuntimeError(REUSS_ERRORS["dfg"])
+        if method == "polarization":
+            raise RuntimeError(REUSS_ERRORS["method"])
+        if est == "energy":
+            raise RuntimeError(REUSS_ERRORS["estimator"])
+        if getattr(self, "_slabs", False):
+            raise RuntimeError(REUSS_ERRORS["slab"])
+        for m, law in zip(phases, laws):
+            if law != "iso":
+                continue   # (an unknown law is reported as such where the materials are read)
+            if mode != "elasticity":
+                if not self._eval(m.attrib.get("mu", "1")) > 0:
+                    raise RuntimeError(REUSS_ERRORS["constant"])
+            else:
+                c = _materials.material_constants(dict(m.attrib), self._eval)
+                if not (2 * c["mu"] > 0 and 2 * c["mu"] + 3 * c["lambda"] > 0):
+                    raise RuntimeError(REUSS_ERRORS["moduli"])
 
     def _set_phase(self, lss, p, phi=None):
         """phase p's constants (and field) into the solver: (mu, lambda), the stiffness of a law="general" material, or the

@@ -12,7 +12,8 @@ import numpy as np
 
 from . import _lib
 
-MIXING = {"voigt": 0, "laminate": 1}
+# mixing_rule option values (create_mixing_rule F:15013): reuss = ReussMixedMaterialLaw F:12651-12724, the harmonic mean
+MIXING = {"voigt": 0, "laminate": 1, "reuss": 2}
 
 # method option values: runBasic F:21716, runCGElasticity F:23153, runPolarization F:21808 (the Eyre-Milton scheme); the
 # reference's "basic+el" and "nesterov" are experiments and stay unknown here
@@ -28,6 +29,21 @@ POLARIZATION_ERRORS = {
                   "the loop's field is the polarisation, not the strain)"),
     "bc": ("method polarization supports pure-strain boundary conditions only (bc_projector = identity; the "
            "reference switches the mixed check off)"),
+}
+
+# what mixing_rule reuss does not cover, in the wording of the solver library (Solver::reuss_check)
+REUSS_ERRORS = {
+    "general": "general (anisotropic) phases support Voigt mixing only (the laminate split is written for isotropic phases)",
+    "aniso": ("mixing_rule reuss is not available with aniso (3 x 3 conductivity) phases (the harmonic mean is written for "
+              "isotropic phases)"),
+    "dfg": ("mixing_rule reuss is not available with gamma_scheme full_staggered / half_staggered (the five moduli of the "
+            "doubly fine grid are arithmetic means)"),
+    "method": POLARIZATION_ERRORS["mixing"],
+    "estimator": "error_estimator energy is not available with mixing_rule reuss (Reuss MaterialLaw energy not implemented)",
+    "slab": "mixing_rule reuss is not available on slab-decomposed solvers",
+    "moduli": ("mixing_rule reuss needs 2 mu > 0 and 2 mu + 3 lambda > 0 in every phase (the inversion of the phase stiffness "
+               "fails otherwise)"),
+    "constant": "mixing_rule reuss needs mu > 0 in every phase (the inversion of the phase constant fails otherwise)",
 }
 
 # gamma_scheme option values; full_staggered and half_staggered are the staggered operator with the material evaluated on
@@ -179,7 +195,7 @@ class LSSolver:
                 if v not in kinds:
                     raise RuntimeError("Unknown error estimator '%s'" % v)
                 self._check(self._lib.fg_set_option_i(self._h, b"error_estimator", kinds[v]))
-            elif k in ("u_loop", "fuse_x", "cg_fused", "fuse_stress_div", "u_tile", "x_layout", "plane_fft", "slab_split", "slab_interleave", "slab_loopback", "laminate_overlap", "phi_sweep", "aniso_tile", "aniso_sc_tile", "pair_chunk", "joint_x", "fft_images", "bluestein", "tile_plans", "staged_copy", "stage_chunk_kb"):
+            elif k in ("u_loop", "fuse_x", "cg_fused", "fuse_stress_div", "u_tile", "x_layout", "plane_fft", "slab_split", "slab_interleave", "slab_loopback", "laminate_overlap", "phi_sweep", "aniso_tile", "reuss_sweep", "aniso_sc_tile", "pair_chunk", "joint_x", "fft_images", "bluestein", "tile_plans", "staged_copy", "stage_chunk_kb"):
                 self._check(self._lib.fg_set_option_i(self._h, k.encode(), int(v)))
             elif k in ("maxiter", "loadstep_extrapolation_order"):
                 self._check(self._lib.fg_set_option_i(self._h, k.encode(), int(v)))

@@ -33,6 +33,7 @@ extern "C" {
 /* mixing_rule option values (F:15129, create_mixing_rule) */
 #define FG_MIXING_VOIGT 0
 #define FG_MIXING_LAMINATE 1
+#define FG_MIXING_REUSS 2   /* ReussMixedMaterialLaw F:12651-12724: the harmonic mean (sum_p phi_p C_p^-1)^-1 of a composite voxel */
 
 /* stages of one basic-scheme pass, for fg_run_stage (each is one reference routine) */
 #define FG_STAGE_STRESS 0        /* calcStressDiff            F:18030-18033, F:18134-18184 : epsilon -> tau   */
@@ -101,7 +102,12 @@ int fg_set_normals(fg_solver* s, const double* normals /* [3][nx][ny][nz] */);
 
 /* Solver settings of readSettings  F:15046-15094.  Keys (double): tol, abs_tol, bc_tol,
  * ref_scale, bc_relax, mu_0, lambda_0 (the <ref> material), eps_g, eps_a (<laminate_mixing>).
- * Keys (integer): maxiter, mixing_rule (FG_MIXING_*), update_ref (0 = "never"), mode (0 = elasticity, 1 = heat /
+ * Keys (integer): maxiter, mixing_rule (FG_MIXING_*; FG_MIXING_REUSS: isotropic phases in all four modes, gamma_scheme
+ * staggered / collocated / willot, methods basic and cg, estimators epsilon / residual / sigma / none, mixed boundary conditions,
+ * load steps, one GPU -- a phase with phi == 0 is skipped, the first with phi == 1 answers alone, every other fraction takes part
+ * (no 10 eps threshold); general and aniso phases, full_staggered / half_staggered, method polarization, estimator energy
+ * ("Reuss MaterialLaw energy not implemented"), slab-decomposed solvers and a phase with 2 mu <= 0, 2 mu + 3 lambda <= 0 or, in
+ * the scalar modes, mu <= 0 are refused by name when the run or the reference-material scan starts), update_ref (0 = "never"), mode (0 = elasticity, 1 = heat /
  * porous F:15224-15228: fields "epsilon" / "sigma" have 3 components (gradient, flux), "u" one (the potential); mu of
  * fg_set_phase is the conductivity; E6 / S6 / out6 arrays carry 3 values followed by zeros; Voigt mixing, basic scheme;
  * 2 = viscosity F:15234-15239: dual Stokes scheme DeltaOperatorStaggered F:20422-20460, mu of fg_set_phase is the
@@ -150,7 +156,9 @@ int fg_set_normals(fg_solver* s, const double* normals /* [3][nx][ny][nz] */);
  * phi_sweep (1 = default: with two phases whose fractions are complementary bit for bit the tiled sweep reads phi_1 and
  * forms the effective moduli itself; 0 = always the two precomputed moduli arrays), aniso_tile (1 = default: two complementary
  * phases with a general phase -- fg_set_phase_stiffness -- run the displacement loop on the tiled sweep's 6 x 6 form where
- * u_tile, phi_sweep and the grid allow; 0 = the strain-state pass), aniso_sc_tile (1 = default: heat / porous with two complementary
+ * u_tile, phi_sweep and the grid allow; 0 = the strain-state pass), reuss_sweep (1 = default: mixing_rule reuss with two
+ * complementary phases: the tiled displacement sweep forms the harmonic moduli from phi_1 itself, one division per voxel, counter
+ * "u_tile_reuss"; 0 = the two precomputed arrays of harmonic moduli, which every other case reads), aniso_sc_tile (1 = default: heat / porous with two complementary
  * phases of which one has law aniso -- fg_set_phase_conductivity -- run the tiled sweep's aniso form where u_loop, u_tile, phi_sweep
  * and the grid allow; 0 = the exact-order 13-point sweep), laminate_overlap (1 = default: the interface kernels of the laminate correction run on a second stream beside the
  * displacement sweep; 0 = one stream), slab_split (slab driver: 1 = one all-to-all per component, overlapping the transforms of the next component; 0 = one
@@ -253,7 +261,8 @@ int fg_get_stage_timing_bias(const fg_solver* s, double* ms);
  * transformed: 0 length 1, 1 power of two, 2 sub-lines p * 2^k, 3 tile kernels, 4 Bluestein, 5 O(n^2) sums;
  * "fft_bluestein_m_x" / "_y" / "_z" = the padded length of the axis' Bluestein pass (0: the axis is not on Bluestein);
  * "phase_uploads" = host arrays this solver has received through fg_set_phase (with a field), fg_set_phase_field_fine and
- * fg_set_normals (fg_voxelize_into adds none); "u_tile_aniso" = launches of the tiled sweep's anisotropic form (general
+ * fg_set_normals (fg_voxelize_into adds none); "u_tile_reuss" = launches of the tiled sweep's in-sweep harmonic form (mixing_rule reuss,
+ * option reuss_sweep); "u_tile_aniso" = launches of the tiled sweep's anisotropic form (general
  * phases, option aniso_tile); "sc_tile_aniso" = launches of the tiled scalar sweep's aniso form (heat / porous, option
  * aniso_sc_tile).  Unknown names give -1. */
 long fg_get_counter(const fg_solver* s, const char* name);
