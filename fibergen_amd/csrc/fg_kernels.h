@@ -277,6 +277,15 @@ void launch_sc_cg_dot(int mode, const Grid& g, const double* a, const double* b,
                       hipStream_t s);
 void launch_sc_cg_axpy(int mode, const Grid& g, double* x, double* y, double* r, const double* w, double a, hipStream_t s,
                        long count = 0 /* doubles to update; 0 = g.n (x-slabs: + the spare planes) */);
+// pressure of mode viscosity (fg_kernels_pressure.hip).  launch_div_vector: b = alpha * divVector(t)  F:19983-20003 on the padded
+// layout, each component minus its periodic forward neighbour (b is none of t's components).  launch_poisson_symbol: the
+// division of poisson_solve  F:23462-23496 in place on the half spectrum [nx][ny][nzc] of one component, bin 0 set to zero;
+// cs[a][m] = cos(2 pi m / n_a) per axis (device arrays, the z table holds nzc entries).
+struct PoissonTables {
+  const double* cs[3];
+};
+void launch_div_vector(const Grid& g, const FieldPtrs<3>& t, double alpha, double* b, hipStream_t s);
+void launch_poisson_symbol(const Grid& g, double* uc, const PoissonTables& tb, hipStream_t s);
 void launch_sc_minmax(const Grid& g, const ScalarParams& sp, const FieldPtrs<kMaxPhases>& phi, double* partial,
                       double* out2, hipStream_t s);
 void launch_tangent_minmax(const Grid& g, const PhaseTable& pt, int mixing, const FieldPtrs<kMaxPhases>& phi,

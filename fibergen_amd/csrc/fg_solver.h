@@ -328,6 +328,10 @@ class Solver {
   FieldPtrs<5> dfg_moduli();            // gamma_scheme 2: A_n, B_n, A_23, A_13, A_12 (once per geometry)
   // calcStress into tau_: the phase fractions, or under gamma_scheme 2 the five moduli
   void stress_to_tau(const StressParams& sp, double* src);
+  // mode viscosity: fu_ = divOperatorStaggered(calcStressDiff(eps_)) through tau_, the front half of the "u" and "p" accessors
+  void viscosity_force(const char* what);
+  PoissonTables poisson_tables();       // cos(2 pi m / n) per axis for the pressure accessor (built on first use)
+  void pressure();                      // get_raw_field("p")  F:15554-15573 into the first component of tau_
   void build_laminate_lists();          // interface / affected voxel lists of the laminate correction (once per geometry)
   void u_pass_front(const double* E6);  // u_k (fu_) -> sums of squares of eps_k, f_{k+1} (fu_alt_)
   void u_pass_back();                   // f_{k+1} -> u_{k+1}, buffers swapped
@@ -490,6 +494,7 @@ class Solver {
   double* xi_[3] = {nullptr, nullptr, nullptr};  // collocated scheme: signed frequency / cell size per axis
   double* wil_t_[3] = {nullptr, nullptr, nullptr};   // willot scheme: tan(q / 2) / (4 w) per axis (willot_axis_table)
   cplx* wil_e_[3] = {nullptr, nullptr, nullptr};     // willot scheme: 1 + e^{iq} per axis
+  double* poi_cs_[3] = {nullptr, nullptr, nullptr};  // pressure accessor: cos(2 pi m / n) per axis
 
   hostmath::Mat6 BC_P_, BC_Q_, BC_M_, BC_MQ_, BC_QC0_;
   double F00_[6];

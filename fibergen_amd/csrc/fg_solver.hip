@@ -209,6 +209,7 @@ void Solver::release() {
     if (xi_[a]) (void)hipFree(xi_[a]);
     if (wil_t_[a]) (void)hipFree(wil_t_[a]);
     if (wil_e_[a]) (void)hipFree(wil_e_[a]);
+    if (poi_cs_[a]) (void)hipFree(poi_cs_[a]);
   }
   for (hipEvent_t e : {ev_[0], ev_[1], ev_copy_})
     if (e) (void)hipEventDestroy(e);
@@ -2398,6 +2399,7 @@ int Solver::field_components(const std::string& name) const {
   if (name == "epsilon" || name == "sigma" || name == "tau" || name == "polarization") return 6;
   if (name == "u" || name == "f" || name == "normals") return 3;
   if (name == "f_hat") return 3;
+  if (name == "p") return opt_.mode == 2 ? 1 : 0;   // the pressure of the dual Stokes scheme
   if (name == "phi") return pt_.n;
   if (name == "sumsq") return 6;
   return 0;
@@ -2413,7 +2415,51 @@ double* Solver::device_component(const std::string& name, int c) {
   return nullptr;
 }
 
-// get_raw_field  F:15396-15684 (epsilon, sigma, u, phi, normals) + raw stage buffers for the tests
+// calcStressDiff(epsilon, sigma) F:18030-18033 + divOperatorStaggered(sigma, sigma): the body force both fields of the dual
+// Stokes scheme start from, with the solver's mixing rule and under gamma_scheme 2 the five moduli (stress_to_tau).
+// tau_ and fu_ hold nothing between passes in this mode (pass_viscosity rebuilds both from the strain state).
+void Solver::viscosity_force(const char* what) {
+  stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), eps_);
+  check_device_error(what);
+  launch_div(g_, ptrs6(tau_), ptrs3(fu_), kNoXHalo, stream_);
+}
+
+// poisson_solve  F:23462, 23471-23482: xi_a = (2 pi / n_a) * m, cos on the host with the libm call the reference makes per bin;
+// built and uploaded by the first pressure accessor (the grid of a solver never changes)
+PoissonTables Solver::poisson_tables() {
+  const int len[3] = {g_.nx, g_.ny, g_.nz};
+  for (int a = 0; a < 3; ++a) {
+    if (poi_cs_[a]) continue;
+    const int cnt = (a == 2) ? g_.nzc : len[a];
+    std::vector<double> cs(cnt);
+    const double xi_0 = 2.0 * M_PI / len[a];
+    for (int m = 0; m < cnt; ++m) cs[m] = std::cos(xi_0 * m);
+    FG_HIP_CHECK(hipMalloc(&poi_cs_[a], cnt * sizeof(double)));
+    FG_HIP_CHECK(hipMemcpy(poi_cs_[a], cs.data(), cnt * sizeof(double), hipMemcpyHostToDevice));
+  }
+  PoissonTables t;
+  for (int a = 0; a < 3; ++a) t.cs[a] = poi_cs_[a];
+  return t;
+}
+
+// get_raw_field("p")  F:15554-15573 / writeVTK F:23428-23434: laplace(p) = div(div(eta_0 (phi - phi_0) sigma_E)), solved by
+// poisson_solve F:23454-23500.  The transforms are FFT3::forward / backward (F:7232-7244): FFTW's r2c and c2r, BOTH unnormalised,
+// so the pair multiplies by nxyz and the symbol's c = 2 nxyz (F:23463) leaves p = L^-1 f with L the 7-point periodic Laplacian --
+// restated as written: forward with scale 1, the division by c (...), inverse.
+// The one-component forward / inverse pair of Fft3 is taken, not the fused chain of the loop: it leaves the spectrum in the
+// canonical [nx][ny][nzc] layout on every route, which is what the symbol kernel indexes (an accessor, not the timed loop).
+// Result: the first component of tau_, free once the divergence has consumed the polarisation.
+void Solver::pressure() {
+  viscosity_force("p");
+  double* const p = tau_;
+  launch_div_vector(g_, ptrs3(fu_), 1 / (2 * opt_.mu_0), p, stream_);   // (contains the multiplication with 2 eta_0  F:15564)
+  const PoissonTables tb = poisson_tables();
+  fft_->forward(p, 1, g_.n, 1.0);
+  launch_poisson_symbol(g_, p, tb, stream_);
+  fft_->inverse(p, 1, g_.n);
+}
+
+// get_raw_field  F:15396-15684 (epsilon, sigma, u, p, phi, normals) + raw stage buffers for the tests
 void Solver::get_field(const std::string& name, double* out) {
   FG_HIP_CHECK(hipSetDevice(device_));
   if (name == "polarization" && opt_.mode != 1) {   // the raw state of method polarization between passes (fg_iterate); reading it keeps it
@@ -2421,12 +2467,19 @@ void Solver::get_field(const std::string& name, double* out) {
     download_unpadded(eps_, out, 6, g_.n);
     return;
   }
+  if (name == "p") {   // the pressure exists in the dual Stokes scheme only (F:15554-15573 is written for mode viscosity)
+    if (slab_layout_ && nranks_ > 1)   // (like "u": a lone slab holds the whole grid)
+      throw std::runtime_error("field 'p' (a global Poisson solve) is not available on slab-decomposed solvers");
+    if (opt_.mode != 2)
+      throw std::runtime_error(std::string("field 'p' (the pressure) exists in mode viscosity only, not in mode ") +
+                               (opt_.mode == 1 ? "heat / porous, whose potential is field 'u'" : "elasticity"));
+  }
   ensure_eps();
   // fu_ is overwritten by the displacement reconstruction (scalar modes: by an equivalent potential, still valid;
   // displacement-space CG: the reconstruction goes to the free buffer fu_alt_, fu_ is the iterate itself)
   if (name == "u" && slab_layout_ && nranks_ > 1)
     throw std::runtime_error("field 'u' (a global reconstruction) is not available on slab-decomposed solvers");
-  if (name == "u" && opt_.mode != 1 && !cg_u_active_) u_valid_ = false;
+  if ((name == "u" || name == "p") && opt_.mode != 1 && !cg_u_active_) u_valid_ = false;
   if (name == "sumsq") {  // the six sums of squares of the last norm sweep (device slot; the displacement loop keeps them there)
     FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotSumSq, dscal_ + kSlotSumSq, 6 * sizeof(double), hipMemcpyDeviceToHost, stream_));
     FG_HIP_CHECK(hipStreamSynchronize(stream_));
@@ -2460,11 +2513,14 @@ void Solver::get_field(const std::string& name, double* out) {
     download_unpadded(tau_, out, 6, g_.n);
     return;
   }
+  if (name == "p") {
+    pressure();
+    download_unpadded(tau_, out);
+    return;
+  }
   if (name == "u" && opt_.mode == 2) {
     // velocity  F:15528-15535: calcStressDiff, div, G0(1/(4 mu0), inf, alpha = 1/(2 mu0)): c10 = c20 = -alpha/mu = -2
-    stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), eps_);
-    check_device_error("u");
-    launch_div(g_, ptrs6(tau_), ptrs3(fu_), kNoXHalo, stream_);
+    viscosity_force("u");
     const double a = 1 / (2 * opt_.mu_0), mu_g = 1 / (4 * opt_.mu_0);
     const double c12[2] = {-a / mu_g, -a / mu_g};
     const bool timing = timing_;
@@ -2518,7 +2574,7 @@ void Solver::set_field(const std::string& name, const double* in) {
     return;
   }
   const int nc = field_components(name);
-  if (nc == 0 || name == "sigma" || name == "sumsq") throw std::runtime_error("field '" + name + "' cannot be set");
+  if (nc == 0 || name == "sigma" || name == "sumsq" || name == "p") throw std::runtime_error("field '" + name + "' cannot be set");
   std::vector<RowBlock> blocks;
   for (int c = 0; c < nc; ++c) {
     double* d = device_component(name, c);

@@ -678,7 +678,7 @@ class FG:
         """GetField  F:26931-27010: ndarray[ncomp, nx, ny, nz] (float64), optionally sub-sampled."""
         self.init_lss()
         lss = self._lss
-        if name in ("epsilon", "sigma", "u"):
+        if name in ("epsilon", "sigma", "u", "p"):   # "p": the pressure, mode viscosity only (F:15554-15573)
             data = lss.get_field(name)
         elif name == "phi":
             self.init_phase()
@@ -764,15 +764,17 @@ class FG:
         st = self._settings()
         lss = self._lss
         eps, sig = lss.get_field("epsilon"), lss.get_field("sigma")
+        pressure = None
         if self._mode == "viscosity":
             # dual scheme: the solver's "epsilon" is the fluid stress, its "sigma" the shear rate (F:23403-23416);
-            # the pressure field of the reference's file (a Poisson solve, F:23418-23430) is not written
+            # after the velocity the file carries the pressure (F:23428-23434)
             eps, sig = sig, eps
+            pressure = lss.get_field("p")[0]
         vtk.write_results(filename, lss.shape, self._dims, self._x0, self._phase_names, lss.get_field("phi"),
                           eps, sig, lss.get_field("u"),
                           binary=self._child_value(st, "res_format", "binary", str) == "binary",
                           dtype=self._child_value(st, "restype", "float", str),
-                          mode="elasticity" if self._mode == "viscosity" else self._mode)
+                          mode="elasticity" if self._mode == "viscosity" else self._mode, pressure=pressure)
 
     # ------------------------------------------------------------------ running
     def _on_iteration(self):

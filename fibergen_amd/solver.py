@@ -336,6 +336,8 @@ class LSSolver:
     def get_field(self, name):
         nc = self._lib.fg_field_components(self._h, name.encode())
         if nc <= 0:
+            if name == "p":   # the pressure of mode viscosity: the library says which mode this solver is in
+                self._check(self._lib.fg_get_field(self._h, b"p", _dp(np.empty(1))))
             raise RuntimeError("Unknown field '%s'" % name)
         if name == "sumsq":
             out = np.zeros(6)

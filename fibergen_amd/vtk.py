@@ -73,8 +73,9 @@ class VTKCubeWriter:
 
 
 def write_results(filename, shape, dims, x0, phase_names, phi, epsilon, sigma, u, binary=True, dtype="float",
-                  mode="elasticity"):
-    """LSSolver::writeVTK  F:23317-23451 (elasticity and heat / porous branches)."""
+                  mode="elasticity", pressure=None):
+    """LSSolver::writeVTK  F:23317-23451 (elasticity and heat / porous branches; pressure: the scalar "p" the viscosity
+    branch writes after the velocity, F:23434)."""
     w = VTKCubeWriter(filename, shape, dims, x0, binary, dtype)
     w.write_mesh()
     for m, name in enumerate(phase_names):
@@ -88,6 +89,8 @@ def write_results(filename, shape, dims, x0, phase_names, phi, epsilon, sigma, u
         w.write_vector("u", u)
     else:
         w.write_scalar("T" if mode == "heat" else "p", u[0])
+    if pressure is not None:
+        w.write_scalar("p", pressure)
     w.close()
 
 

@@ -227,6 +227,11 @@ int fg_get_ref_material(const fg_solver* s, double* mu_0, double* lambda_0);
 /* get_raw_field  F:15396-15684.  Names: "epsilon" (6), "sigma" (6, evaluated with C0 = 0),
  * "u" (3), "phi" (nphases), "normals" (3); work buffers for stage tests: "tau" (6), "f" (3),
  * "f_hat" (3 complex components in the padded layout [nx][ny][nz/2+1][2]), "sumsq" (6 scalars).
+ * "p" (1, mode viscosity only): the pressure of the dual Stokes scheme, F:15554-15573 -- calcStressDiff, divOperatorStaggered,
+ * divVector with 1/(2 mu_0), poisson_solve (the 7-point periodic Laplacian inverted in Fourier space, mean 0), for the solver's
+ * mixing rule and gamma_scheme like "u".  Reading it leaves the loop state alone (it uses the work buffers "u" uses).  In the
+ * other modes fg_field_components("p") is 0 and fg_get_field refuses, naming the field and the mode (heat / porous: the
+ * potential is "u"); slab-decomposed solvers refuse it ("not available on slab-decomposed solvers"); it cannot be set.
  * The work buffers hold what the LAST fg_run_stage left there and nothing else: between stages "tau" is scratch of the
  * transform chain (the x-contiguous spectrum layout of large grids, the all-to-all halves of a slab solver, CG vectors),
  * so after fg_iterate / fg_run_* its contents are unspecified -- read "tau" directly after FG_STAGE_STRESS only.  The
