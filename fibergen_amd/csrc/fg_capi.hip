@@ -254,7 +254,7 @@ int fg_set_option_i(fg_solver* s, const char* key, long value) {
     if (k == "maxiter") o.maxiter = value;
     else if (k == "mixing_rule") {
       if (value != FG_MIXING_VOIGT && value != FG_MIXING_LAMINATE && value != FG_MIXING_REUSS) throw std::runtime_error("Unknown mixing rule");
-      if (value == FG_MIXING_REUSS && v.is_slab()) throw std::runtime_error("mixing_rule reuss is not available on slab-decomposed solvers");
+      if (value == FG_MIXING_REUSS && v.is_slab()) throw std::runtime_error(fg::plan::kReussSlab);
       o.mixing = (int)value;
     } else if (k == "update_ref") o.update_ref = value != 0;
     else if (k == "mode") {
@@ -265,8 +265,8 @@ int fg_set_option_i(fg_solver* s, const char* key, long value) {
     else if (k == "gamma_scheme") {
       if (value < 0 || value > 3)
         throw std::runtime_error("gamma_scheme must be 0 (staggered), 1 (collocated), 2 (full_staggered: doubly fine grid) or 3 (willot)");
-      if (value == 2 && v.is_slab()) throw std::runtime_error("full_staggered is not available on slab-decomposed solvers");
-      if (value == 3 && v.is_slab()) throw std::runtime_error("gamma_scheme willot is not available on slab-decomposed solvers");
+      if (value == 2 && v.is_slab()) throw std::runtime_error(fg::plan::kDfgSlab);
+      if (value == 3 && v.is_slab()) throw std::runtime_error(fg::plan::kWillotSlab);
       o.gamma_scheme = (int)value;
     }
     else if (k == "u_tile") {
@@ -307,7 +307,7 @@ int fg_set_option_i(fg_solver* s, const char* key, long value) {
     else if (k == "u_loop") o.u_loop = (int)value;
     else if (k == "method") {
       if (value != 0 && value != 1 && value != 2) throw std::runtime_error("Unknown solver method");
-      if (value == 2 && v.is_slab()) throw std::runtime_error("method polarization is not available on slab-decomposed solvers");
+      if (value == 2 && v.is_slab()) throw std::runtime_error(fg::plan::kPolarSlab);
       o.method = (int)value;
     }
     else if (k == "fuse_stress_div") o.fuse_stress_div = value != 0;

@@ -249,14 +249,12 @@ void Solver::slab_fetch_norms(int n) {
   FG_HIP_CHECK(hipEventRecord(ev_norm_, comm_stream_));
 }
 
-bool Solver::slab_fast_ok(bool allow_mixed_bc) const {
-  if (opt_.mode == 1)   // heat / porous: the potential sweep on the precomputed conductivity
-    return opt_.u_loop >= 2 && opt_.gamma_scheme == 0 && pt_.n >= 1 && opt_.mixing == kMixVoigt && opt_.bc_relax == 1.0 && fft_ys_ &&
-           (!mixed_bc() || allow_mixed_bc);
-  if (!(opt_.u_loop >= 2 && opt_.u_tile && opt_.mode == 0 && opt_.gamma_scheme == 0 && pt_.n >= 1 &&
-        (opt_.mixing == kMixVoigt || (opt_.mixing == kMixLaminate && normals_)) && opt_.bc_relax == 1.0 && u_tile_supported(g_)))
-    return false;
-  return !mixed_bc() || allow_mixed_bc;
+// the fast path of a member (heat / porous: the potential sweep on the precomputed conductivity); allow_mixed_bc: under the run
+// driver of method basic, whose host corrects the prescribed mean between passes
+bool Solver::slab_fast_ok(bool allow_mixed_bc) {
+  plan::PlanInput in = plan_input(plan::Entry::Slab);
+  in.in_run = allow_mixed_bc;
+  return plan::plan_sweeps(in).slab_fast;
 }
 
 void Solver::slab_moduli_step() {
@@ -266,7 +264,7 @@ void Solver::slab_moduli_step() {
   mod.p[1] = smod_ + ucs_;
   // two complementary phases: the sweep reads phi_1 (with its halo planes) and forms the moduli itself.  The decision is
   // local data; every rank of a run sees the same kind of phase fields (normalizePhi output or not)
-  slab_phi_ = opt_.mode == 0 && two_phase_complementary();
+  slab_phi_ = opt_.mode == 0 && plan_input(plan::Entry::Slab, 2).complementary;
   if (slab_phi_) {
     FG_HIP_CHECK(hipMemcpyAsync(smod_, phi_ + g_.n, (size_t)g_.n * sizeof(double), hipMemcpyDeviceToDevice, stream_));
   } else {
@@ -525,7 +523,7 @@ void Solver::slab_front_exact(bool sum_tau) {
   comm_wait(kXHaloU);
   comm_wait(kXSums);
   if (su_valid_ && eps_stale_) slab_materialise_eps();
-  if (opt_.mixing == kMixLaminate && !normals_) throw std::runtime_error("laminate mixing needs interface normals");
+  if (opt_.mixing == kMixLaminate && !normals_) throw std::runtime_error(plan::kLaminateNormals);
   launch_stress(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs6(eps_), phase_ptrs(), normal_ptrs(), ptrs6(tau_), derr_, stream_);
   sum_tau = sum_tau || opt_.mode == 2;   // viscosity: the Delta operator needs <tau> in every pass
   if (sum_tau) launch_sum6(g_, ptrs6(tau_), false, partial_, dscal_ + kSlotMean, stream_);
@@ -607,14 +605,13 @@ void Solver::slab_reset_state() {
 void SlabGroup::check_members() const {
   if (m_.empty()) throw std::runtime_error("empty slab group");
   const Solver& a = *m_[0];
-  for (Solver* s : m_) s->reuss_check();   // mixing_rule reuss is refused on slabs
-  if (a.opt_.gamma_scheme != 0) throw std::runtime_error("slab-decomposed solvers run the staggered Green operator");
-  if (a.opt_.mode == 2 && (a.opt_.mixing != kMixVoigt || a.opt_.bc_relax != 1.0))
-    throw std::runtime_error("viscosity mode supports Voigt mixing and bc_relax = 1 only");
-  if (a.pt_.n < 1) throw std::runtime_error("No materials specified");
+  // what the slab driver does not run (fg_sweep_plan.h): mixing_rule reuss on any member, then the head's options, which speak
+  // for the group, then per member its phase laws, its transport and the sameness of its options
+  for (Solver* s : m_)
+    if (const char* refusal = plan::reuss_refusal(s->plan_input(plan::Entry::Slab))) throw std::runtime_error(refusal);
+  m_[0]->require_plan(plan::Entry::Slab);
   for (Solver* s : m_) {
-    if (s->general_phase()) throw std::runtime_error("general (anisotropic) phases are not available on slab-decomposed solvers");
-    if (s->aniso_phase()) throw std::runtime_error("aniso (3 x 3 conductivity) phases are not available on slab-decomposed solvers");
+    if (const char* refusal = plan::slab_law_refusal(s->plan_input(plan::Entry::Slab))) throw std::runtime_error(refusal);
     if (s->nranks_ > 1 && !s->comm_) throw std::runtime_error("slab solver is not connected to a transport (fg_slab_connect_*)");
     if (s->opt_.mixing != a.opt_.mixing || s->pt_.n != a.pt_.n || s->opt_.u_loop != a.opt_.u_loop || s->opt_.u_tile != a.opt_.u_tile ||
         s->opt_.slab_split != a.opt_.slab_split || s->opt_.slab_interleave != a.opt_.slab_interleave || s->opt_.method != a.opt_.method ||
@@ -626,8 +623,7 @@ void SlabGroup::check_members() const {
 // heat / porous on slabs: the potential-based fast path only (prescribed mean gradients, a grid the tiled sweep fits)
 void SlabGroup::require_scalar_fast(bool allow_mixed_bc) const {
   if (m_[0]->opt_.mode == 1 && !fast_ok(allow_mixed_bc))
-    throw std::runtime_error("heat / porous on slab-decomposed solvers: Voigt mixing, u_loop=2, bc_relax=1 (method=cg: prescribed "
-                             "mean gradients)");
+    throw std::runtime_error(plan::kSlabHeatFast);
 }
 
 void SlabGroup::synchronize() {
@@ -823,7 +819,7 @@ double SlabGroup::mean_energy() {
 void SlabGroup::estimator_begin(bool fresh) {
   Solver& a = *m_[0];
   if (a.opt_.error_estimator < 2) return;
-  if (a.opt_.mode == 1) throw std::runtime_error("heat / porous mode supports the error estimators epsilon and residual");
+  if (a.opt_.mode == 1) throw std::runtime_error(plan::kHeatEstimator);
   double m[6] = {0, 0, 0, 0, 0, 0};
   double w = 0.0;
   if (a.opt_.error_estimator == 2 && !fresh) mean_stress(m);

@@ -24,6 +24,7 @@
 #include "fg_hostmath.h"
 #include "fg_kernels.h"
 #include "fg_stop_rule.h"
+#include "fg_sweep_plan.h"
 #include "fg_transfer.h"
 
 struct fg_fiber;   // include/fibergen_amd.h
@@ -303,26 +304,22 @@ class Solver {
   bool run_cg(const double* E0, const double* S0, double prev0);
   bool run_cg_scalar(const double* E0, double prev0);  // heat / porous: CG in potential space
   bool run_cg_u(const double* E0, double prev0);      // the same CG carried in displacement space (Voigt, prescribed mean strains)
-  bool u_loop_eligible(bool allow_mixed_bc = false);   // (may run the complement check on the device)
-  bool sc_tile_aniso_ok(bool mixed_bc); // aniso phases: the tiled sweep has a form for this problem (k_sc_tile_aniso)
+  // configuration -> refusals and sweeps (fg_sweep_plan.h).  plan_input is the only caller of two_phase_complementary: it runs
+  // the device check where the decision asked for reads it (ask 0: refusals only, 1: the loop decision, 2: the sweeps)
+  plan::PlanInput plan_input(plan::Entry entry, int ask = 0);
+  void require_plan(plan::Entry entry);   // throws plan_error
+  plan::SweepPlan sweep_plan(int ask = 2) { return plan::plan_sweeps(plan_input(in_run_ ? plan::Entry::Run : plan::Entry::Iterate, ask)); }
   void sc_aniso_constants(double* K0, double* K1) const;   // the six constants of phases 0 and 1 (isotropic: mu on the diagonal)
-  bool two_phase_complementary(bool scalar = false);       // phi_0 == 1 - phi_1 everywhere (checked once per geometry)
-  void general_check() const;           // throws for the combinations general phases do not cover
-  void reuss_check() const;             // throws for the combinations mixing_rule reuss does not cover, each naming the option
-  bool reuss_sweep_ok();                // Reuss mixing: the tiled sweep forms the moduli from phi_1 (k_u_tile REUSS)
+  bool two_phase_complementary();       // phi_0 == 1 - phi_1 everywhere (checked once per geometry)
   // method polarization (fg_solver.hip, "the polarisation loop")
-  void polar_check() const;             // throws for the combinations the method does not cover, each naming the option
   void polar_start(const double* E6);   // P = 4 mu_0 E, the constant field the loop starts from  F:21828
   void polar_pass(const double* E6);    // one polarizationScheme call on the state P held in eps_
   void polar_to_strain();               // calcPolarization(..., inv = true)  F:21850: eps_ <- (C + C0)^-1 P
   void polar_settle();                  // before the phases change: a held polarisation state becomes the strain of the phases it was built with
   bool run_polarization(const double* E0, const double* S0, double prev0);
-  bool aniso_tile_ok();                 // general phases: the displacement loop has a sweep for this problem (k_u_tile ANISO)
   FieldPtrs<2> effective_moduli();      // per-voxel sums of the phase moduli for the fast kernels (allocated on first use)
   bool dfg() const { return opt_.gamma_scheme == 2; }
-  void dfg_check() const;               // throws for the combinations full_staggered does not cover
   bool willot() const { return opt_.gamma_scheme == 3; }
-  void willot_check() const;            // throws for the combinations the willot scheme does not cover
   WillotTables willot_tables();         // the per-axis tables of the scheme (built on first use)
   void willot_scheme(const double* E6, double* src, double* dst);
   FieldPtrs<5> dfg_moduli();            // gamma_scheme 2: A_n, B_n, A_23, A_13, A_12 (once per geometry)
@@ -334,6 +331,8 @@ class Solver {
   void pressure();                      // get_raw_field("p")  F:15554-15573 into the first component of tau_
   void build_laminate_lists();          // interface / affected voxel lists of the laminate correction (once per geometry)
   void u_pass_front(const double* E6);  // u_k (fu_) -> sums of squares of eps_k, f_{k+1} (fu_alt_)
+  void laminate_fork();                 // the laminate correction beside the Voigt sweep: u_k is complete, a second stream may start
+  void laminate_correction(const Vec6& E);   // ... its kernels, joined into f_{k+1}
   void u_pass_back();                   // f_{k+1} -> u_{k+1}, buffers swapped
   // r2c, y, x + Green operator + x^-1, y^-1, c2r on 3 components
   // c12: optional {c10, c20} replacing the factors derived from (mu_0, lambda_0, alpha)
@@ -379,7 +378,7 @@ class Solver {
   // ---- slab driver: per-member steps (fg_slab.hip); every comm call is the last dependent thing of its step
   friend class SlabGroup;
   void slab_alloc();
-  bool slab_fast_ok(bool allow_mixed_bc) const;
+  bool slab_fast_ok(bool allow_mixed_bc);
   void slab_moduli_step();                               // effective moduli of the slab + exchange of their halo planes
   // su_[cur] (or u_src) -> norms of eps_k (all-reduced unless !reduce), f_{k+1} in fu_
   void slab_front_fast(const double* E6, bool sum_tau, const double* u_src = nullptr, bool reduce = true);
@@ -478,6 +477,9 @@ class Solver {
   double sc_K_[kMaxPhases][6];     // and the six constants of an aniso phase
   long sc_tile_aniso_ = 0;  // launches of the tiled scalar sweep's aniso form (fg_get_counter "sc_tile_aniso")
   long u_tile_aniso_ = 0;   // launches of the tiled sweep's anisotropic form (fg_get_counter "u_tile_aniso")
+  long complement_checks_ = 0;   // launches of the device complement check (fg_get_counter "complement_checks")
+  long front_sweep_ = -1;   // plan::Front of the last launch of u_pass_front (fg_get_counter "front_sweep")
+  long cg_dir_sweep_ = -1;  // ... of the last direction sweep of a fused CG form (fg_get_counter "cg_dir_sweep")
   long u_tile_reuss_ = 0;   // launches of the tiled sweep's in-sweep harmonic form (fg_get_counter "u_tile_reuss")
   double* fu_alt_ = nullptr;   // 3: second f/u buffer of the displacement-based loop (swapped with fu_)
   double* phi_ = nullptr;      // nphase

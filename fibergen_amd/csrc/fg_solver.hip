@@ -274,7 +274,7 @@ void Solver::set_phase_material(int p, double mu, double lambda) {
 void Solver::set_phase_stiffness(int p, const double* C36) {
   if (p < 0 || p >= pt_.n) throw std::runtime_error("phase index out of range");
   if (!C36) throw std::runtime_error("stiffness pointer is NULL");
-  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("general (anisotropic) phases are not available on slab-decomposed solvers");
+  if (nranks_ != 1 || slab_layout_) throw std::runtime_error(plan::kGeneralSlab);
   double cmax = 0.0;
   for (int i = 0; i < 36; ++i) {
     if (!std::isfinite(C36[i])) throw std::runtime_error("phase stiffness is not finite");
@@ -297,8 +297,8 @@ void Solver::set_phase_stiffness(int p, const double* C36) {
 void Solver::set_phase_conductivity(int p, const double* c6) {
   if (p < 0 || p >= pt_.n) throw std::runtime_error("phase index out of range");
   if (!c6) throw std::runtime_error("conductivity pointer is NULL");
-  if (opt_.mode != 1) throw std::runtime_error("aniso (3 x 3 conductivity) phases are available in heat / porous mode only");
-  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("aniso (3 x 3 conductivity) phases are not available on slab-decomposed solvers");
+  if (opt_.mode != 1) throw std::runtime_error(plan::kAnisoMode);
+  if (nranks_ != 1 || slab_layout_) throw std::runtime_error(plan::kAnisoSlab);
   for (int i = 0; i < 6; ++i)
     if (!std::isfinite(c6[i])) throw std::runtime_error("phase conductivity is not finite");
   invalidate_moduli();
@@ -331,7 +331,7 @@ void Solver::set_phase_field_fine(int p, const double* fine_host) {
   if (p < 0 || p >= pt_.n) throw std::runtime_error("phase index out of range");
   if (willot()) throw std::runtime_error("gamma_scheme willot takes phase fields on the solver's grid (a fine phase field needs full_staggered)");
   if (!dfg()) throw std::runtime_error("a phase field on the doubly fine grid needs gamma_scheme full_staggered (2)");
-  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("full_staggered is not available on slab-decomposed solvers");
+  if (nranks_ != 1 || slab_layout_) throw std::runtime_error(plan::kDfgSlab);
   FG_HIP_CHECK(hipSetDevice(device_));
   ++phase_uploads_;
   const size_t nfine = 8 * (size_t)g_.nxyz;
@@ -678,6 +678,9 @@ long Solver::counter(const std::string& name) const {
   if (name == "interface_voxels") return mixed_dirty_ ? 0 : (long)mixed_n_;
   if (name == "affected_voxels") return mixed_dirty_ ? 0 : (long)aff_n_;
   if (name == "phase_uploads") return phase_uploads_;
+  if (name == "complement_checks") return complement_checks_;
+  if (name == "front_sweep") return front_sweep_;
+  if (name == "cg_dir_sweep") return cg_dir_sweep_;
   if (name == "u_tile_aniso") return u_tile_aniso_;
   if (name == "u_tile_reuss") return u_tile_reuss_;
   if (name == "sc_tile_aniso") return sc_tile_aniso_;
@@ -715,23 +718,12 @@ void Solver::time_end(int stage) {
 void Solver::basic_scheme(const double* E6, double* src, double* dst) {
   if (!src) src = eps_;
   if (!dst) dst = eps_;
-  if (nranks_ != 1) throw std::runtime_error("basic_scheme: slab solvers run under the slab driver (fg_slab.hip)");
-  if (pt_.n < 1) throw std::runtime_error("No materials specified");
-  if (opt_.mixing == kMixLaminate && !normals_) throw std::runtime_error("laminate mixing needs interface normals");
-  reuss_check();
-  if (dfg()) dfg_check();
-  if (willot()) willot_check();
-  general_check();
+  require_plan(plan::Entry::Pass);
 
   ensure_eps();  // the displacement-based loop may have left the strain implicit
   if (opt_.bc_relax != 1.0) {  // F:20563-20565: mean of the operator's argument
     launch_sum6(g_, ptrs6(src), false, partial_, dscal_ + kSlotMean, stream_);
     fetch_mean6(F00_);
-  }
-  if (opt_.mode == 2) {
-    if (opt_.gamma_scheme == 1) throw std::runtime_error("viscosity mode supports gamma_scheme staggered, full_staggered and willot only");
-    if (opt_.mixing == kMixLaminate) throw std::runtime_error("viscosity mode supports Voigt and Reuss mixing only");
-    if (opt_.bc_relax != 1.0) throw std::runtime_error("viscosity mode supports bc_relax = 1 only");
   }
   if (willot()) willot_scheme(E6, src, dst);
   else if (opt_.mode == 2) pass_viscosity(E6, src, dst);
@@ -778,29 +770,30 @@ void Solver::pass_viscosity(const double* E6, double* src, double* dst) {
   const StressParams sp = stress_params(opt_.mu_0, opt_.lambda_0, 1.0);
   // full_staggered: the fused form exists as the tiled sweep only (other grids store the polarisation)
   // (Reuss mixing: the fused forms re-evaluate the Voigt rule from the phase fractions in their tail sweep -- the stored form)
-  const bool fused = opt_.fuse_stress_div != 0 && opt_.mixing != kMixReuss && (!dfg() || (opt_.u_loop >= 2 && u_tile_supported(g_)));
-  if (fused) {
-    // the polarisation is a point-wise function of the strain: it is evaluated inside the divergence sweep (with its
-    // six sums) and again in the tail sweep, and never stored
-    time_begin(0);
-    if (dfg())
-      launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), dfg_moduli(), ptrs3(fu_), partial_, dscal_ + kSlotMean,
-                      stream_);
-    else if (opt_.u_loop >= 2 && u_tile_supported(g_))   // fast kernels allowed: the LDS-tiled marching form
-      launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), effective_moduli(), ptrs3(fu_), partial_,
-                      dscal_ + kSlotMean, stream_);
-    else
+  const plan::Viscosity form = sweep_plan(0).viscosity;
+  const bool fused = form != plan::Viscosity::Stored;
+  // fused: the polarisation is a point-wise function of the strain: it is evaluated inside the divergence sweep (with its
+  // six sums) and again in the tail sweep, and never stored
+  time_begin(0);
+  switch (form) {
+    case plan::Viscosity::TileDfg:
+      launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), dfg_moduli(), ptrs3(fu_), partial_, dscal_ + kSlotMean, stream_);
+      break;
+    case plan::Viscosity::Tile:   // fast kernels allowed: the LDS-tiled marching form
+      launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), effective_moduli(), ptrs3(fu_), partial_, dscal_ + kSlotMean, stream_);
+      break;
+    case plan::Viscosity::FusedVoigt:
       launch_stress_div_sum_voigt(g_, sp, ptrs6(src), phase_ptrs(), ptrs3(fu_), partial_, dscal_ + kSlotMean, stream_);
-    time_end(0);
-  } else {
-    time_begin(0);
-    stress_to_tau(sp, src);
-    time_end(0);
-    launch_sum6(g_, ptrs6(tau_), false, partial_, dscal_ + kSlotMean, stream_);   // tau_copy->average(), stays on the device
-    time_begin(1);
-    launch_div(g_, ptrs6(tau_), ptrs3(fu_), kNoXHalo, stream_);
-    time_end(1);
+      break;
+    case plan::Viscosity::Stored:
+      stress_to_tau(sp, src);
+      time_end(0);
+      launch_sum6(g_, ptrs6(tau_), false, partial_, dscal_ + kSlotMean, stream_);   // tau_copy->average(), stays on the device
+      time_begin(1);
+      launch_div(g_, ptrs6(tau_), ptrs3(fu_), kNoXHalo, stream_);
+      break;
   }
+  time_end(fused ? 0 : 1);
   // initBCProjector / applyBCProjector inside GammaOperatorStaggered (k_bc_adjust_sums has the algebra)
   if (mixed_bc()) bc_adjust_sums(alpha / (2 * alpha * m));
   const double mu_g = -1.0 / (4 * m);
@@ -886,38 +879,36 @@ void Solver::pass_staggered(const double* E6, double* src, double* dst) {
   // initBCProjector  F:20228-20239 needs <tau> only for mixed boundary conditions
   double F0[6] = {0, 0, 0, 0, 0, 0};
   const bool mixed = mixed_bc();
-  // Voigt mixing: polarisation and divergence in one sweep (tau never stored); the laminate rule keeps the
-  // two-kernel form (its per-voxel Newton solve is too costly to repeat at the six neighbours)
-  // (general phases: both fused forms evaluate the polarisation from (mu, lambda) -- the stored-polarisation form serves them)
-  const bool fuse_sd = opt_.fuse_stress_div && opt_.mixing == kMixVoigt && !mixed && !dfg() && !general_phase();
-  // with the fast kernels allowed (u_loop = 2) the LDS-tiled form takes over where the grid fits; it also delivers
-  // the sums of tau, so mixed boundary conditions keep the fused sweep
-  // (the tiled form reads the moduli arrays: it serves the Reuss rule as well, fuse_sd evaluates the Voigt rule from the phases)
-  const bool tile_sd = opt_.fuse_stress_div && opt_.mixing != kMixLaminate && opt_.u_loop >= 2 && u_tile_supported(g_) && !general_phase();
-  if (tile_sd) {
-    time_begin(0);
-    if (dfg())
-      launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), dfg_moduli(), ptrs3(fu_), partial_, dscal_ + kSlotMean, stream_);
-    else
-      launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), effective_moduli(), ptrs3(fu_), partial_, dscal_ + kSlotMean,
-                      stream_);
-    time_end(0);
-    if (mixed) fetch_mean6(F0);
-  } else if (fuse_sd) {
-    time_begin(0);
-    launch_stress_div_voigt(g_, sp, ptrs6(src), phase_ptrs(), ptrs3(fu_), stream_);
-    time_end(0);
-  } else {
-    time_begin(0);
-    stress_to_tau(sp, src);
-    time_end(0);
-    if (mixed) {
-      launch_sum6(g_, ptrs6(tau_), false, partial_, dscal_ + kSlotMean, stream_);
-      fetch_mean6(F0);
-    }
-    time_begin(1);
-    launch_div(g_, ptrs6(tau_), ptrs3(fu_), kNoXHalo, stream_);
-    time_end(1);
+  const plan::SweepPlan sweeps = sweep_plan(0);
+  time_begin(0);
+  switch (sweeps.staggered) {
+    case plan::Staggered::Tile:
+      // the fast kernels allowed (u_loop = 2) and a grid the tiles fit: the LDS-tiled form on the moduli arrays (Voigt and Reuss);
+      // it also delivers the sums of tau, so mixed boundary conditions keep the fused sweep
+      if (sweeps.staggered_dfg)
+        launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), dfg_moduli(), ptrs3(fu_), partial_, dscal_ + kSlotMean, stream_);
+      else
+        launch_eps_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs6(src), effective_moduli(), ptrs3(fu_), partial_, dscal_ + kSlotMean, stream_);
+      time_end(0);
+      if (mixed) fetch_mean6(F0);
+      break;
+    case plan::Staggered::FusedVoigt:   // Voigt mixing: polarisation and divergence in one sweep (tau never stored)
+      launch_stress_div_voigt(g_, sp, ptrs6(src), phase_ptrs(), ptrs3(fu_), stream_);
+      time_end(0);
+      break;
+    case plan::Staggered::Stored:
+      // the laminate rule (its per-voxel Newton solve is too costly to repeat at the six neighbours) and general phases (both
+      // fused forms evaluate the polarisation from (mu, lambda))
+      stress_to_tau(sp, src);
+      time_end(0);
+      if (mixed) {
+        launch_sum6(g_, ptrs6(tau_), false, partial_, dscal_ + kSlotMean, stream_);
+        fetch_mean6(F0);
+      }
+      time_begin(1);
+      launch_div(g_, ptrs6(tau_), ptrs3(fu_), kNoXHalo, stream_);
+      time_end(1);
+      break;
   }
   fft_g0_chain(fu_, alpha, nullptr, tau_);   // the polarisation is dead once its divergence is taken
 
@@ -1107,37 +1098,35 @@ FieldPtrs<3> Solver::normal_ptrs() const {
   return nrm;
 }
 
-bool Solver::u_loop_eligible(bool allow_mixed_bc) {
-  if (opt_.mode == 1) {
-    // the scalar modes only have the potential-based loop
-    if (nranks_ != 1) throw std::runtime_error("heat / porous mode is not available on slab-decomposed solvers");
-    if (opt_.mixing == kMixLaminate) throw std::runtime_error("heat / porous mode supports Voigt and Reuss mixing only");
-    if (opt_.bc_relax != 1.0) throw std::runtime_error("heat / porous mode does not support bc_relax != 1");
-    if (mixed_bc() && !allow_mixed_bc)
-      throw std::runtime_error("heat / porous mode: mixed boundary conditions run with method=basic (fg_run_load_case) only");
-    return pt_.n >= 1;
-  }
-  // general phases: the displacement loop exists as the tiled sweep's anisotropic form only; everything else takes the
-  // strain-state pass
-  if (general_phase() && !aniso_tile_ok()) return false;
-  // full_staggered: the displacement loop runs the tiled Voigt sweep only (the untiled sweep has no five-moduli form)
-  const bool scheme_ok = opt_.gamma_scheme == 0 ||
-                         (dfg() && opt_.mixing == kMixVoigt && opt_.u_loop >= 2 && opt_.u_tile && u_tile_supported(g_));
-  if (!(opt_.u_loop && opt_.mode == 0 && scheme_ok && nranks_ == 1 && pt_.n >= 1 &&
-        (opt_.mixing != kMixLaminate || normals_) && opt_.bc_relax == 1.0))
-    return false;
-  if (!mixed_bc()) return true;
-  // mixed boundary conditions: <tau> of every pass corrects the prescribed mean of the next one; the tiled Voigt sweep
-  // delivers it with the norms (run() only: the correction needs the host between passes)
-  return allow_mixed_bc && opt_.u_loop >= 2 && opt_.u_tile && u_tile_supported(g_);   // Voigt / Reuss, or laminate as the Voigt sweep's correction
+// What the refusals and the choice of sweeps read (fg_sweep_plan.h).  ask: 0 the refusals and the strain-state passes (no
+// complement check), 1 the loop decision, 2 the sweeps of the displacement / potential loop.
+plan::PlanInput Solver::plan_input(plan::Entry entry, int ask) {
+  plan::PlanInput in;
+  in.mode = opt_.mode, in.mixing = opt_.mixing, in.gamma_scheme = opt_.gamma_scheme, in.method = opt_.method;
+  in.error_estimator = opt_.error_estimator, in.u_loop = opt_.u_loop;
+  in.u_tile = opt_.u_tile != 0, in.fuse_stress_div = opt_.fuse_stress_div != 0, in.cg_fused = opt_.cg_fused != 0;
+  in.phi_sweep = opt_.phi_sweep != 0, in.aniso_tile = opt_.aniso_tile != 0, in.aniso_sc_tile = opt_.aniso_sc_tile != 0;
+  in.reuss_sweep = opt_.reuss_sweep != 0, in.bc_relaxed = opt_.bc_relax != 1.0;
+  in.n_phases = pt_.n, in.general_phase = general_phase(), in.aniso_phase = aniso_phase();
+  for (int p = 0; p < pt_.n && in.mixing == kMixReuss; ++p)
+    in.reuss_invertible = in.reuss_invertible && (opt_.mode == 0 ? 2 * pt_.mu[p] > 0 && 2 * pt_.mu[p] + 3 * pt_.lambda[p] > 0 : pt_.mu[p] > 0);
+  in.tiled = u_tile_supported(g_), in.normals = normals_ != nullptr;
+  in.multi_rank = nranks_ != 1, in.slab = in.multi_rank || slab_layout_, in.slab_ys = fft_ys_ != nullptr;
+  in.mixed_bc = mixed_bc(), in.bc_identity = frobenius(BC_Q_) == 0.0;   // Q = Id - P != 0  <=>  |MQ| >= eps
+  in.entry = entry, in.in_run = in_run_;
+  in.complementary = ask > 0 && plan::reads_complement(in, ask > 1) && two_phase_complementary();
+  return in;
+}
+
+void Solver::require_plan(plan::Entry entry) {
+  if (const char* refusal = plan::plan_error(plan_input(entry))) throw std::runtime_error(refusal);
 }
 
 // Two phases whose fractions are complementary bit for bit (phi_0 == 1 - phi_1: what normalizePhi leaves for two
 // materials), checked once per geometry on the device.  Option phi_sweep = 0 switches the shortcut off (A/B runs).
-bool Solver::two_phase_complementary(bool scalar) {
-  if (pt_.n != 2 || !opt_.phi_sweep) return false;
-  if (opt_.mode != 0 && !(scalar && opt_.mode == 1)) return false;   // (scalar: the aniso form of the tiled scalar sweep asks)
+bool Solver::two_phase_complementary() {
   if (complement_dirty_) {
+    ++complement_checks_;
     int one = 1;
     FG_HIP_CHECK(hipMemcpyAsync(derr_ + 1, &one, sizeof(int), hipMemcpyHostToDevice, stream_));
     launch_complement_check(g_, phi_, phi_ + g_.n, derr_ + 1, stream_);
@@ -1175,65 +1164,6 @@ FieldPtrs<2> Solver::effective_moduli() {
   return mod;
 }
 
-// law "general" (constant 6 x 6 stiffness per phase): elasticity, Voigt mixing, staggered / collocated / willot, one GPU
-void Solver::general_check() const {
-  // law "aniso" (constant 3 x 3 conductivity per phase): heat / porous, one GPU (Voigt mixing is all these modes have)
-  if (aniso_phase()) {
-    if (opt_.mode != 1) throw std::runtime_error("aniso (3 x 3 conductivity) phases are available in heat / porous mode only");
-    if (nranks_ != 1 || slab_layout_) throw std::runtime_error("aniso (3 x 3 conductivity) phases are not available on slab-decomposed solvers");
-  }
-  if (!general_phase()) return;
-  if (opt_.mode != 0) throw std::runtime_error("general (anisotropic) phases are available in elasticity mode only");
-  if (opt_.mixing != kMixVoigt)
-    throw std::runtime_error("general (anisotropic) phases support Voigt mixing only (the laminate split is written for isotropic phases)");
-  if (dfg()) throw std::runtime_error("general (anisotropic) phases are not available with gamma_scheme full_staggered / half_staggered");
-  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("general (anisotropic) phases are not available on slab-decomposed solvers");
-}
-
-// mixing_rule reuss (ReussMixedMaterialLaw F:12651-12724): isotropic phases in all four modes, gamma_scheme staggered /
-// collocated / willot, methods basic and cg, estimators epsilon / residual / sigma / none, one GPU
-void Solver::reuss_check() const {
-  if (opt_.mixing != kMixReuss) return;
-  if (general_phase())
-    throw std::runtime_error("general (anisotropic) phases support Voigt mixing only (the laminate split is written for isotropic phases)");
-  if (aniso_phase())
-    throw std::runtime_error("mixing_rule reuss is not available with aniso (3 x 3 conductivity) phases (the harmonic mean is "
-                             "written for isotropic phases)");
-  if (dfg())
-    throw std::runtime_error("mixing_rule reuss is not available with gamma_scheme full_staggered / half_staggered (the five "
-                             "moduli of the doubly fine grid are arithmetic means)");
-  if (opt_.method == 2) throw std::runtime_error("method polarization supports mixing_rule voigt only (not laminate)");
-  if (opt_.error_estimator == 3)
-    throw std::runtime_error("error_estimator energy is not available with mixing_rule reuss (Reuss MaterialLaw energy not implemented)");
-  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("mixing_rule reuss is not available on slab-decomposed solvers");
-  for (int p = 0; p < pt_.n; ++p) {
-    const bool bad = opt_.mode == 0 ? !(2 * pt_.mu[p] > 0 && 2 * pt_.mu[p] + 3 * pt_.lambda[p] > 0) : !(pt_.mu[p] > 0);
-    if (bad)
-      throw std::runtime_error(opt_.mode == 0 ? "mixing_rule reuss needs 2 mu > 0 and 2 mu + 3 lambda > 0 in every phase (the "
-                                                "inversion of the phase stiffness fails otherwise)"
-                                              : "mixing_rule reuss needs mu > 0 in every phase (the inversion of the phase "
-                                                "constant fails otherwise)");
-  }
-}
-
-// the tiled sweep of two complementary phases forms the harmonic means itself (k_u_tile REUSS); option reuss_sweep = 0: the
-// two moduli arrays (A/B runs)
-bool Solver::reuss_sweep_ok() {
-  return opt_.reuss_sweep && opt_.mixing == kMixReuss && opt_.mode == 0 && two_phase_complementary();
-}
-
-bool Solver::aniso_tile_ok() {
-  return opt_.aniso_tile && opt_.mode == 0 && opt_.gamma_scheme == 0 && opt_.mixing == kMixVoigt && opt_.u_loop >= 2 && opt_.u_tile &&
-         nranks_ == 1 && !slab_layout_ && u_tile_supported(g_) && two_phase_complementary();
-}
-
-// aniso phases of the scalar modes: k_sc_tile_aniso serves two complementary phases on the grids the tiled sweep takes; mixed
-// boundary conditions (no form with the sums of tau) and everything else run the exact-order sweep
-bool Solver::sc_tile_aniso_ok(bool mixed_bc) {
-  return opt_.aniso_sc_tile && opt_.mode == 1 && aniso_phase() && opt_.u_loop >= 2 && opt_.u_tile && !mixed_bc && nranks_ == 1 &&
-         !slab_layout_ && sc_sweep_tiled(g_) && two_phase_complementary(true);
-}
-
 void Solver::sc_aniso_constants(double* K0, double* K1) const {
   for (int p = 0; p < 2; ++p) {
     double* K = p ? K1 : K0;
@@ -1241,24 +1171,10 @@ void Solver::sc_aniso_constants(double* K0, double* K1) const {
   }
 }
 
-void Solver::willot_check() const {
-  if (opt_.mode == 1)
-    throw std::runtime_error("gamma_scheme willot is not available in heat / porous mode (the reference has no such operator)");
-  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("gamma_scheme willot is not available on slab-decomposed solvers");
-}
-
-void Solver::dfg_check() const {
-  if (opt_.mode == 1)
-    throw std::runtime_error("gamma_scheme full_staggered is not available in heat / porous mode (the reference's 3-component "
-                             "prolongation uses another grid convention)");
-  if (opt_.mixing != kMixVoigt)
-    throw std::runtime_error("gamma_scheme full_staggered supports Voigt mixing only (the laminate split is not linear in phi and "
-                             "needs normals on the fine grid)");
-  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("full_staggered is not available on slab-decomposed solvers");
-}
-
 FieldPtrs<5> Solver::dfg_moduli() {
-  dfg_check();
+  plan::PlanInput in;   // (what dfg_refusal reads)
+  in.gamma_scheme = opt_.gamma_scheme, in.mode = opt_.mode, in.mixing = opt_.mixing, in.slab = nranks_ != 1 || slab_layout_;
+  if (const char* refusal = plan::dfg_refusal(in)) throw std::runtime_error(refusal);
   if (!mod5_) {
     FG_HIP_CHECK(hipMalloc(&mod5_, 5 * (size_t)g_.n * sizeof(double)));
     mod5_dirty_ = true;
@@ -1314,7 +1230,38 @@ void Solver::build_laminate_lists() {
   mixed_dirty_ = false;
 }
 
+// laminate mixing = the Voigt sweep over all voxels + the divergence of (tau_laminate - tau_voigt), which lives on the interface
+// voxels (lists built once per geometry, see k_interface_strain).  d depends on u only: its two kernels (a light gather, a short
+// solve) run on a second stream beside the sweep (option laminate_overlap).  Fork: u_k is complete, the previous pass is done with d
+void Solver::laminate_fork() {
+  build_laminate_lists();
+  if (!opt_.laminate_overlap) return;
+  if (!aux_stream_) {
+    int lo = 0, hi = 0;
+    FG_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));   // hi = numerically lowest = highest priority
+    FG_HIP_CHECK(hipStreamCreateWithPriority(&aux_stream_, hipStreamNonBlocking, hi));
+    FG_HIP_CHECK(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
+    FG_HIP_CHECK(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
+  }
+  FG_HIP_CHECK(hipEventRecord(ev_fork_, stream_));
+}
+
+void Solver::laminate_correction(const Vec6& E) {
+  hipStream_t ds = opt_.laminate_overlap ? aux_stream_ : stream_;
+  if (ds != stream_) FG_HIP_CHECK(hipStreamWaitEvent(ds, ev_fork_, 0));
+  launch_interface_delta(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs3(fu_), E, mixed_list_, mixed_n_, lam_epsc_,
+                         lam_phic_, lam_nrmc_, dtau_, derr_, ds);
+  if (ds != stream_) {
+    FG_HIP_CHECK(hipEventRecord(ev_join_, ds));
+    FG_HIP_CHECK(hipStreamWaitEvent(stream_, ev_join_, 0));
+  }
+  launch_delta_div(g_, aff_list_, aff_slots_, aff_n_, dtau_, ptrs3(fu_alt_), stream_);
+  if (mixed_bc())   // mixed BC: <tau_laminate> = <tau_voigt> (from the sweep) + sum of the differences / N
+    launch_sum_dtau(dtau_, mixed_n_, partial_, dscal_ + kSlotScratch, stream_);
+}
+
 void Solver::u_pass_front(const double* E6) {
+  using plan::Front;
   const FieldPtrs<kMaxPhases> phi = phase_ptrs();
   // the strain that belongs to u_k was built with the prescribed strain of ITS pass (E_cur_);
   // E6 is the prescribed strain of the pass being started and takes effect with u_{k+1}
@@ -1323,99 +1270,80 @@ void Solver::u_pass_front(const double* E6) {
     E.v[c] = E_cur_[c];
     E_next_[c] = E6[c];
   }
+  const plan::SweepPlan sweeps = sweep_plan();
+  const bool sum_tau = sweeps.sum_tau;   // mixed BC: sums of tau land in kSlotMean
+  const StressParams sp = stress_params(opt_.mu_0, opt_.lambda_0, 1.0);
+  const PhaseTable t = phase_table();
+  FieldPtrs<2> ph;   // two phases with phi_0 = 1 - phi_1: the sweep reads phi_1 and forms the moduli itself (8 B per voxel less)
+  ph.p[0] = phi_ + g_.n;
+  ph.p[1] = nullptr;
+  double K0[6], K1[6];
   time_begin(0);
-  if (opt_.mode == 1) {
-    if (opt_.u_loop >= 2 && !aniso_phase()) {
-      // fast variant: effective conductivity a = sum_p phi_p mu_p precomputed (first moduli array); an aniso phase has no
-      // such array and takes the exact-order sweep's 13-point form
-      const bool mixed = mixed_bc() && in_run_;
-      sc_tau_sums_ = launch_sc_sweep_fast(g_, opt_.mu_0, fu_, effective_moduli().p[0], fu_alt_, E, partial_, dscal_ + kSlotSumSq,
-                                          stream_, mixed ? dscal_ + kSlotMean : nullptr);
-    } else if (sc_tile_aniso_ok(mixed_bc() && in_run_)) {
-      double K0[6], K1[6];
+  if (sweeps.laminate_correction) laminate_fork();
+  switch (sweeps.front) {
+    case Front::ScFast:   // effective conductivity a = sum_p phi_p mu_p precomputed (first moduli array)
+      sc_tau_sums_ = launch_sc_sweep_fast(g_, opt_.mu_0, fu_, effective_moduli().p[0], fu_alt_, E, partial_, dscal_ + kSlotSumSq, stream_,
+                                          sum_tau ? dscal_ + kSlotMean : nullptr);
+      front_sweep_ = (long)Front::ScFast;
+      break;
+    case Front::ScTileAniso:
       sc_aniso_constants(K0, K1);
       sc_tau_sums_ = false;
       launch_sc_tile_aniso(g_, opt_.mu_0, K0, K1, fu_, phi_ + g_.n, fu_alt_, E, partial_, dscal_ + kSlotSumSq, stream_);
       ++sc_tile_aniso_;
-    } else {
+      front_sweep_ = (long)Front::ScTileAniso;
+      break;
+    case Front::ScExact:   // (an aniso phase has no conductivity array: the 13-point form of the exact-order sweep)
       sc_tau_sums_ = false;
-      launch_sc_sweep(g_, scalar_params(opt_.mu_0, 1.0), fu_, phase_ptrs(), fu_alt_, E, partial_, dscal_ + kSlotSumSq, stream_);
-    }
-  } else if (opt_.mixing != kMixVoigt && opt_.u_loop < 2) {
-    // laminate / Reuss mixing, exact order: strain + polarisation from u in one sweep (tau stored), divergence as its own sweep
-    launch_u_stress(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs3(fu_), phi, normal_ptrs(), ptrs6(tau_), E, partial_,
-                    dscal_ + kSlotSumSq, derr_, stream_);
-    time_end(0);
-    time_begin(1);
-    launch_div(g_, ptrs6(tau_), ptrs3(fu_alt_), kNoXHalo, stream_);
-    time_end(1);
-    eps_stale_ = true;
-    return;
-  } else if (opt_.u_loop >= 2) {
-    // fast variant: per-voxel effective moduli instead of the per-phase accumulation (computed once per geometry, on
-    // first use: the tiled sweep of two complementary phases does without them)
-    const bool laminate = opt_.mixing == kMixLaminate;
-    if (laminate) {
-      build_laminate_lists();
-      if (opt_.laminate_overlap) {   // fork: u_k is complete, the previous pass is done with d
-        if (!aux_stream_) {
-          int lo = 0, hi = 0;
-          FG_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));   // hi = numerically lowest = highest priority
-          FG_HIP_CHECK(hipStreamCreateWithPriority(&aux_stream_, hipStreamNonBlocking, hi));
-          FG_HIP_CHECK(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
-          FG_HIP_CHECK(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-        }
-        FG_HIP_CHECK(hipEventRecord(ev_fork_, stream_));
-      }
-    }
-    if (opt_.u_tile && u_tile_supported(g_)) {
-      const bool sum_tau = mixed_bc();   // mixed BC: sums of tau land in kSlotMean
-      if (dfg()) {   // full_staggered: the five moduli, also for two complementary phases
-        launch_u_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), dfg_moduli(), ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq,
-                      stream_, sum_tau);
-      } else if (general_phase()) {   // u_loop_eligible: two complementary phases
-        launch_u_tile_aniso(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), phi_ + g_.n, ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq,
-                            stream_, sum_tau, phase_table());
-        ++u_tile_aniso_;
-      } else if (opt_.mixing == kMixReuss ? reuss_sweep_ok() : two_phase_complementary()) {
-        // two phases with phi_0 = 1 - phi_1: the sweep reads phi_1 and forms the moduli itself (8 B per voxel less)
-        FieldPtrs<2> ph;
-        ph.p[0] = phi_ + g_.n;
-        ph.p[1] = nullptr;
-        const PhaseTable t = phase_table();
-        const bool reuss = opt_.mixing == kMixReuss;
-        launch_u_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), ph, ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq, stream_, sum_tau,
-                      &t, reuss);
-        if (reuss) ++u_tile_reuss_;
-      } else {
-        launch_u_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), effective_moduli(), ptrs3(fu_alt_), E, partial_,
-                      dscal_ + kSlotSumSq, stream_, sum_tau);
-      }
-    } else if (dfg()) {   // u_loop_eligible admits full_staggered on tiled grids only
-      throw std::logic_error("full_staggered: the untiled displacement sweep has no five-moduli form");
-    } else   // grids the tiles do not fit (odd nz, short rows): the untiled sweep
-      launch_u_fast(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), effective_moduli(), ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq,
-                    stream_);
-    if (laminate) {
-      // laminate mixing = the Voigt sweep over all voxels + the divergence of (tau_laminate - tau_voigt), which lives
-      // on the interface voxels (lists built once per geometry, see k_interface_strain)
-      // d depends on u only: its two kernels (a light gather, a short solve) run on a second stream beside the sweep
-      hipStream_t ds = opt_.laminate_overlap ? aux_stream_ : stream_;
-      if (ds != stream_) FG_HIP_CHECK(hipStreamWaitEvent(ds, ev_fork_, 0));
-      launch_interface_delta(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs3(fu_), E, mixed_list_, mixed_n_, lam_epsc_,
-                             lam_phic_, lam_nrmc_, dtau_, derr_, ds);
-      if (ds != stream_) {
-        FG_HIP_CHECK(hipEventRecord(ev_join_, ds));
-        FG_HIP_CHECK(hipStreamWaitEvent(stream_, ev_join_, 0));
-      }
-      launch_delta_div(g_, aff_list_, aff_slots_, aff_n_, dtau_, ptrs3(fu_alt_), stream_);
-      if (mixed_bc())   // mixed BC: <tau_laminate> = <tau_voigt> (from the sweep) + sum of the differences / N
-        launch_sum_dtau(dtau_, mixed_n_, partial_, dscal_ + kSlotScratch, stream_);
-    }
-  } else {
-    launch_u_stress_div_voigt(g_, stress_params(opt_.mu_0, opt_.lambda_0, 1.0), ptrs3(fu_), phi, ptrs3(fu_alt_), E,
-                              partial_, dscal_ + kSlotSumSq, stream_);
+      launch_sc_sweep(g_, scalar_params(opt_.mu_0, 1.0), fu_, phi, fu_alt_, E, partial_, dscal_ + kSlotSumSq, stream_);
+      front_sweep_ = (long)Front::ScExact;
+      break;
+    case Front::UStressThenDiv:
+      // laminate / Reuss mixing, exact order: strain + polarisation from u in one sweep (tau stored), divergence as its own sweep
+      launch_u_stress(g_, sp, ptrs3(fu_), phi, normal_ptrs(), ptrs6(tau_), E, partial_, dscal_ + kSlotSumSq, derr_, stream_);
+      time_end(0);
+      time_begin(1);
+      launch_div(g_, ptrs6(tau_), ptrs3(fu_alt_), kNoXHalo, stream_);
+      time_end(1);
+      front_sweep_ = (long)Front::UStressThenDiv;
+      eps_stale_ = true;
+      return;
+    case Front::UTileDfg:   // full_staggered: the five moduli, also for two complementary phases
+      launch_u_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), dfg_moduli(), ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq, stream_, sum_tau);
+      front_sweep_ = (long)Front::UTileDfg;
+      break;
+    case Front::UTileAniso:
+      launch_u_tile_aniso(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), phi_ + g_.n, ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq, stream_,
+                          sum_tau, t);
+      ++u_tile_aniso_;
+      front_sweep_ = (long)Front::UTileAniso;
+      break;
+    case Front::UTilePhi:
+      launch_u_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), ph, ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq, stream_, sum_tau, &t, false);
+      front_sweep_ = (long)Front::UTilePhi;
+      break;
+    case Front::UTilePhiReuss:
+      launch_u_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), ph, ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq, stream_, sum_tau, &t, true);
+      ++u_tile_reuss_;
+      front_sweep_ = (long)Front::UTilePhiReuss;
+      break;
+    case Front::UTileModuli:   // per-voxel effective moduli instead of the per-phase accumulation (once per geometry, on first use)
+      launch_u_tile(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), effective_moduli(), ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq, stream_,
+                    sum_tau);
+      front_sweep_ = (long)Front::UTileModuli;
+      break;
+    case Front::UFastModuli:   // grids the tiles do not fit (odd nz, short rows): the untiled sweep
+      launch_u_fast(g_, opt_.mu_0, opt_.lambda_0, ptrs3(fu_), effective_moduli(), ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq, stream_);
+      front_sweep_ = (long)Front::UFastModuli;
+      break;
+    case Front::UStressDivVoigt:
+      launch_u_stress_div_voigt(g_, sp, ptrs3(fu_), phi, ptrs3(fu_alt_), E, partial_, dscal_ + kSlotSumSq, stream_);
+      front_sweep_ = (long)Front::UStressDivVoigt;
+      break;
+    case Front::None:
+      throw std::logic_error("u_pass_front: this configuration has no displacement / potential loop");
   }
+  if (sweeps.laminate_correction) laminate_correction(E);
   time_end(0);
   eps_stale_ = true;
 }
@@ -1447,20 +1375,16 @@ void Solver::ensure_eps() {
 
 void Solver::iterate(const double* E6, int n) {
   FG_HIP_CHECK(hipSetDevice(device_));
-  reuss_check();
-  if (dfg()) dfg_check();
-  if (willot()) willot_check();
-  general_check();
+  require_plan(plan::Entry::Iterate);
   int i = 0;
   if (opt_.method == 2) {   // the polarisation loop: from P = 4 mu_0 E unless a polarisation state is there already
-    polar_check();
     if (pol_state_ && opt_.mu_0 != pol_mu0_) ensure_eps();   // the reference material changed: that state is of another operator
     if (!pol_state_) polar_start(E6);
     for (; i < n; ++i) polar_pass(E6);
     return;
   }
   ensure_eps();   // a polarisation state left by method polarization becomes the strain before another method iterates on it
-  if (u_loop_eligible()) {
+  if (plan::plan_sweeps(plan_input(plan::Entry::Iterate, 1)).u_loop) {
     if (!u_valid_ && n > 0 && opt_.mode == 1) {
       // no potential yet: the zero gradient field is E = 0, T = 0
       FG_HIP_CHECK(hipMemsetAsync(fu_, 0, g_.n * sizeof(double), stream_));
@@ -1486,7 +1410,7 @@ void Solver::iterate(const double* E6, int n) {
 void Solver::mean_stress(double* out6) {
   FG_HIP_CHECK(hipSetDevice(device_));
   ensure_eps();
-  if (pt_.n < 1) throw std::runtime_error("No materials specified");
+  if (pt_.n < 1) throw std::runtime_error(plan::kNoMaterials);
   if (opt_.mode == 1) {
     launch_sc_flux_mean(g_, scalar_params(0.0, 1.0 / (double)nglobal_), ptrs3(eps_), phase_ptrs(), partial_,
                         dscal_ + kSlotMean, stream_);
@@ -1510,7 +1434,7 @@ void Solver::mean_stress(double* out6) {
 double Solver::mean_energy() {
   FG_HIP_CHECK(hipSetDevice(device_));
   ensure_eps();
-  if (pt_.n < 1) throw std::runtime_error("No materials specified");
+  if (pt_.n < 1) throw std::runtime_error(plan::kNoMaterials);
   if (opt_.mode == 1) throw std::runtime_error("the energy error estimator is not available in heat / porous mode");
   if (opt_.mixing == kMixReuss) throw std::runtime_error("Reuss MaterialLaw energy not implemented");   // F:12657-12661
   if (dfg())
@@ -1567,9 +1491,7 @@ double Solver::volume_fraction(int p) {
 // calcRefMaterial  F:22283-22313 -> getRefMaterial  F:12153-12236
 void Solver::calc_ref_material() {
   FG_HIP_CHECK(hipSetDevice(device_));
-  if (pt_.n < 1) throw std::runtime_error("No materials specified");
-  reuss_check();
-  general_check();
+  require_plan(plan::Entry::RefMaterial);
   if (opt_.mode == 1)
     launch_sc_minmax(g_, scalar_params(0.0, 1.0), phase_ptrs(), partial_, dscal_ + kSlotMinMax, stream_);
   else
@@ -1705,7 +1627,7 @@ double Solver::current_norm9() {
 bool Solver::run_load_steps(const double* E6, const double* S6, const double* params, int nparams, int first,
                             LoadstepCallback step_cb, void* user) {
   FG_HIP_CHECK(hipSetDevice(device_));
-  if (pt_.n < 1) throw std::runtime_error("No materials specified");
+  if (pt_.n < 1) throw std::runtime_error(plan::kNoMaterials);
   if (nparams < 1 || first < 0 || !params) throw std::runtime_error("invalid load steps");
   solve_time_ = 0.0;
   cg_u_active_ = false;
@@ -1799,30 +1721,18 @@ bool Solver::run_load_steps(const double* E6, const double* S6, const double* pa
 
 // runSolver  F:21400-21433 for one load step
 bool Solver::run_one_step(const double* E0, const double* S0) {
-  reuss_check();
-  if (dfg()) dfg_check();
-  if (willot()) willot_check();
-  general_check();
-  if (opt_.method == 2) polar_check();
+  require_plan(plan::Entry::Run);
   // EpsilonErrorEstimator  F:14591-14637: constructed on the field the step starts from (zero for the first step)
   const double prev0 = fresh_step_ ? 0.0 : current_norm9();
-  if (opt_.error_estimator >= 2) {
-    if (opt_.mode == 1) throw std::runtime_error("heat / porous mode supports the error estimators epsilon and residual");
-    estimator_begin(fresh_step_);
-  }
-  if (opt_.method == 1 && opt_.mode == 1) {
-    (void)u_loop_eligible();   // throws for configurations the scalar modes do not support
-    return run_cg_scalar(E0, prev0);
-  }
+  if (opt_.error_estimator >= 2) estimator_begin(fresh_step_);
+  if (opt_.method == 1 && opt_.mode == 1) return run_cg_scalar(E0, prev0);
   if (opt_.method == 1) return run_cg(E0, S0, prev0);
   if (opt_.method == 2) return run_polarization(E0, S0, prev0);
-  if (opt_.error_estimator == 1)   // ErrorEstimator::update  F:14359
-    throw std::runtime_error("Selected error estimator is not compatible with the selected solution method");
   const double t_start = now_seconds();
   for (int i = 0; i < 6; ++i) F00_[i] = 0.0;
   // Displacement-based loop: eps_0 = 0 gives tau = 0, u_1 = 0 and eps_1 = E, so the loop starts from
   // u = 0 and every pass is [u_k -> norms of eps_k, f_{k+1}] + [f_{k+1} -> u_{k+1}] (see u_pass_front).
-  bool uloop = u_loop_eligible(true);
+  bool uloop = plan::plan_sweeps(plan_input(plan::Entry::Run, 1)).u_loop;
   const bool mixed_bc = this->mixed_bc();   // (NaN until calcRefMaterial ran: Q != 0)
   if (uloop && fresh_step_) {
     FG_HIP_CHECK(hipMemsetAsync(fu_, 0, 3 * g_.n * sizeof(double), stream_));
@@ -1917,20 +1827,6 @@ bool Solver::run_one_step(const double* E0, const double* S0) {
 // method "polarization": Eyre & Milton's scheme as runPolarization F:21808-21851 drives it.  The state is the polarisation
 // P = (C + C0) : eps with C0 = 2 mu_0 Id, held in eps_ (pol_state_); one pass is polarizationScheme F:20536-20554:
 //   Q = (C - C0)(C + C0)^-1 P per voxel,  P00 = <Q>,  P_hat = -4 mu_0 Gamma0_hat : Q_hat + Q_hat,  P_hat(0) = P00 + 4 mu_0 E.
-void Solver::polar_check() const {
-  if (nranks_ != 1 || slab_layout_) throw std::runtime_error("method polarization is not available on slab-decomposed solvers");
-  if (opt_.mode != 0) throw std::runtime_error("method polarization is available in mode elasticity only (not heat / porous / viscosity)");
-  if (opt_.mixing != kMixVoigt) throw std::runtime_error("method polarization supports mixing_rule voigt only (not laminate)");
-  if (dfg()) throw std::runtime_error("method polarization is not available with gamma_scheme full_staggered / half_staggered");
-  if (opt_.error_estimator != 0 && opt_.error_estimator != 4)
-    throw std::runtime_error("method polarization supports error_estimator epsilon and none only (not sigma / energy / residual: "
-                             "the loop's field is the polarisation, not the strain)");
-  if (frobenius(BC_Q_) != 0.0)   // Q = Id - P != 0  <=>  |MQ| >= eps
-    throw std::runtime_error("method polarization supports pure-strain boundary conditions only (bc_projector = identity; the "
-                             "reference switches the mixed check off)");
-  if (opt_.bc_relax != 1.0) throw std::runtime_error("method polarization supports bc_relax = 1 only");
-}
-
 void Solver::polar_start(const double* E6) {
   Vec6 P0;
   for (int c = 0; c < 6; ++c) P0.v[c] = 4 * opt_.mu_0 * E6[c];
@@ -1942,7 +1838,7 @@ void Solver::polar_start(const double* E6) {
 }
 
 void Solver::polar_pass(const double* E6) {
-  if (pt_.n < 1) throw std::runtime_error("No materials specified");
+  if (pt_.n < 1) throw std::runtime_error(plan::kNoMaterials);
   const double mu_0 = opt_.mu_0, alpha = -4 * mu_0;   // GammaOperator(P00 + P0, ..., -4 mu_0, 1)  F:20553
   Vec6 P0;
   for (int c = 0; c < 6; ++c) P0.v[c] = 4 * mu_0 * E6[c];   // F:21836
@@ -2029,8 +1925,8 @@ bool Solver::run_cg_u(const double* E0, double prev0) {
   // norms of the new eps and r:r (mode 1) -- and the direction update p = r + beta p is formed inside the operator's
   // displacement sweep (launch_u_tile_cg).  Updates are out of place (the tiles' halo rows re-evaluate them), so u_e, u_r and
   // u_p alternate between two buffers each; fu_ stays the current iterate.
-  const int fused_opt = opt_.cg_fused;
-  bool fused = fused_opt != 0 && opt_.u_tile && u_tile_supported(g_) && !slab_layout_;
+  const plan::SweepPlan sweeps = plan::plan_sweeps(plan_input(plan::Entry::Run, 2));
+  bool fused = sweeps.cg_fused_wanted;
   if (fused && (!cg_p_ || !fu_cg_)) {
     // nine more components (the alternates of u_e, u_r, u_p): on grids that fill the card (1024^3: 78 GB) the four-kernel form
     size_t free_b = 0, total_b = 0;
@@ -2038,7 +1934,7 @@ bool Solver::run_cg_u(const double* E0, double prev0) {
     const size_t need = (cg_p_ ? 0 : 2 * f3) + (fu_cg_ ? 0 : f3);
     if (free_b < need + (size_t)(0.02 * (double)total_b)) fused = false;
   }
-  const bool fused_dir = fused && opt_.mixing != kMixLaminate;   // laminate mixing: the interface kernels read u_p as a stored field
+  const bool fused_dir = fused && sweeps.cg_fused_dir;   // laminate mixing: the interface kernels read u_p as a stored field
   double *r_alt = nullptr, *p_alt = nullptr;
   if (fused) {
     if (!cg_p_) FG_HIP_CHECK(hipMalloc(&cg_p_, 2 * f3));
@@ -2056,38 +1952,38 @@ bool Solver::run_cg_u(const double* E0, double prev0) {
   auto apply = [&](double* u_in, const double* Eadd) { cg_apply(u_in, Eadd, tau_); };
   // fused form: u_p := u_r + beta u_p (beta from the sums at dscal_[i_num] / dscal_[i_den]) inside the sweep of the operator
   auto apply_dir = [&](int i_num, int i_den) {
-    if (dfg()) {
-      time_begin(0);
-      launch_u_tile_cg(g_, opt_.mu_0, opt_.lambda_0, ptrs3(u_p), ptrs3(u_r), ptrs3(p_alt), dfg_moduli(), ptrs3(fu_alt_), Z, dscal_,
-                       i_num, i_den, (double)nglobal_, std::numeric_limits<double>::min(), partial_, dscal_ + kSlotSumSq, stream_);
-      time_end(0);
-      fft_g0_chain(fu_alt_, -1.0, nullptr, tau_);
-      std::swap(u_p, p_alt);
-      return;
-    }
-    FieldPtrs<2> m;
+    using plan::Front;
     const PhaseTable t = phase_table();
-    if (general_phase()) {
-      time_begin(0);
-      launch_u_tile_aniso_cg(g_, opt_.mu_0, opt_.lambda_0, ptrs3(u_p), ptrs3(u_r), ptrs3(p_alt), phi_ + g_.n, ptrs3(fu_alt_), Z, dscal_,
-                             i_num, i_den, (double)nglobal_, std::numeric_limits<double>::min(), partial_, dscal_ + kSlotSumSq,
-                             stream_, t);
-      ++u_tile_aniso_;
-      time_end(0);
-      fft_g0_chain(fu_alt_, -1.0, nullptr, tau_);
-      std::swap(u_p, p_alt);
-      return;
-    }
-    const bool two = opt_.mixing != kMixReuss && two_phase_complementary();   // (Reuss mixing: the CG sweep reads the moduli arrays)
-    if (two) {
-      m.p[0] = phi_ + g_.n;
-      m.p[1] = nullptr;
-    } else {
-      m = effective_moduli();
-    }
+    const double tiny = std::numeric_limits<double>::min();
+    FieldPtrs<2> ph;   // two complementary phases: the sweep reads phi_1
+    ph.p[0] = phi_ + g_.n;
+    ph.p[1] = nullptr;
     time_begin(0);
-    launch_u_tile_cg(g_, opt_.mu_0, opt_.lambda_0, ptrs3(u_p), ptrs3(u_r), ptrs3(p_alt), m, ptrs3(fu_alt_), Z, dscal_, i_num, i_den,
-                     (double)nglobal_, std::numeric_limits<double>::min(), partial_, dscal_ + kSlotSumSq, stream_, two ? &t : nullptr);
+    switch (sweeps.cg_dir) {
+      case Front::UTileDfg:
+        launch_u_tile_cg(g_, opt_.mu_0, opt_.lambda_0, ptrs3(u_p), ptrs3(u_r), ptrs3(p_alt), dfg_moduli(), ptrs3(fu_alt_), Z, dscal_, i_num,
+                         i_den, (double)nglobal_, tiny, partial_, dscal_ + kSlotSumSq, stream_);
+        cg_dir_sweep_ = (long)Front::UTileDfg;
+        break;
+      case Front::UTileAniso:
+        launch_u_tile_aniso_cg(g_, opt_.mu_0, opt_.lambda_0, ptrs3(u_p), ptrs3(u_r), ptrs3(p_alt), phi_ + g_.n, ptrs3(fu_alt_), Z, dscal_,
+                               i_num, i_den, (double)nglobal_, tiny, partial_, dscal_ + kSlotSumSq, stream_, t);
+        ++u_tile_aniso_;
+        cg_dir_sweep_ = (long)Front::UTileAniso;
+        break;
+      case Front::UTilePhi:
+        launch_u_tile_cg(g_, opt_.mu_0, opt_.lambda_0, ptrs3(u_p), ptrs3(u_r), ptrs3(p_alt), ph, ptrs3(fu_alt_), Z, dscal_, i_num, i_den,
+                         (double)nglobal_, tiny, partial_, dscal_ + kSlotSumSq, stream_, &t);
+        cg_dir_sweep_ = (long)Front::UTilePhi;
+        break;
+      case Front::UTileModuli:   // (Reuss mixing: the CG sweep reads the moduli arrays)
+        launch_u_tile_cg(g_, opt_.mu_0, opt_.lambda_0, ptrs3(u_p), ptrs3(u_r), ptrs3(p_alt), effective_moduli(), ptrs3(fu_alt_), Z, dscal_,
+                         i_num, i_den, (double)nglobal_, tiny, partial_, dscal_ + kSlotSumSq, stream_, nullptr);
+        cg_dir_sweep_ = (long)Front::UTileModuli;
+        break;
+      default:
+        throw std::logic_error("run_cg_u: no direction sweep for this configuration");
+    }
     time_end(0);
     fft_g0_chain(fu_alt_, -1.0, nullptr, tau_);
     std::swap(u_p, p_alt);
@@ -2168,10 +2064,10 @@ bool Solver::run_cg_scalar(const double* E0, double prev0) {
   // Fused form (option cg_fused; as in run_cg_u, cg_pipelined with the direction inside the operator's sweep).  Out of place:
   // T_e, T_r, T_p alternate between two components each (the spare components of fu_ and cg_r_).  Not with a convergence
   // callback (accessors read fu_'s first component in between).
-  const int fused_opt = opt_.cg_fused;
   const double nvox = (double)nglobal_;
-  const bool aniso = aniso_phase();   // the fused form needs the tiled sweep: for aniso phases its two-phase form
-  if (fused_opt != 0 && !cb_ && opt_.u_loop >= 2 && sc_sweep_tiled(g_) && !slab_layout_ && (!aniso || sc_tile_aniso_ok(false))) {
+  const plan::SweepPlan sweeps = sweep_plan();
+  const bool aniso = sweeps.cg_dir == plan::Front::ScTileAniso;   // the fused form needs the tiled sweep: for aniso phases its two-phase form
+  if (sweeps.cg_fused_wanted && !cb_) {
     const CgSlots slot = cg_slots(kSlotCg);
     double *e_cur = fu_, *e_alt = fu_ + g_.n, *r_cur = T_r, *r_alt = cg_r_ + 2 * g_.n, *p_cur = T_p, *p_alt = cg_r_ + 3 * g_.n;
     const double* cond = aniso ? nullptr : effective_moduli().p[0];
@@ -2191,9 +2087,11 @@ bool Solver::run_cg_scalar(const double* E0, double prev0) {
         launch_sc_tile_aniso(g_, opt_.mu_0, K0, K1, p_cur, phi_ + g_.n, fu_alt_, Z, partial_, dscal_ + kSlotSumSq, stream_, r_cur, p_alt,
                              dscal_, num, den, nvox, small);
         ++sc_tile_aniso_;
+        cg_dir_sweep_ = (long)plan::Front::ScTileAniso;
       } else {
         launch_sc_sweep_cg(g_, opt_.mu_0, p_cur, r_cur, p_alt, cond, fu_alt_, Z, dscal_, num, den, nvox, small, partial_,
                            dscal_ + kSlotSumSq, stream_);
+        cg_dir_sweep_ = (long)plan::Front::ScFast;
       }
       time_end(0);
       fft_g0_chain(fu_alt_);
@@ -2255,9 +2153,8 @@ bool Solver::run_cg_scalar(const double* E0, double prev0) {
 }
 
 bool Solver::run_cg(const double* E0, const double* S0, double prev0) {
-  if (nranks_ != 1) throw std::runtime_error("slab-decomposed solvers run method=cg under the slab driver (fg_slab.hip)");
-  // (the estimators that measure a mean of the strain field run in strain space, where the iterate is a stored field)
-  if (opt_.u_loop >= 2 && u_loop_eligible() && norm2(S0, 6) == 0.0 && opt_.error_estimator < 2) return run_cg_u(E0, prev0);
+  // (prescribed stresses run in strain space, like the estimators that measure a mean of the strain field)
+  if (plan::plan_sweeps(plan_input(plan::Entry::Run, 1)).cg == plan::Cg::DisplacementSpace && norm2(S0, 6) == 0.0) return run_cg_u(E0, prev0);
   const double t_start = now_seconds();
   const size_t f6 = 6 * (size_t)g_.n * sizeof(double);
   for (double** b : {&cg_r_, &cg_p_, &cg_w_})
@@ -2340,7 +2237,7 @@ void Solver::run_stage(int stage, const double* E6) {
   const double* E = E6 ? E6 : zero6;
   switch (stage) {
     case kStageStress:
-      if (pt_.n < 1) throw std::runtime_error("No materials specified");
+      if (pt_.n < 1) throw std::runtime_error(plan::kNoMaterials);
       stress_to_tau(stress_params(opt_.mu_0, opt_.lambda_0, 1.0), eps_);
       check_device_error("stress");
       break;
@@ -2491,7 +2388,7 @@ void Solver::get_field(const std::string& name, double* out) {
     return;
   }
   if (opt_.mode == 1 && name == "sigma") {  // calcStress with C0 = 0  F:15496-15508: the flux
-    if (pt_.n < 1) throw std::runtime_error("No materials specified");
+    if (pt_.n < 1) throw std::runtime_error(plan::kNoMaterials);
     launch_sc_flux(g_, scalar_params(0.0, 1.0), ptrs3(eps_), phase_ptrs(), ptrs3(tau_), stream_);
     download_unpadded(tau_, out, 3, g_.n);
     return;
@@ -2507,7 +2404,7 @@ void Solver::get_field(const std::string& name, double* out) {
     return;
   }
   if (name == "sigma") {  // calcStress with C0 = 0  F:15496-15508
-    if (pt_.n < 1) throw std::runtime_error("No materials specified");
+    if (pt_.n < 1) throw std::runtime_error(plan::kNoMaterials);
     stress_to_tau(stress_params(0.0, 0.0, 1.0), eps_);
     check_device_error("sigma");
     download_unpadded(tau_, out, 6, g_.n);

@@ -307,7 +307,7 @@ class FG:
                                "laminate split is not linear in phi)" % (scheme, mixing))
 
         # method polarization (runPolarization F:21808-21851): what it does not cover is refused before a solver exists, in the
-        # wording of the solver library (Solver::polar_check); the boundary conditions are checked in run_load_case
+        # wording of the solver library (polar_refusal in csrc/fg_sweep_plan.h); the boundary conditions are checked in run_load_case
         if method == "polarization":
             if getattr(self, "_slabs", False):
                 raise RuntimeError(POLARIZATION_ERRORS["slab"])
@@ -320,7 +320,7 @@ class FG:
             if est not in ("epsilon", "none"):
                 raise RuntimeError(POLARIZATION_ERRORS["estimator"])
         # law="general" (a constant 6x6 stiffness): what it does not cover is refused before a solver exists, in the wording of
-        # the solver library (Solver::general_check)
+        # the solver library (law_refusal in csrc/fg_sweep_plan.h)
         mats_el = solver.find("materials") if solver is not None else None
         if mats_el is not None and any(isinstance(m.tag, str) and m.tag != "ref" and m.attrib.get("law", "iso") == "general"
                                        for m in mats_el):
@@ -435,7 +435,7 @@ class FG:
 
     def _check_reuss(self, solver, mode, method, dfg, est):
         """mixing_rule reuss (ReussMixedMaterialLaw F:12651-12724): what it does not cover is refused before a solver exists, in
-        the wording of the solver library (Solver::reuss_check)"""
+        the wording of the solver library (reuss_refusal in csrc/fg_sweep_plan.h)"""
         mats = solver.find("materials") if solver is not None else None
         phases = [m for m in (mats if mats is not None else []) if isinstance(m.tag, str) and m.tag != "ref"]
         laws = [m.attrib.get("law", "iso") for m in phases]

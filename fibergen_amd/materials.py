@@ -80,7 +80,7 @@ def material_constants(attrs, evaluate=float):
     return {"K": r["K"], "E": r["E"], "lambda": r["lam"], "mu": r["mu"], "nu": r["nu"], "M": r["M"]}
 
 
-# law="general": the combinations it does not cover, in the wording of the solver library (Solver::general_check)
+# law="general": the combinations it does not cover, in the wording of the solver library (law_refusal in csrc/fg_sweep_plan.h)
 GENERAL_MODE_ERROR = "general (anisotropic) phases are available in elasticity mode only"
 GENERAL_MIXING_ERROR = ("general (anisotropic) phases support Voigt mixing only (the laminate split is written for isotropic "
                         "phases)")

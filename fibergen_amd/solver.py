@@ -19,7 +19,7 @@ MIXING = {"voigt": 0, "laminate": 1, "reuss": 2}
 # reference's "basic+el" and "nesterov" are experiments and stay unknown here
 METHODS = {"basic": 0, "cg": 1, "polarization": 2}
 
-# what method polarization does not cover, in the wording of the solver library (Solver::polar_check)
+# what method polarization does not cover, in the wording of the solver library (polar_refusal in csrc/fg_sweep_plan.h)
 POLARIZATION_ERRORS = {
     "slab": "method polarization is not available on slab-decomposed solvers",
     "mode": "method polarization is available in mode elasticity only (not heat / porous / viscosity)",
@@ -31,7 +31,7 @@ POLARIZATION_ERRORS = {
            "reference switches the mixed check off)"),
 }
 
-# what mixing_rule reuss does not cover, in the wording of the solver library (Solver::reuss_check)
+# what mixing_rule reuss does not cover, in the wording of the solver library (reuss_refusal in csrc/fg_sweep_plan.h)
 REUSS_ERRORS = {
     "general": "general (anisotropic) phases support Voigt mixing only (the laminate split is written for isotropic phases)",
     "aniso": ("mixing_rule reuss is not available with aniso (3 x 3 conductivity) phases (the harmonic mean is written for "
@@ -267,7 +267,10 @@ class LSSolver:
         "fft_bluestein_m_x|y|z" (padded length of the axis' Bluestein pass, 0 = not on Bluestein), "phase_uploads" (host
         arrays received by set_phase / set_phase_fine / set_normals), "u_tile_aniso" (launches of the tiled sweep's anisotropic
         form), "sc_tile_aniso" (launches of the tiled scalar sweep's aniso form), "polarization_generic_voxels" (method
-        polarization: voxels that took the 6 x 6 solve in the last forward pass); -1 = unknown name."""
+        polarization: voxels that took the 6 x 6 solve in the last forward pass), "front_sweep" / "cg_dir_sweep" (the sweep the
+        last pass of the displacement / potential loop / the last direction sweep of a fused CG form launched: plan::Front of
+        csrc/fg_sweep_plan.h, -1 before the first), "complement_checks" (launches of the device check phi_0 == 1 - phi_1);
+        -1 = unknown name."""
         return int(self._lib.fg_get_counter(self._h, name.encode()))
 
     def iterate(self, E, n):

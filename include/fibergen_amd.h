@@ -269,7 +269,10 @@ int fg_get_stage_timing_bias(const fg_solver* s, double* ms);
  * fg_set_normals (fg_voxelize_into adds none); "u_tile_reuss" = launches of the tiled sweep's in-sweep harmonic form (mixing_rule reuss,
  * option reuss_sweep); "u_tile_aniso" = launches of the tiled sweep's anisotropic form (general
  * phases, option aniso_tile); "sc_tile_aniso" = launches of the tiled scalar sweep's aniso form (heat / porous, option
- * aniso_sc_tile).  Unknown names give -1. */
+ * aniso_sc_tile); "front_sweep" / "cg_dir_sweep" = which sweep the last pass of the displacement / potential loop, and the last
+ * direction sweep of a fused CG form, launched: the value of plan::Front in csrc/fg_sweep_plan.h (0 ScFast ... 10
+ * UStressDivVoigt), -1 before the first; "complement_checks" = launches of the device check "phi_0 == 1 - phi_1 bit for bit"
+ * (once per geometry, and only in configurations with a two-phase form of the sweep).  Unknown names give -1. */
 long fg_get_counter(const fg_solver* s, const char* name);
 
 /* Measurement helper (no counterpart in the reference): achieved HBM bandwidth of a streaming copy a = b and of the

@@ -376,11 +376,11 @@ def legal(x, c):
     if x == "set_field":
         return c.mode not in SCALAR_MODES                                   # "fields cannot be set in heat / porous mode"
     if x == "set_stiffness":
-        return el and c.mixing == "voigt"                                    # general_check
+        return el and c.mixing == "voigt"                                    # law_refusal (fg_sweep_plan.h)
     if x == "run_load_steps":
         return c.mode not in SCALAR_MODES and c.method != "polarization"    # (see above: not modelled)
     if x == "bc_projector":
-        return el and c.method != "polarization"                            # polar_check: pure strain only
+        return el and c.method != "polarization"                            # polar_refusal (fg_sweep_plan.h): pure strain only
     # the switches (mixing_rule, gamma_scheme, method, mode) are always legal: _draw picks among the values the
     # configuration admits (laminate: two isotropic complementary phases, not under polarization; polarization: Voigt, pure
     # strain, elasticity; collocated: not in viscosity; heat: staggered only)

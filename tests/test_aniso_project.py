@@ -151,11 +151,13 @@ def test_refused_on_slabs(fake):
 
 
 def test_messages_are_the_library_s():
-    src = open(os.path.join(ROOT, "fibergen_amd", "csrc", "fg_solver.hip")).read()
+    # the solver's setter and the slab driver's check_members raise the one constant of fg_sweep_plan.h
+    src = open(os.path.join(ROOT, "fibergen_amd", "csrc", "fg_sweep_plan.h")).read()
     src = re.sub(r'"\s*\n\s*"', "", src)
-    assert '"%s"' % materials.ANISO_SLAB_ERROR in src
+    assert 'kAnisoSlab = "%s"' % materials.ANISO_SLAB_ERROR in src
+    assert "plan::kAnisoSlab" in open(os.path.join(ROOT, "fibergen_amd", "csrc", "fg_solver.hip")).read()
     slab = open(os.path.join(ROOT, "fibergen_amd", "csrc", "fg_slab.hip")).read()
-    assert '"%s"' % materials.ANISO_SLAB_ERROR in slab
+    assert "require_plan(plan::Entry::Slab)" in slab
 
 
 # ---- the C boundary

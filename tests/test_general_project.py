@@ -140,8 +140,8 @@ def test_refused_on_slabs(fake):
 
 
 def test_messages_are_the_library_s():
-    """the project layer raises in the wording of Solver::general_check"""
-    src = open(os.path.join(ROOT, "fibergen_amd", "csrc", "fg_solver.hip")).read()
+    """the project layer raises in the wording of the solver library (law_refusal in fg_sweep_plan.h)"""
+    src = open(os.path.join(ROOT, "fibergen_amd", "csrc", "fg_sweep_plan.h")).read()
     src = re.sub(r'"\s*\n\s*"', "", src)
     for msg in (materials.GENERAL_MODE_ERROR, materials.GENERAL_MIXING_ERROR, materials.GENERAL_DFG_ERROR,
                 materials.GENERAL_SLAB_ERROR):

@@ -67,7 +67,7 @@ def draw_aniso_tile(seed):
 
 
 def tiled_form_expected(c):
-    """Whether k_sc_tile_aniso must run, from the draw alone: Solver::sc_tile_aniso_ok -- option aniso_sc_tile, heat / porous, an
+    """Whether k_sc_tile_aniso must run, from the draw alone: plan::sc_tile_aniso (fg_sweep_plan.h) -- option aniso_sc_tile, heat / porous, an
     aniso phase, u_loop >= 2, u_tile, no mixed boundary condition, one GPU, a grid sc_sweep_tiled takes (= u_tile_supported: even
     nz >= 80, ny >= 14, nx >= 4) and two phases whose fractions are complementary bit for bit with phi_sweep on
     (two_phase_complementary).  method basic asks it in every u_pass_front; method cg (run_cg_scalar) asks it for the fused form,

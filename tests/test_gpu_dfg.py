@@ -231,7 +231,7 @@ TILED_GRIDS = [((6, 14, 128), (2.0, 1.0, 0.5)), ((16, 16, 128), (1, 1, 1)), ((4,
 def test_every_tile_shape_converged_runs(grid, dims, variant):
     """Converged runs on every shape of the five-moduli tiled sweeps, three phases (coarse, fine, coarse input) with pure cells:
     basic_mixed_bc -- the displacement loop with the sums of tau (k_u_tile<..., SUMT, 5>); cg -- the displacement-space CG
-    (launch_u_tile_cg: k_u_tile<..., CGP, 5>); cg_mixed_bc -- a projector sends CG to strain space (u_loop_eligible() is false
+    (launch_u_tile_cg: k_u_tile<..., CGP, 5>); cg_mixed_bc -- a projector sends CG to strain space (plan::u_loop of fg_sweep_plan.h is false
     with a projector unless mixed BC are allowed, i.e. in run() of the basic scheme): k_eps_tile<..., 5> per operator
     application; viscosity_mixed_bc -- k_eps_tile<..., 5> with the recomputing tail and the adjusted sums"""
     rng = np.random.default_rng(15)

@@ -132,7 +132,7 @@ def test_iteration_stage_and_iterate(grid, dims, nph, kind):
     """One pass of Solver::basic_scheme (run_stage "iteration": the strain-state pipeline -- k_eps_tile<...,5> on tiled
     grids, k_dfg_stress<0> + k_div on the others and with fuse_stress_div = 0), then iterate(E, n) for n = 1 and 3 from the same
     strain field.  Solver::iterate from a SET strain field has no displacement yet (u_valid_ is false): its first pass is
-    basic_scheme, the passes after it are the displacement loop where u_loop_eligible() admits it -- under full_staggered
+    basic_scheme, the passes after it are the displacement loop where plan::u_loop (fg_sweep_plan.h) admits it -- under full_staggered
     that is the tiled grids with u_loop = 2 and u_tile = 1 (the five-moduli k_u_tile); with u_tile = 0, and on untiled grids,
     every pass is basic_scheme.  So n = 3 with the default options runs k_eps_tile<...,5> once and k_u_tile<...,5> twice,
     n = 3 with u_tile = 0 runs k_eps_tile<...,5> three times: both against three passes of the oracle."""
@@ -177,7 +177,7 @@ def test_displacement_loop_from_the_uniform_field(grid, dims):
 def test_viscosity_stress_and_iteration_stages(grid, dims, nph, kind):
     """mode = viscosity: the five-moduli branch of the strain-state pass (k_eps_tile<...,5> + the recomputing tail
     launch_eps_delta_recompute on tiled grids; k_dfg_stress<0> + k_div + k_eps_delta elsewhere and with fuse_stress_div = 0)
-    against DfgViscosityOracle; iterate() never enters the displacement loop in this mode (u_loop_eligible: mode 0 only)"""
+    against DfgViscosityOracle; iterate() never enters the displacement loop in this mode (plan::u_loop, fg_sweep_plan.h: mode 0 only)"""
     s, o, ofine, mats, rng = _pair(grid, dims, nph, kind, viscosity=True, seed=3)
     _stress_checks(s, o, ofine, mats, rng.standard_normal((6,) + grid), True)
     eps0 = rng.standard_normal((6,) + grid)

@@ -98,12 +98,12 @@ def draw_general_tile(seed):
 
 def tiled_form_expected(c):
     """Whether k_u_tile's ANISO form must run, from the draw alone.  A general phase enters the displacement loop only through
-    Solver::aniso_tile_ok: option aniso_tile, elasticity, the staggered operator, Voigt mixing, u_loop >= 2, u_tile, one GPU, a grid
+    plan::aniso_tile (fg_sweep_plan.h): option aniso_tile, elasticity, the staggered operator, Voigt mixing, u_loop >= 2, u_tile, one GPU, a grid
     u_tile_supported takes (even nz >= 80, ny >= 14, nx >= 4) and two phases whose fractions are complementary bit for bit with
-    phi_sweep on (two_phase_complementary).  method basic: Solver::u_loop_eligible(allow_mixed_bc = true) then admits pure strain
+    phi_sweep on (two_phase_complementary).  method basic: plan::u_loop with mixed boundary conditions allowed then admits pure strain
     and, on these grids, mixed boundary conditions (the sweep's form with the sums of tau), and the first pass of a fresh step
     already runs u_pass_front.  method cg: run_cg enters run_cg_u (whose operator is u_pass_front, or the sweep's form with the CG
-    direction) only if u_loop_eligible() without mixed boundary conditions holds and the estimator is epsilon or residual;
+    direction) only if plan::u_loop without mixed boundary conditions holds and the estimator is epsilon or residual;
     otherwise CG runs in strain space through k_stress."""
     o = c["opts"]
     nx, ny, nz = c["shape"]

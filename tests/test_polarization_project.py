@@ -130,9 +130,9 @@ def test_experimental_methods_stay_unknown(fake, method):
 
 
 def test_messages_are_the_library_s():
-    """the project layer raises in the wording of Solver::polar_check / fg_set_option_i"""
+    """the project layer raises in the wording of polar_refusal (fg_sweep_plan.h) / fg_set_option_i"""
     src = ""
-    for name in ("fg_solver.hip", "fg_capi.hip"):
+    for name in ("fg_sweep_plan.h", "fg_solver.hip", "fg_capi.hip"):
         src += open(os.path.join(ROOT, "fibergen_amd", "csrc", name)).read()
     src = re.sub(r'"\s*\n\s*"', "", src)
     for key, msg in POLARIZATION_ERRORS.items():

@@ -1,6 +1,6 @@
 """mixing_rule "reuss" at the project layer, without a GPU: <mixing_rule>reuss</mixing_rule> parses in each of the four modes and
 reaches the solver, every combination the rule does not cover is refused before a solver exists in the wording of the
-solver library (Solver::reuss_check), and the C header carries the option value."""
+solver library (reuss_refusal in fg_sweep_plan.h), and the C header carries the option value."""
 import os
 import re
 
@@ -138,10 +138,12 @@ def test_refusals_name_the_option():
 
 
 def test_the_library_speaks_the_same_words():
-    """the texts of Solver::reuss_check (joined string literals) are those of REUSS_ERRORS"""
-    src = open(os.path.join(ROOT, "fibergen_amd", "csrc", "fg_solver.hip")).read()
-    body = src[src.index("void Solver::reuss_check() const {"):]
-    body = body[:body.index("\n}\n")]
+    """the message constants of fg_sweep_plan.h (joined string literals; reuss_refusal picks among them) hold those of REUSS_ERRORS"""
+    hdr = open(os.path.join(ROOT, "fibergen_amd", "csrc", "fg_sweep_plan.h")).read()
+    fn = hdr[hdr.index("constexpr const char* reuss_refusal("):]
+    named = set(re.findall(r"\bk[A-Z]\w+", fn[:fn.index("\n}\n")]))   # the constants reuss_refusal picks among
+    assert len(named) == 8
+    body = "".join(m.group(0) for m in re.finditer(r"constexpr const char\* (k\w+) =[^;]+;", hdr) if m.group(1) in named)
     joined = re.sub(r'"\s+"', "", body)   # adjacent literals
     texts = set(re.findall(r'"([^"]+)"', joined))
     for key, msg in reuss_errors().items():

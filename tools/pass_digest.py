@@ -5,6 +5,7 @@ arithmetic on every path the list reaches: the check for a change that must leav
     python tools/pass_digest.py > profiles/pass_digest_<build>.txt
     python tools/pass_digest.py tiles > profiles/pass_digest_tiles_<build>.txt     (a second list: the tiled marching sweeps)
     python tools/pass_digest.py fft > profiles/pass_digest_fft_<build>.txt         (a third: every transform family per axis)
+    python tools/pass_digest.py reuss > profiles/pass_digest_reuss_<build>.txt     (a fourth: mixing_rule reuss on every sweep)
 
 One line per run: grid, name, the digest of the residuals, the digest of the field and the iteration count -- or the solver's
 error text where a combination is refused (a refusal is part of the behaviour that is compared)."""
@@ -234,5 +235,26 @@ def fft():
         report("heat joint_x=%d" % j, (100, 8, 16), joint_x=j, **HEAT)
 
 
+def reuss():
+    """mixing_rule reuss on the untiled and the tiled grids, methods basic and cg: the exact-order sweep (u_loop 0 / 1), the moduli
+    arrays, the in-sweep harmonic form of two complementary phases and its switch (reuss_sweep, phi_sweep), mixed boundary
+    conditions, heat and viscosity.  These are digests of RESULTS (residuals, final field), not of the launches; behind a line the
+    counter of the in-sweep form"""
+    global COUNTERS
+    COUNTERS = ("u_tile_reuss",)
+    R = dict(mixing_rule="reuss")
+    for grid in (G16, GODD, (4, 16, 80), (6, 14, 128)):
+        for method in ("basic", "cg"):
+            for ul in (0, 1, 2):
+                report("reuss %s u_loop=%d" % (method, ul), grid, method=method, u_loop=ul, **R)
+            for o in (dict(reuss_sweep=0), dict(phi_sweep=0), dict(u_tile=0), dict(cg_fused=0), dict(fuse_stress_div=0)):
+                report("reuss %s %s" % (method, opts(o)), grid, method=method, **o, **R)
+        report("reuss mixed bc", grid, mixed=True, **R)
+        report("reuss collocated", grid, gamma_scheme="collocated", **R)
+        report("reuss heat", grid, **R, **HEAT)
+        report("reuss heat cg", grid, method="cg", **R, **HEAT)
+        report("reuss viscosity", grid, **R, **VISC)
+
+
 if __name__ == "__main__":
-    {"tiles": tiles, "fft": fft}.get((sys.argv[1:] or [""])[0], main)()
+    {"tiles": tiles, "fft": fft, "reuss": reuss}.get((sys.argv[1:] or [""])[0], main)()
