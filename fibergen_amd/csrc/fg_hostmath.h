@@ -7,6 +7,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <stdexcept>
 
 namespace fg {
 namespace hostmath {
@@ -101,6 +102,82 @@ inline double norm2(const double* v, int n) {
   double s = 0.0;
   for (int i = 0; i < n; ++i) s += v[i] * v[i];
   return std::sqrt(s);
+}
+
+// bc_error  F:21129-21161 from the two means: max of |P:<eps> - E| / |P:E| and |Q:<sigma> - S| / |S| (a norm below bc_tol
+// divides by 1)
+inline double bc_error_value(const Mat6& P, const Mat6& Q, double bc_tol, const double* Emean, const double* Smean,
+                             const double* E_cur, const double* S_cur) {
+  double PE[6], QS[6], PEc[6], d[6];
+  voigt_mv(P, Emean, PE);
+  voigt_mv(Q, Smean, QS);
+  voigt_mv(P, E_cur, PEc);
+  const double norm_E = voigt_norm2(PEc);
+  for (int i = 0; i < 6; ++i) d[i] = PE[i] - E_cur[i];
+  const double err_F = voigt_norm2(d) / ((norm_E < bc_tol) ? 1 : norm_E);
+  const double norm_S = voigt_norm2(S_cur);
+  for (int i = 0; i < 6; ++i) d[i] = QS[i] - S_cur[i];
+  const double err_S = voigt_norm2(d) / ((norm_S < bc_tol) ? 1 : norm_S);
+  return err_F > err_S ? err_F : err_S;
+}
+
+// LSSolver::run's check of the prescribed values against the projector  F:21356-21364: P:S and Q:E must vanish
+inline void check_bc_compatible(const Mat6& P, const Mat6& Q, const double* Emax, const double* Smax) {
+  const double se = std::sqrt(2.220446049250313e-16);
+  double t[6];
+  voigt_mv(P, Smax, t);
+  if (norm2(t, 6) > se * norm2(Smax, 6)) throw std::runtime_error("Incompatible stress boundary condition specified");
+  voigt_mv(Q, Emax, t);
+  if (norm2(t, 6) > se * norm2(Emax, 6)) throw std::runtime_error("Incompatible strain boundary condition specified");
+}
+
+// runLoadsteppingSolver  F:21584-21685: the steps first .. nparams - 1 of a load path, and the prescribed values of the step with
+// parameter t
+inline void check_load_steps(const double* params, int nparams, int first) {
+  if (nparams < 1 || first < 0 || !params) throw std::runtime_error("invalid load steps");
+}
+inline void load_step_values(double t, const double* Emax, const double* Smax, double* E, double* S) {
+  for (int i = 0; i < 6; ++i) E[i] = t * Emax[i], S[i] = t * Smax[i];
+}
+
+// getRefMaterial  F:12153-12236 on the extreme tangent eigenvalues: the lower one clamped at 0 (F:12183-12223), their
+// arithmetic mean -- method polarization (2): their geometric mean, F:12227-12229 --, halved and scaled
+inline double ref_mu0(double lambda_min, double lambda_max, int method, double ref_scale) {
+  if (lambda_min < 0) lambda_min = 0;
+  double mu_0 = method == 2 ? std::sqrt(lambda_min * lambda_max) : 0.5 * (lambda_min + lambda_max);
+  mu_0 *= 0.5 * ref_scale;
+  return mu_0;
+}
+
+// Weights of the polynomial load-step extrapolation  F:21468-21514: w = V^-T tpowers with V_ij = t_i^j, i.e. V^T w = tpowers
+// with tpowers_i = t_new^i, by Gauss elimination with partial pivoting (n <= 8).  False: a pivot is zero ("Error inverting
+// Vandermonde matrix", F:21487-21490), w is not written.
+inline bool extrapolation_weights(const double* t, int n, double t_new, double* w) {
+  double A[8][9];
+  for (int i = 0; i < n; ++i) {
+    for (int j = 0; j < n; ++j) A[i][j] = std::pow(t[j], i);   // (V^T)_ij = t_j^i
+    A[i][n] = std::pow(t_new, i);
+  }
+  for (int c = 0; c < n; ++c) {
+    int piv = c;
+    for (int r = c + 1; r < n; ++r)
+      if (std::fabs(A[r][c]) > std::fabs(A[piv][c])) piv = r;
+    if (A[piv][c] == 0.0) return false;
+    for (int j = 0; j <= n; ++j) {
+      const double s = A[c][j];
+      A[c][j] = A[piv][j], A[piv][j] = s;
+    }
+    for (int r = c + 1; r < n; ++r) {
+      const double m = A[r][c] / A[c][c];
+      for (int j = c; j <= n; ++j) A[r][j] -= m * A[c][j];
+    }
+  }
+  for (int r = n - 1; r >= 0; --r) {
+    double v = A[r][n];
+    for (int j = r + 1; j < n; ++j) v -= A[r][j] * w[j];
+    w[r] = v / A[r][r];
+  }
+  return true;
 }
 
 // Symmetric N x N eigen-decomposition by cyclic Jacobi: A = V diag(w) V^T.

@@ -37,6 +37,10 @@ class SlabGroup {
   double mean_energy();
   void estimator_begin(bool fresh);
   void estimator_update(double* abs_err, double* rel_err);
+  template <class F>
+  void each_estimator(F f) {   // (estimator_begin / estimator_update of fg_stop_rule.h)
+    for (Solver* s : m_) f(s->est_);
+  }
   void mean_strain(double* out6);
   double volume_fraction(int p);
   void calc_ref_material();
@@ -66,7 +70,9 @@ class SlabGroup {
   bool converged(const StopRule& rule, long iter, const std::function<bool()>& bc_ok, bool* failed) {
     return converged(rule, iter, cg_voting_, bc_ok, failed, cg_callbacks_);
   }
-  bool cg_voting_ = false, cg_callbacks_ = true;                       // of the pipelined CG run in progress
+  bool cg_voting_ = false, cg_callbacks_ = true;                       // of the skeleton's run in progress
+  template <class Site>
+  friend BasicResult basic_loop(Site&, const BasicLoopOps&, StopRule&, const double*, bool, bool, bool);   // fg_basic_loop.h
   template <class Site>
   friend CgResult cg_pipelined(Site&, const CgPipelinedOps&, StopRule&, const CgSlots&, double);
   void set_state_u(const double* E);                                   // the iterate is (E, u_e) on every member

@@ -770,12 +770,14 @@ void SlabGroup::vote(double* v2) {
   v2[1] = m_[0]->hscal_[kSlotMisc + 1];
 }
 
+// The measurements: every member materialises its strain where the state is (E, u) and enqueues its local half
+// (Solver::enqueue_*, fg_solver.hip); the contributions are all-reduced and reach every host.
 void SlabGroup::mean_strain(double* out6) {
   check_members();
   prepare();
   for (Solver* s : m_) {
     if (s->su_valid_ && s->eps_stale_) s->slab_materialise_eps();
-    launch_sum6(s->g_, s->ptrs6(s->eps_), false, s->partial_, s->dscal_ + kSlotMean, s->stream_);
+    s->enqueue_strain_sums(kSlotMean, false);
   }
   reduce_and_fetch(kSlotMean, 6, false);
   for (int c = 0; c < 6; ++c) out6[c] = m_[0]->hscal_[kSlotMean + c] / (double)m_[0]->nglobal_;
@@ -786,14 +788,7 @@ void SlabGroup::mean_stress(double* out6) {
   prepare();
   for (Solver* s : m_) {
     if (s->su_valid_ && s->eps_stale_) s->slab_materialise_eps();
-    const FieldPtrs<3> nrm = s->normal_ptrs();
-    // meanPK1: alpha /= nxyz (global), accumulate  F:12318-12340
-    if (s->opt_.mode == 1)
-      launch_sc_flux_mean(s->g_, s->scalar_params(0.0, 1.0 / (double)s->nglobal_), s->ptrs3(s->eps_), s->phase_ptrs(), s->partial_,
-                          s->dscal_ + kSlotMean, s->stream_);
-    else
-      launch_stress_mean(s->g_, s->stress_params(0.0, 0.0, 1.0 / (double)s->nglobal_), s->ptrs6(s->eps_), s->phase_ptrs(), nrm,
-                         s->partial_, s->dscal_ + kSlotMean, s->derr_, s->stream_);
+    s->enqueue_mean_stress(kSlotMean);
   }
   reduce_and_fetch(kSlotMean, 6, false);
   for (int c = 0; c < 6; ++c) out6[c] = m_[0]->hscal_[kSlotMean + c];
@@ -806,46 +801,23 @@ double SlabGroup::mean_energy() {
   for (Solver* s : m_) {
     if (s->opt_.mode == 1) throw std::runtime_error("the energy error estimator is not available in heat / porous mode");
     if (s->su_valid_ && s->eps_stale_) s->slab_materialise_eps();
-    const FieldPtrs<3> nrm = s->normal_ptrs();
-    launch_energy_mean(s->g_, s->stress_params(0.0, 0.0, 1.0), s->ptrs6(s->eps_), s->phase_ptrs(), nrm, s->partial_,
-                       s->dscal_ + kSlotMean, s->derr_, s->stream_);
+    s->enqueue_mean_energy(kSlotMean);
   }
   reduce_and_fetch(kSlotMean, 6, false);
   return m_[0]->hscal_[kSlotMean] / (double)m_[0]->nglobal_;
 }
 
-// the estimators that measure a mean of the strain field (Solver::estimator_begin / estimator_update), collectively: every
-// rank holds the same all-reduced means and so the same estimator state
+// the estimators that measure a mean of the strain field (fg_stop_rule.h), collectively: every rank holds the same all-reduced
+// means and so the same estimator state
 void SlabGroup::estimator_begin(bool fresh) {
   Solver& a = *m_[0];
   if (a.opt_.error_estimator < 2) return;
   if (a.opt_.mode == 1) throw std::runtime_error(plan::kHeatEstimator);
-  double m[6] = {0, 0, 0, 0, 0, 0};
-  double w = 0.0;
-  if (a.opt_.error_estimator == 2 && !fresh) mean_stress(m);
-  if (a.opt_.error_estimator == 3 && !fresh) w = mean_energy();
-  for (Solver* s : m_) {
-    if (a.opt_.error_estimator == 2) s->est_.start_sigma(m);
-    if (a.opt_.error_estimator == 3) s->est_.start_energy(w);
-  }
+  fg::estimator_begin(*this, a.opt_.error_estimator, fresh);
 }
 
 void SlabGroup::estimator_update(double* abs_err, double* rel_err) {
-  Solver& a = *m_[0];
-  if (a.opt_.error_estimator == 2) {
-    double m[6];
-    mean_stress(m);
-    double ae = 0.0, re = 0.0;
-    for (Solver* s : m_) s->est_.update_sigma(m, &ae, &re);
-    *abs_err = ae, *rel_err = re;
-  } else if (a.opt_.error_estimator == 3) {
-    const double w = mean_energy();
-    double ae = 0.0, re = 0.0;
-    for (Solver* s : m_) s->est_.update_energy(w, &ae, &re);
-    *abs_err = ae, *rel_err = re;
-  } else if (a.opt_.error_estimator == 4) {
-    *abs_err = *rel_err = 1.0;
-  }
+  fg::estimator_update(*this, m_[0]->opt_.error_estimator, abs_err, rel_err);
 }
 
 double SlabGroup::volume_fraction(int p) {
@@ -853,7 +825,7 @@ double SlabGroup::volume_fraction(int p) {
   prepare();
   for (Solver* s : m_) {
     if (p < 0 || p >= s->pt_.n) throw std::runtime_error("phase index out of range");
-    launch_sum1(s->g_, s->phi_ + (long)p * s->g_.n, s->partial_, s->dscal_ + kSlotMisc, s->stream_);
+    s->enqueue_phase_sum(p, kSlotMisc);
   }
   reduce_and_fetch(kSlotMisc, 1, false);
   return m_[0]->hscal_[kSlotMisc] / (double)m_[0]->nglobal_;
@@ -863,18 +835,10 @@ double SlabGroup::volume_fraction(int p) {
 void SlabGroup::calc_ref_material() {
   check_members();
   prepare();
-  for (Solver* s : m_) {
-    if (s->opt_.mode == 1)
-      launch_sc_minmax(s->g_, s->scalar_params(0.0, 1.0), s->phase_ptrs(), s->partial_, s->dscal_ + kSlotMinMax, s->stream_);
-    else
-      launch_tangent_minmax(s->g_, s->phase_table(), s->opt_.mixing, s->phase_ptrs(), s->partial_, s->dscal_ + kSlotMinMax, s->derr_,
-                            s->stream_);
-  }
+  for (Solver* s : m_) s->enqueue_tangent_minmax(kSlotMinMax);
   reduce_and_fetch(kSlotMinMax, 2, true);   // stored as (min, -max): one element-wise minimum serves both
-  double lambda_min = m_[0]->hscal_[kSlotMinMax], lambda_max = -m_[0]->hscal_[kSlotMinMax + 1];
-  if (lambda_min < 0) lambda_min = 0;   // F:12183-12223
-  double mu_0 = 0.5 * (lambda_min + lambda_max);
-  mu_0 *= 0.5 * m_[0]->opt_.ref_scale;
+  // (method 0: the slab driver has no polarisation loop, the arithmetic mean holds whatever the option says)
+  const double mu_0 = ref_mu0(m_[0]->hscal_[kSlotMinMax], -m_[0]->hscal_[kSlotMinMax + 1], 0, m_[0]->opt_.ref_scale);
   for (Solver* s : m_) {
     s->opt_.mu_0 = mu_0;
     s->recompute_bc();   // F:22312
@@ -884,19 +848,10 @@ void SlabGroup::calc_ref_material() {
 // bc_error  F:21129-21161
 double SlabGroup::bc_error(const double* E_cur, const double* S_cur) {
   Solver& a = *m_[0];
-  double Emean[6], Smean[6], PE[6], QS[6], PEc[6], d[6];
+  double Emean[6], Smean[6];
   mean_strain(Emean);
   mean_stress(Smean);
-  voigt_mv(a.BC_P_, Emean, PE);
-  voigt_mv(a.BC_Q_, Smean, QS);
-  voigt_mv(a.BC_P_, E_cur, PEc);
-  const double norm_E = voigt_norm2(PEc);
-  for (int i = 0; i < 6; ++i) d[i] = PE[i] - E_cur[i];
-  const double err_F = voigt_norm2(d) / ((norm_E < a.opt_.bc_tol) ? 1 : norm_E);
-  const double norm_S = voigt_norm2(S_cur);
-  for (int i = 0; i < 6; ++i) d[i] = QS[i] - S_cur[i];
-  const double err_S = voigt_norm2(d) / ((norm_S < a.opt_.bc_tol) ? 1 : norm_S);
-  return err_F > err_S ? err_F : err_S;
+  return bc_error_value(a.BC_P_, a.BC_Q_, a.opt_.bc_tol, Emean, Smean, E_cur, S_cur);
 }
 
 // one displacement pass on every member: the sweep (norms of eps_k), then -- speculatively, the host has not seen the
@@ -999,7 +954,7 @@ bool SlabGroup::run_load_steps(const double* E6, const double* S6, const double*
                                LoadstepCallback step_cb, void* user) {
   check_members();
   Solver& a = *m_[0];
-  if (nparams < 1 || first < 0 || !params) throw std::runtime_error("invalid load steps");
+  check_load_steps(params, nparams, first);
   if (a.opt_.loadstep_extrapolation_order > 0 && nparams - first > 1)
     throw std::runtime_error("load-step extrapolation is not available on slab-decomposed solvers");
   double Emax[6], Smax[6];
@@ -1012,17 +967,10 @@ bool SlabGroup::run_load_steps(const double* E6, const double* S6, const double*
     s->slab_reset_state();
     s->recompute_bc();   // F:21354
   }
-  {
-    const double se = std::sqrt(kEps);
-    double t[6];
-    voigt_mv(a.BC_P_, Smax, t);
-    if (norm2(t, 6) > se * norm2(Smax, 6)) throw std::runtime_error("Incompatible stress boundary condition specified");
-    voigt_mv(a.BC_Q_, Emax, t);
-    if (norm2(t, 6) > se * norm2(Emax, 6)) throw std::runtime_error("Incompatible strain boundary condition specified");
-  }
+  check_bc_compatible(a.BC_P_, a.BC_Q_, Emax, Smax);
   for (int istep = first; istep < nparams; ++istep) {
     double E[6], S[6];
-    for (int i = 0; i < 6; ++i) E[i] = params[istep] * Emax[i], S[i] = params[istep] * Smax[i];
+    load_step_values(params[istep], Emax, Smax, E, S);
     const bool fresh = istep == first;
     const bool failed = a.opt_.method == 1 ? run_cg(E, S, fresh) : run_step(E, S, fresh);
     // The step's outcome and the load-step callback's answer are agreed over the ranks: a callback that exists on one
@@ -1041,7 +989,7 @@ double SlabGroup::current_norm9() {
   prepare();
   for (Solver* s : m_) {
     if (s->su_valid_ && s->eps_stale_) s->slab_materialise_eps();
-    launch_sum6(s->g_, s->ptrs6(s->eps_), true, s->partial_, s->dscal_ + kSlotMean, s->stream_);
+    s->enqueue_strain_sums(kSlotMean, true);
   }
   reduce_and_fetch(kSlotMean, 6, false);
   double s9 = 0.0;
@@ -1059,8 +1007,7 @@ bool SlabGroup::run_step(const double* E0, const double* S0, bool fresh) {
   const double t_start = now_seconds();
   prepare();
   require_scalar_fast(true);
-  const bool fast_allowed = fast_ok(true);
-  bool fast = fast_allowed;
+  const bool fast = fast_ok(true);
   double prev0 = 0.0;   // EpsilonErrorEstimator  F:14591-14637: norms of the field the step starts from
   if (fresh) {
     for (Solver* s : m_) {
@@ -1077,11 +1024,6 @@ bool SlabGroup::run_step(const double* E0, const double* S0, bool fresh) {
   StopRule rule = a.stop_rule(prev0);
   estimator_begin(fresh);
   for (Solver* s : m_) s->in_run_ = true;
-  // a continuing step in the displacement loop: the state is u of the previous load (eps = E_old + sym grad u); one
-  // unrecorded pass turns it into u' with eps' = E_new + sym grad u', the field the reference's first iteration of the step
-  // produces (Solver::run_one_step)
-  bool carry = !fresh && fast;
-  for (Solver* s : m_) carry = carry && s->su_valid_;
 
   // Stop decisions are collective.  Callbacks may be installed on some ranks only (rank 0 printing its progress) and may
   // answer differently; whether any rank has one is agreed once per run, and if so every pass ends with a vote on the
@@ -1089,84 +1031,65 @@ bool SlabGroup::run_step(const double* E0, const double* S0, bool fresh) {
   // speculative exchanges would wait for them).  Without callbacks only fg_cancel can ask for a stop from outside; it
   // travels with the flag word of the next pass's reduction.
   const bool voting = agree_on_voting();
+  cg_voting_ = voting, cg_callbacks_ = true;   // (what the four-argument converged binds)
 
-  long iter = 1;
-  bool update_ref = a.opt_.update_ref != 0;
-  double E[6], E_next[6];
-  for (int i = 0; i < 6; ++i) E[i] = E0[i];
-  bool failed = false;
   const double nglobal = (double)a.nglobal_;
-
-  for (;;) {
-    if (update_ref) {
-      calc_ref_material();
-      bc_mean(a.BC_QC0_, a.BC_M_, a.opt_.bc_relax, E0, S0, E);
-      update_ref = false;
-      if (fast) prepare();   // effective moduli are independent of the reference material, but may not exist yet
+  auto adopt_u = [&](const double* E) {
+    for (Solver* s : m_) {
+      s->slab_adopt(E, true);
+      s->eps_stale_ = true;
     }
-    const bool mixed_bc = a.mixed_bc();
-    if (carry) {
-      carry = false;
-      if (mixed_bc) {
-        fast = false;   // the correction of the prescribed mean needs <tau> of the old field: strain-state passes for this step
-      } else {
-        pass_fast(a.E_cur_, false, true);
-        for (Solver* s : m_) {
-          s->slab_adopt(E, true);
-          s->eps_stale_ = true;
-        }
-      }
-    }
-    bool all_u = true;
-    for (Solver* s : m_) all_u = all_u && s->su_valid_;
-    bool pending = false;
-    if (fast && all_u) {
-      if (iter == 1 && fresh)
-        for (Solver* s : m_)
-          for (int i = 0; i < 6; ++i) s->E_cur_[i] = E[i];   // eps_1 = E (u_1 = 0)
-      pass_fast(a.E_cur_, mixed_bc, !voting);
-      pending = true;
-    } else {
-      pass_exact(E, mixed_bc);
-      // the pass leaves a displacement unless the projector's correction went into the strain: go on in displacement space
-      // after the unrecorded pass of a continuing state (carry)
-      bool have_u = fast && !mixed_bc;
-      for (Solver* s : m_) have_u = have_u && s->su_valid_;
-      if (have_u) carry = true;
-      else fast = false;
-    }
-    wait_norms();
-    for (int i = 0; i < 6; ++i) E_next[i] = E[i];
-    if (pending && mixed_bc) {
-      // applyBCProjector  F:20247-20270 with bc_relax = 1: eps_{k+1} = E + alpha MQ:<tau_k> + sym grad u_{k+1}
-      double F0[6], t1[6];
-      for (int c = 0; c < 6; ++c) F0[c] = a.hscal_[kSlotMean + c] / nglobal;
-      voigt_mv(a.BC_MQ_, F0, t1);
-      for (int c = 0; c < 6; ++c) E_next[c] = E[c] - t1[c];   // alpha = -1  (F:20575)
-    }
-
+  };
+  BasicLoopOps ops;   // the iteration itself: fg_basic_loop.h
+  ops.refresh_ref = [&](double* E) {
+    calc_ref_material();
+    bc_mean(a.BC_QC0_, a.BC_M_, a.opt_.bc_relax, E0, S0, E);
+    if (fast) prepare();   // effective moduli are independent of the reference material, but may not exist yet
+  };
+  ops.have_u = [&] {
+    for (Solver* s : m_)
+      if (!s->su_valid_) return false;
+    return true;
+  };
+  ops.mixed_bc = [&] { return a.mixed_bc(); };
+  ops.start_from = [&](const double* E) {
+    for (Solver* s : m_)
+      for (int i = 0; i < 6; ++i) s->E_cur_[i] = E[i];
+  };
+  ops.carry_pass = [&](const double* E) {
+    pass_fast(a.E_cur_, false, true);
+    adopt_u(E);
+  };
+  ops.u_pass = [&](const double*, bool mixed_bc) { pass_fast(a.E_cur_, mixed_bc, !voting); };   // (E takes effect with u_{k+1})
+  ops.strain_pass = [&](const double* E, bool mixed_bc) { pass_exact(E, mixed_bc); };
+  ops.wait = [&] { wait_norms(); };
+  ops.mq_mean_tau = [&](double* t6) {
+    double F0[6];
+    for (int c = 0; c < 6; ++c) F0[c] = a.hscal_[kSlotMean + c] / nglobal;
+    voigt_mv(a.BC_MQ_, F0, t6);
+  };
+  ops.norm = [&] {
     set_sumsq(kSlotSumSq, 6);
-    rule.measure(norm9_of_sums(a.sumsq_, nglobal));
-    if (a.opt_.error_estimator >= 2) estimator_update(&rule.abs_err, &rule.rel_err);   // sigma / energy / none: F:14410-14587
-    if (converged(rule, iter, voting, [&] { return bc_error(E0, S0) <= a.opt_.bc_tol; }, &failed)) break;
-    if (pending) {
-      if (voting) pass_fast_chain();
-      for (Solver* s : m_) {
-        s->slab_adopt(E_next, true);
-        s->eps_stale_ = true;
-      }
-    }
-    iter++;
-  }
+    return norm9_of_sums(a.sumsq_, nglobal);
+  };
+  ops.estimator = [&](StopRule& r) {
+    if (a.opt_.error_estimator >= 2) estimator_update(&r.abs_err, &r.rel_err);
+  };
+  ops.bc_ok = [&] { return bc_error(E0, S0) <= a.opt_.bc_tol; };
+  ops.adopt = [&](const double* E_next) {
+    if (voting) pass_fast_chain();
+    adopt_u(E_next);
+  };
+  const BasicResult end = basic_loop(*this, ops, rule, E0, fresh, fast, a.opt_.update_ref != 0);
   for (Solver* s : m_) {
     s->in_run_ = false;
-    s->iterations_ = iter;
+    s->iterations_ = end.iter;
     if (s->su_valid_ && s->eps_stale_) s->slab_materialise_eps();
   }
   synchronize();
   const double dt = now_seconds() - t_start;
   for (Solver* s : m_) s->solve_time_ += dt;
-  return failed;
+  return end.failed;
 }
 
 // runCGElasticity  F:23153-23247 on the slabs, carried in displacement space like Solver::run_cg_u (eps = E + grad_s u_e;

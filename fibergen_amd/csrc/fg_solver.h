@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "fg_basic_loop.h"
 #include "fg_cg_loop.h"
 #include "fg_comm.h"
 #include "fg_fft.h"
@@ -206,6 +207,8 @@ class Solver {
   double mean_energy();             // meanW  F:12239-12262 of the current strain field
   void mean_strain(double* out6);   // TensorField::average  F:10171
   double volume_fraction(int p);
+  template <class F>
+  void each_estimator(F f) { f(est_); }   // (estimator_begin / estimator_update of fg_stop_rule.h)
 
   const std::vector<double>& residuals() const { return residuals_; }
   long iterations() const { return iterations_; }
@@ -279,7 +282,16 @@ class Solver {
   void bc_adjust_sums(double factor);   // k_bc_adjust_sums on kSlotMean with the plain matrix of v -> MQ:v
   void release();
   bool run_one_step(const double* E0, const double* S0);
+  template <class Site>
+  friend BasicResult basic_loop(Site&, const BasicLoopOps&, StopRule&, const double*, bool, bool, bool);   // fg_basic_loop.h
   double current_norm9();
+  // the local halves of the measurements: this solver's (slab's) contribution -> dscal_ + slot, nothing else
+  void enqueue_strain_sums(int slot, bool squared);   // six sums of the strain components (or of their squares)
+  void enqueue_mean_stress(int slot);                 // scalar modes: the mean flux; gamma_scheme 2: from the five moduli
+  void enqueue_mean_energy(int slot);
+  void enqueue_tangent_minmax(int slot);              // (min, -max) of the tangents' eigenvalues
+  void enqueue_phase_sum(int p, int slot);
+  void fetch_sums(int slot, int n);                   // D2H of n of them into hscal_ + slot, waited for
   // estimators 2 (sigma), 3 (energy), 4 (none): constructor on the field a step starts from, update after an iteration
   void estimator_begin(bool fresh);
   void estimator_update(double* abs_err, double* rel_err);

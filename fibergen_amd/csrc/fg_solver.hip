@@ -1407,28 +1407,56 @@ void Solver::iterate(const double* E6, int n) {
 }
 
 // ------------------------------------------------------------------ means
+// The local halves of the measurements: this solver's (a slab's) contribution enqueued into dscal_ + slot, nothing else.  The lone
+// solver fetches and scales it; SlabGroup (fg_slab.hip) all-reduces the members' contributions first.
+void Solver::enqueue_strain_sums(int slot, bool squared) {
+  launch_sum6(g_, ptrs6(eps_), squared, partial_, dscal_ + slot, stream_);
+}
+
+// meanPK1: alpha /= nxyz (global), accumulate  F:12318-12340; heat / porous: the mean flux in the first three slots
+void Solver::enqueue_mean_stress(int slot) {
+  if (opt_.mode == 1)
+    launch_sc_flux_mean(g_, scalar_params(0.0, 1.0 / (double)nglobal_), ptrs3(eps_), phase_ptrs(), partial_, dscal_ + slot, stream_);
+  else if (dfg())
+    launch_dfg_stress(1, g_, stress_params(0.0, 0.0, 1.0 / (double)nglobal_), ptrs6(eps_), dfg_moduli(), FieldPtrs<6>{}, partial_,
+                      dscal_ + slot, stream_);
+  else
+    launch_stress_mean(g_, stress_params(0.0, 0.0, 1.0 / (double)nglobal_), ptrs6(eps_), phase_ptrs(), normal_ptrs(), partial_,
+                       dscal_ + slot, derr_, stream_);
+}
+
+// meanW  F:12239-12262: the sum, not yet divided by N
+void Solver::enqueue_mean_energy(int slot) {
+  if (dfg())
+    launch_dfg_stress(2, g_, stress_params(0.0, 0.0, 1.0), ptrs6(eps_), dfg_moduli(), FieldPtrs<6>{}, partial_, dscal_ + slot, stream_);
+  else
+    launch_energy_mean(g_, stress_params(0.0, 0.0, 1.0), ptrs6(eps_), phase_ptrs(), normal_ptrs(), partial_, dscal_ + slot, derr_,
+                       stream_);
+}
+
+// extreme eigenvalues of the tangents as (min, -max)
+void Solver::enqueue_tangent_minmax(int slot) {
+  if (opt_.mode == 1)
+    launch_sc_minmax(g_, scalar_params(0.0, 1.0), phase_ptrs(), partial_, dscal_ + slot, stream_);
+  else
+    launch_tangent_minmax(g_, phase_table(), opt_.mixing, phase_ptrs(), partial_, dscal_ + slot, derr_, stream_);
+}
+
+void Solver::enqueue_phase_sum(int p, int slot) { launch_sum1(g_, phi_ + (long)p * g_.n, partial_, dscal_ + slot, stream_); }
+
+// n sums of dscal_ + slot brought to hscal_ + slot, waited for
+void Solver::fetch_sums(int slot, int n) {
+  FG_HIP_CHECK(hipMemcpyAsync(hscal_ + slot, dscal_ + slot, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  FG_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
 void Solver::mean_stress(double* out6) {
   FG_HIP_CHECK(hipSetDevice(device_));
   ensure_eps();
   if (pt_.n < 1) throw std::runtime_error(plan::kNoMaterials);
-  if (opt_.mode == 1) {
-    launch_sc_flux_mean(g_, scalar_params(0.0, 1.0 / (double)nglobal_), ptrs3(eps_), phase_ptrs(), partial_,
-                        dscal_ + kSlotMean, stream_);
-    FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean, dscal_ + kSlotMean, 6 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    FG_HIP_CHECK(hipStreamSynchronize(stream_));
-    for (int c = 0; c < 6; ++c) out6[c] = c < 3 ? hscal_[kSlotMean + c] : 0.0;
-    return;
-  }
-  // meanPK1: alpha /= nxyz, accumulate  F:12318-12340
-  if (dfg())
-    launch_dfg_stress(1, g_, stress_params(0.0, 0.0, 1.0 / (double)nglobal_), ptrs6(eps_), dfg_moduli(), FieldPtrs<6>{}, partial_,
-                      dscal_ + kSlotMean, stream_);
-  else
-    launch_stress_mean(g_, stress_params(0.0, 0.0, 1.0 / (double)nglobal_), ptrs6(eps_), phase_ptrs(), normal_ptrs(),
-                       partial_, dscal_ + kSlotMean, derr_, stream_);
-  FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean, dscal_ + kSlotMean, 6 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-  FG_HIP_CHECK(hipStreamSynchronize(stream_));
-  for (int c = 0; c < 6; ++c) out6[c] = hscal_[kSlotMean + c];
+  enqueue_mean_stress(kSlotMean);
+  fetch_sums(kSlotMean, 6);
+  for (int c = 0; c < 6; ++c) out6[c] = (opt_.mode == 1 && c >= 3) ? 0.0 : hscal_[kSlotMean + c];
 }
 
 double Solver::mean_energy() {
@@ -1437,91 +1465,47 @@ double Solver::mean_energy() {
   if (pt_.n < 1) throw std::runtime_error(plan::kNoMaterials);
   if (opt_.mode == 1) throw std::runtime_error("the energy error estimator is not available in heat / porous mode");
   if (opt_.mixing == kMixReuss) throw std::runtime_error("Reuss MaterialLaw energy not implemented");   // F:12657-12661
-  if (dfg())
-    launch_dfg_stress(2, g_, stress_params(0.0, 0.0, 1.0), ptrs6(eps_), dfg_moduli(), FieldPtrs<6>{}, partial_, dscal_ + kSlotMean,
-                      stream_);
-  else
-    launch_energy_mean(g_, stress_params(0.0, 0.0, 1.0), ptrs6(eps_), phase_ptrs(), normal_ptrs(), partial_, dscal_ + kSlotMean,
-                       derr_, stream_);
-  FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMean, dscal_ + kSlotMean, sizeof(double), hipMemcpyDeviceToHost, stream_));
-  FG_HIP_CHECK(hipStreamSynchronize(stream_));
+  enqueue_mean_energy(kSlotMean);
+  fetch_sums(kSlotMean, 1);
   return hscal_[kSlotMean] / (double)nglobal_;
 }
 
-// create_error_estimator  F:14940-14972 for the estimators that measure a mean of the strain field: their constructors run on
-// the field the step starts from (zero for a first step: <sigma> = 0, <W> = 0), update() after every iteration
-void Solver::estimator_begin(bool fresh) {
-  double m[6] = {0, 0, 0, 0, 0, 0};
-  if (opt_.error_estimator == 2) {
-    if (!fresh) mean_stress(m);
-    est_.start_sigma(m);
-  } else if (opt_.error_estimator == 3) {
-    est_.start_energy(fresh ? 0.0 : mean_energy());
-  }
-}
-
-void Solver::estimator_update(double* abs_err, double* rel_err) {
-  if (opt_.error_estimator == 2) {
-    double m[6];
-    mean_stress(m);
-    est_.update_sigma(m, abs_err, rel_err);
-  } else if (opt_.error_estimator == 3) {
-    est_.update_energy(mean_energy(), abs_err, rel_err);
-  } else if (opt_.error_estimator == 4) {
-    *abs_err = *rel_err = 1.0;
-  }
-}
+// estimators 2 (sigma), 3 (energy), 4 (none): fg_stop_rule.h
+void Solver::estimator_begin(bool fresh) { fg::estimator_begin(*this, opt_.error_estimator, fresh); }
+void Solver::estimator_update(double* abs_err, double* rel_err) { fg::estimator_update(*this, opt_.error_estimator, abs_err, rel_err); }
 
 void Solver::mean_strain(double* out6) {
   FG_HIP_CHECK(hipSetDevice(device_));
   ensure_eps();
-  launch_sum6(g_, ptrs6(eps_), false, partial_, dscal_ + kSlotMean, stream_);
+  enqueue_strain_sums(kSlotMean, false);
   fetch_mean6(out6);
 }
 
 double Solver::volume_fraction(int p) {
   if (p < 0 || p >= pt_.n) throw std::runtime_error("phase index out of range");
   FG_HIP_CHECK(hipSetDevice(device_));
-  launch_sum1(g_, phi_ + (long)p * g_.n, partial_, dscal_ + kSlotMisc, stream_);
-  FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMisc, dscal_ + kSlotMisc, sizeof(double), hipMemcpyDeviceToHost, stream_));
-  FG_HIP_CHECK(hipStreamSynchronize(stream_));
+  enqueue_phase_sum(p, kSlotMisc);
+  fetch_sums(kSlotMisc, 1);
   return hscal_[kSlotMisc] / (double)nglobal_;
 }
 
-// calcRefMaterial  F:22283-22313 -> getRefMaterial  F:12153-12236
+// calcRefMaterial  F:22283-22313 -> getRefMaterial  F:12153-12236 (hostmath::ref_mu0)
 void Solver::calc_ref_material() {
   FG_HIP_CHECK(hipSetDevice(device_));
   require_plan(plan::Entry::RefMaterial);
-  if (opt_.mode == 1)
-    launch_sc_minmax(g_, scalar_params(0.0, 1.0), phase_ptrs(), partial_, dscal_ + kSlotMinMax, stream_);
-  else
-    launch_tangent_minmax(g_, phase_table(), opt_.mixing, phase_ptrs(), partial_, dscal_ + kSlotMinMax, derr_, stream_);
+  enqueue_tangent_minmax(kSlotMinMax);
   FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotMinMax, dscal_ + kSlotMinMax, 2 * sizeof(double), hipMemcpyDeviceToHost, stream_));
   check_device_error("reference material");
-  double lambda_min = hscal_[kSlotMinMax], lambda_max = -hscal_[kSlotMinMax + 1];
-  if (lambda_min < 0) lambda_min = 0;  // F:12183-12223
-  double mu_0 = opt_.method == 2 ? std::sqrt(lambda_min * lambda_max)   // getRefMaterial(..., polarization)  F:12227-12229
-                                 : 0.5 * (lambda_min + lambda_max);
-  mu_0 *= 0.5 * opt_.ref_scale;
-  opt_.mu_0 = mu_0;
+  opt_.mu_0 = ref_mu0(hscal_[kSlotMinMax], -hscal_[kSlotMinMax + 1], opt_.method, opt_.ref_scale);
   recompute_bc();  // F:22312
 }
 
 // bc_error  F:21129-21161
 double Solver::bc_error(const double* E_cur, const double* S_cur) {
-  double Emean[6], Smean[6], PE[6], QS[6], PEc[6], d[6];
+  double Emean[6], Smean[6];
   mean_strain(Emean);
   mean_stress(Smean);
-  voigt_mv(BC_P_, Emean, PE);
-  voigt_mv(BC_Q_, Smean, QS);
-  voigt_mv(BC_P_, E_cur, PEc);
-  const double norm_E = voigt_norm2(PEc);
-  for (int i = 0; i < 6; ++i) d[i] = PE[i] - E_cur[i];
-  const double err_F = voigt_norm2(d) / ((norm_E < opt_.bc_tol) ? 1 : norm_E);
-  const double norm_S = voigt_norm2(S_cur);
-  for (int i = 0; i < 6; ++i) d[i] = QS[i] - S_cur[i];
-  const double err_S = voigt_norm2(d) / ((norm_S < opt_.bc_tol) ? 1 : norm_S);
-  return err_F > err_S ? err_F : err_S;
+  return bc_error_value(BC_P_, BC_Q_, opt_.bc_tol, Emean, Smean, E_cur, S_cur);
 }
 
 // ------------------------------------------------------------------ the solver loop
@@ -1607,9 +1591,8 @@ bool Solver::run(const double* E6, const double* S6) {
 // continues from the previous one starts its error estimate there, the first one at the zero field
 double Solver::current_norm9() {
   ensure_eps();
-  launch_sum6(g_, ptrs6(eps_), true, partial_, dscal_ + kSlotScratch, stream_);
-  FG_HIP_CHECK(hipMemcpyAsync(hscal_ + kSlotScratch, dscal_ + kSlotScratch, 6 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-  FG_HIP_CHECK(hipStreamSynchronize(stream_));
+  enqueue_strain_sums(kSlotScratch, true);
+  fetch_sums(kSlotScratch, 6);
   double s9 = 0.0;
   const int nc = opt_.mode == 1 ? 3 : 6;
   for (int c = 0; c < nc; ++c) {
@@ -1628,7 +1611,7 @@ bool Solver::run_load_steps(const double* E6, const double* S6, const double* pa
                             LoadstepCallback step_cb, void* user) {
   FG_HIP_CHECK(hipSetDevice(device_));
   if (pt_.n < 1) throw std::runtime_error(plan::kNoMaterials);
-  if (nparams < 1 || first < 0 || !params) throw std::runtime_error("invalid load steps");
+  check_load_steps(params, nparams, first);
   solve_time_ = 0.0;
   cg_u_active_ = false;
   residuals_.clear();
@@ -1640,14 +1623,7 @@ bool Solver::run_load_steps(const double* E6, const double* S6, const double* pa
     Smax[i] = S6 ? S6[i] : 0.0;
   }
   recompute_bc();  // F:21354
-  {
-    const double se = std::sqrt(kEps);
-    double t[6];
-    voigt_mv(BC_P_, Smax, t);
-    if (norm2(t, 6) > se * norm2(Smax, 6)) throw std::runtime_error("Incompatible stress boundary condition specified");
-    voigt_mv(BC_Q_, Emax, t);
-    if (norm2(t, 6) > se * norm2(Emax, 6)) throw std::runtime_error("Incompatible strain boundary condition specified");
-  }
+  check_bc_compatible(BC_P_, BC_Q_, Emax, Smax);
   FG_HIP_CHECK(hipMemsetAsync(eps_, 0, 6 * (size_t)g_.n * sizeof(double), stream_));  // F:21379
   pol_state_ = false;
   u_valid_ = false;
@@ -1667,7 +1643,7 @@ bool Solver::run_load_steps(const double* E6, const double* S6, const double* pa
   const size_t f6 = 6 * (size_t)g_.n * sizeof(double);
   for (int istep = first; istep < nparams; ++istep) {
     double E[6], S[6];
-    for (int i = 0; i < 6; ++i) E[i] = params[istep] * Emax[i], S[i] = params[istep] * Smax[i];
+    load_step_values(params[istep], Emax, Smax, E, S);
     fresh_step_ = istep == first;
     const int order = opt_.loadstep_extrapolation_order;
     if (order > 0 && istep > first) {   // F:21634-21650
@@ -1684,28 +1660,9 @@ bool Solver::run_load_steps(const double* E6, const double* S6, const double* pa
       last.push_back(Kept{params[istep - 1], buf});
       const int n = (int)last.size();
       if (n >= 2) {
-        // w = V^-T tpowers with V_ij = t_i^j: solve V^T w = tpowers (Gauss elimination with partial pivoting, n <= 8)
-        double A[8][9], w[8];
-        for (int i = 0; i < n; ++i) {
-          for (int j = 0; j < n; ++j) A[i][j] = std::pow(last[j].t, i);   // (V^T)_ij = t_j^i
-          A[i][n] = std::pow(params[istep], i);
-        }
-        for (int c = 0; c < n; ++c) {
-          int piv = c;
-          for (int r = c + 1; r < n; ++r)
-            if (std::fabs(A[r][c]) > std::fabs(A[piv][c])) piv = r;
-          if (A[piv][c] == 0.0) throw std::runtime_error("Error inverting Vandermonde matrix");   // F:21490-21492
-          for (int j = 0; j <= n; ++j) std::swap(A[c][j], A[piv][j]);
-          for (int r = c + 1; r < n; ++r) {
-            const double m = A[r][c] / A[c][c];
-            for (int j = c; j <= n; ++j) A[r][j] -= m * A[c][j];
-          }
-        }
-        for (int r = n - 1; r >= 0; --r) {
-          double v = A[r][n];
-          for (int j = r + 1; j < n; ++j) v -= A[r][j] * w[j];
-          w[r] = v / A[r][r];
-        }
+        double t[8], w[8];
+        for (int i = 0; i < n; ++i) t[i] = last[i].t;
+        if (!extrapolation_weights(t, n, params[istep], w)) throw std::runtime_error("Error inverting Vandermonde matrix");   // F:21487-21490
         const double* in[8];
         for (int i = 0; i < n; ++i) in[i] = last[i].eps;
         launch_lincomb(n, in, w, eps_, 6 * g_.n, stream_);
@@ -1732,7 +1689,7 @@ bool Solver::run_one_step(const double* E0, const double* S0) {
   for (int i = 0; i < 6; ++i) F00_[i] = 0.0;
   // Displacement-based loop: eps_0 = 0 gives tau = 0, u_1 = 0 and eps_1 = E, so the loop starts from
   // u = 0 and every pass is [u_k -> norms of eps_k, f_{k+1}] + [f_{k+1} -> u_{k+1}] (see u_pass_front).
-  bool uloop = plan::plan_sweeps(plan_input(plan::Entry::Run, 1)).u_loop;
+  const bool uloop = plan::plan_sweeps(plan_input(plan::Entry::Run, 1)).u_loop;
   const bool mixed_bc = this->mixed_bc();   // (NaN until calcRefMaterial ran: Q != 0)
   if (uloop && fresh_step_) {
     FG_HIP_CHECK(hipMemsetAsync(fu_, 0, 3 * g_.n * sizeof(double), stream_));
@@ -1741,86 +1698,68 @@ bool Solver::run_one_step(const double* E0, const double* S0) {
     for (int i = 0; i < 6; ++i) E_cur_[i] = E0[i];
   }
   in_run_ = true;
+  pending_back_ = back_ready_ = false;
 
   StopRule rule = stop_rule(prev0);
-  long iter = 1;
-  // a continuing load step in the displacement loop: the state is u of the previous step (eps = E_old + sym grad u); one
-  // unrecorded pass turns it into u' with eps' = E_new + sym grad u' -- the field the reference's first iteration of the
-  // step produces -- and the loop below then measures eps' in its first pass
-  bool carry = uloop && !fresh_step_ && u_valid_;
-  bool update_ref = opt_.update_ref != 0;
-  double E[6];
-  for (int i = 0; i < 6; ++i) E[i] = E0[i];
-  bool failed = false;
-
-  for (;;) {
-    if (update_ref) {
-      calc_ref_material();
-      bc_mean(BC_QC0_, BC_M_, opt_.bc_relax, E0, S0, E);
-      update_ref = false;
+  const double nglobal = (double)nglobal_;
+  BasicLoopOps ops;   // the iteration itself: fg_basic_loop.h
+  ops.refresh_ref = [&](double* E) {
+    calc_ref_material();
+    bc_mean(BC_QC0_, BC_M_, opt_.bc_relax, E0, S0, E);
+  };
+  ops.have_u = [&] { return u_valid_; };
+  ops.mixed_bc = [&] { return mixed_bc; };   // as read before the reference material was refreshed
+  ops.start_from = [&](const double* E) {
+    for (int i = 0; i < 6; ++i) E_cur_[i] = E[i];
+  };
+  ops.carry_pass = [&](const double* E) {
+    u_pass_front(E);
+    u_pass_back();
+  };
+  ops.u_pass = [&](const double* E, bool) {   // (the sweep plan has asked mixed_bc() itself)
+    u_pass_front(E);
+    if (opt_.mode == 1 && mixed_bc && !sc_tau_sums_) {
+      // heat / porous with mixed boundary conditions (initBCProjector in GammaOperatorStaggeredHeat F:20342-20350): the
+      // LDS-tiled sweep leaves the sums of tau in kSlotMean; where it does not apply, <tau> = <P(g) - 2 mu0 g> is taken
+      // from the gradient field (two extra sweeps per pass)
+      ensure_eps();
+      launch_sc_flux_mean(g_, scalar_params(opt_.mu_0, 1.0 / (double)nglobal_), ptrs3(eps_), phase_ptrs(), partial_,
+                          dscal_ + kSlotMean, stream_);
+      eps_stale_ = true;
     }
-    bool pending_back = false;
-    pending_back_ = back_ready_ = false;
-    if (carry) {
-      if (mixed_bc) {
-        carry = false;   // (the correction of the prescribed mean needs <tau> on the host: take the strain-state pass)
-        uloop = false;
-      } else {
-        u_pass_front(E);
-        u_pass_back();
-        carry = false;
-      }
-    }
-    if (uloop && u_valid_) {
-      if (iter == 1 && fresh_step_)
-        for (int i = 0; i < 6; ++i) E_cur_[i] = E[i];  // eps_1 = E (u_1 = 0)
-      u_pass_front(E);
-      if (opt_.mode == 1 && mixed_bc && !sc_tau_sums_) {
-        // heat / porous with mixed boundary conditions (initBCProjector in GammaOperatorStaggeredHeat F:20342-20350): the
-        // LDS-tiled sweep leaves the sums of tau in kSlotMean; where it does not apply, <tau> = <P(g) - 2 mu0 g> is taken
-        // from the gradient field (two extra sweeps per pass)
-        ensure_eps();
-        launch_sc_flux_mean(g_, scalar_params(opt_.mu_0, 1.0 / (double)nglobal_), ptrs3(eps_), phase_ptrs(), partial_,
-                            dscal_ + kSlotMean, stream_);
-        eps_stale_ = true;
-      }
-      pending_back = true;
-      pending_back_ = true;   // fetch_norms_and_errors enqueues the FFT chain behind the copies
-    } else {
-      // no displacement behind the strain field (a step that starts from a given / extrapolated field, mixed boundary
-      // conditions with their correction term in the strain): strain-state pass.  If it leaves a displacement, the loop
-      // goes on in displacement space after the unrecorded pass of a continuing step (carry).
-      basic_scheme(E);
-      if (uloop && u_valid_ && !mixed_bc) carry = true;
-      else uloop = false;
-    }
-    fetch_norms_and_errors("stress");
-    if (pending_back && mixed_bc) {
-      // applyBCProjector  F:20247-20270 with bc_relax = 1: eps_{k+1} = E + alpha MQ:<tau_k> + sym grad u_{k+1}
-      double F0[6], t1[6];
-      for (int c = 0; c < 6; ++c) F0[c] = hscal_[kSlotMean + c] / (double)nglobal_;
-      if (opt_.mode == 1)   // components 3..5 do not exist; the flux-mean sweep has divided by N already, the tiled sweep has not
-        for (int c = 0; c < 6; ++c) F0[c] = c < 3 ? hscal_[kSlotMean + c] / (sc_tau_sums_ ? (double)nglobal_ : 1.0) : 0.0;
-      if (opt_.mixing == kMixLaminate)
-        for (int c = 0; c < 6; ++c) F0[c] += hscal_[kSlotScratch + c] / (double)nglobal_;
-      voigt_mv(BC_MQ_, F0, t1);
-      for (int c = 0; c < 6; ++c) E_next_[c] = E[c] - t1[c];   // alpha = -1  (F:20575)
-    }
-
+    pending_back_ = true;   // fetch_norms_and_errors enqueues the FFT chain behind the copies
+  };
+  ops.strain_pass = [&](const double* E, bool) { basic_scheme(E); };
+  ops.wait = [&] { fetch_norms_and_errors("stress"); };
+  ops.mq_mean_tau = [&](double* t6) {
+    double F0[6];
+    for (int c = 0; c < 6; ++c) F0[c] = hscal_[kSlotMean + c] / nglobal;
+    if (opt_.mode == 1)   // components 3..5 do not exist; the flux-mean sweep has divided by N already, the tiled sweep has not
+      for (int c = 0; c < 6; ++c) F0[c] = c < 3 ? hscal_[kSlotMean + c] / (sc_tau_sums_ ? nglobal : 1.0) : 0.0;
+    if (opt_.mixing == kMixLaminate)
+      for (int c = 0; c < 6; ++c) F0[c] += hscal_[kSlotScratch + c] / nglobal;
+    voigt_mv(BC_MQ_, F0, t6);
+  };
+  ops.norm = [&] {
     for (int c = 0; c < 6; ++c) sumsq_[c] = hscal_[kSlotSumSq + c];
-    rule.measure(norm9_of_sums(sumsq_, (double)nglobal_));
-    if (opt_.error_estimator >= 2) estimator_update(&rule.abs_err, &rule.rel_err);   // sigma / energy / none: F:14410-14587
-    if (converged(rule, iter, [&] { return bc_error(E0, S0) <= opt_.bc_tol; }, &failed)) break;
-    if (pending_back) adopt_back();
-    iter++;
-  }
+    return norm9_of_sums(sumsq_, nglobal);
+  };
+  ops.estimator = [&](StopRule& r) {
+    if (opt_.error_estimator >= 2) estimator_update(&r.abs_err, &r.rel_err);
+  };
+  ops.bc_ok = [&] { return bc_error(E0, S0) <= opt_.bc_tol; };
+  ops.adopt = [&](const double* E_next) {
+    for (int c = 0; c < 6; ++c) E_next_[c] = E_next[c];
+    adopt_back();
+  };
+  const BasicResult end = basic_loop(*this, ops, rule, E0, fresh_step_, uloop, opt_.update_ref != 0);
   pending_back_ = back_ready_ = false;
   in_run_ = false;
-  iterations_ = iter;
+  iterations_ = end.iter;
   ensure_eps();
   FG_HIP_CHECK(hipStreamSynchronize(stream_));
   solve_time_ += now_seconds() - t_start;
-  return failed;
+  return end.failed;
 }
 
 // ------------------------------------------------------------------ the polarisation loop

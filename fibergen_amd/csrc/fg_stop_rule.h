@@ -60,6 +60,36 @@ struct MeanEstimator {
   }
 };
 
+// create_error_estimator  F:14940-14972 for these estimators, on a site (Solver, SlabGroup) that supplies mean_stress(m6),
+// mean_energy() and each_estimator(f), which applies f to its estimator (the group: to every member's; all hold the same
+// all-reduced means).  Their constructors run on the field the step starts from (zero for a first step: <sigma> = 0, <W> = 0),
+// update() after every iteration.
+template <class Site>
+void estimator_begin(Site& site, int error_estimator, bool fresh) {
+  if (error_estimator == 2) {
+    double m[6] = {0, 0, 0, 0, 0, 0};
+    if (!fresh) site.mean_stress(m);
+    site.each_estimator([&](MeanEstimator& e) { e.start_sigma(m); });
+  } else if (error_estimator == 3) {
+    const double w = fresh ? 0.0 : site.mean_energy();
+    site.each_estimator([&](MeanEstimator& e) { e.start_energy(w); });
+  }
+}
+
+template <class Site>
+void estimator_update(Site& site, int error_estimator, double* abs_err, double* rel_err) {
+  if (error_estimator == 2) {
+    double m[6];
+    site.mean_stress(m);
+    site.each_estimator([&](MeanEstimator& e) { e.update_sigma(m, abs_err, rel_err); });
+  } else if (error_estimator == 3) {
+    const double w = site.mean_energy();
+    site.each_estimator([&](MeanEstimator& e) { e.update_energy(w, abs_err, rel_err); });
+  } else if (error_estimator == 4) {
+    *abs_err = *rel_err = 1.0;
+  }
+}
+
 enum class StopDecision { kContinue, kStop, kFail };
 
 // what the callbacks answered after an iteration

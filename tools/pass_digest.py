@@ -6,6 +6,8 @@ arithmetic on every path the list reaches: the check for a change that must leav
     python tools/pass_digest.py tiles > profiles/pass_digest_tiles_<build>.txt     (a second list: the tiled marching sweeps)
     python tools/pass_digest.py fft > profiles/pass_digest_fft_<build>.txt         (a third: every transform family per axis)
     python tools/pass_digest.py reuss > profiles/pass_digest_reuss_<build>.txt     (a fourth: mixing_rule reuss on every sweep)
+    python tools/pass_digest.py slab > profiles/pass_digest_slab_<build>.txt       (a fifth: groups of 1, 2 and 4 slabs on one GPU)
+    python tools/pass_digest.py steps > profiles/pass_digest_steps_<build>.txt     (a sixth: load paths on the lone solver)
 
 One line per run: grid, name, the digest of the residuals, the digest of the field and the iteration count -- or the solver's
 error text where a combination is refused (a refusal is part of the behaviour that is compared)."""
@@ -49,9 +51,14 @@ def general_stiffness():
     return a @ a.T / 6 + 2.0 * np.eye(6)
 
 
-def solver(grid, mode="elasticity", mats=((0.4, 0.6), (4.0, 2.5)), normals=False, general=False, aniso=False, fine=False, **opts):
+def solver(grid, mode="elasticity", mats=((0.4, 0.6), (4.0, 2.5)), normals=False, general=False, aniso=False, fine=False, group=0,
+           **opts):
     phi, nrm = geometry(grid)
-    s = LSSolver(*grid)
+    if group:   # all slabs of the problem on this GPU, below the C ABI
+        from fibergen_amd.distributed import SlabGroup
+        s = SlabGroup(*grid, nranks=group)
+    else:
+        s = LSSolver(*grid)
     s.set_options(mode=mode)
     if "gamma_scheme" in opts:
         s.set_options(gamma_scheme=opts.pop("gamma_scheme"))
@@ -75,14 +82,22 @@ def digest(a):
     return hashlib.sha256(np.ascontiguousarray(a, dtype=np.float64).tobytes()).hexdigest()
 
 
-def report(name, grid, E=E6, mixed=False, **kw):
+def report(name, grid, E=E6, mixed=False, params=None, callback=False, **kw):
+    """params: a load path (run_load_steps from its first entry) instead of one run; callback: a convergence callback that never
+    asks to stop (a group of several slabs then votes after every pass)"""
     tag = "%s %s" % ("x".join(map(str, grid)), name)
     try:
         s = solver(grid, **kw)
         if mixed:
             s.set_bc_projector(P_MIXED)
             E = E3_MIXED if len(E) == 3 else E_MIXED
-        s.run(E, (S3_MIXED if len(E) == 3 else S_MIXED) if mixed else None)
+        if callback:
+            s.set_convergence_callback(lambda: False)
+        S = (S3_MIXED if len(E) == 3 else S_MIXED) if mixed else None
+        if params:
+            s.run_load_steps(E, S, params=params, first=0)
+        else:
+            s.run(E, S)
         reached = "".join(" %s=%d" % (c, s.counter(c)) for c in COUNTERS if s.counter(c) > 0)
         print("%s: %s %s %d%s" % (tag, digest(s.residuals), digest(s.get_field("epsilon")), s.iterations, reached))
         s.close()
@@ -256,5 +271,57 @@ def reuss():
         report("reuss viscosity", grid, **R, **VISC)
 
 
+GSLAB = ((8, 16, 128), (16, 16, 16), (12, 10, 6))   # the displacement loop of the slabs; the strain-state pipeline; its generic transforms
+
+
+def slab():
+    """the slab driver (SlabGroup::run_step, run_cg and the collective measurements) in groups of 1, 2 and 4 members on one GPU.
+    A group the grid cannot be cut into, or a feature the slabs refuse, prints its refusal"""
+    for grid in GSLAB:
+        for P in (1, 2, 4):
+            def rep(name, **kw):
+                report("P=%d %s" % (P, name), grid, group=P, **kw)
+            for method in ("basic", "cg"):
+                rep(method, method=method)
+                rep("%s laminate" % method, method=method, **LAM)
+            rep("heat", **HEAT)
+            rep("viscosity", **VISC)
+            rep("mixed bc", mixed=True)
+            rep("laminate mixed bc", mixed=True, **LAM)
+            rep("heat mixed bc", mixed=True, **HEAT)
+            rep("two steps", params=(0.5, 1.0))
+            rep("three steps laminate", params=(0.25, 0.5, 1.0), **LAM)
+            rep("two steps mixed bc", mixed=True, params=(0.5, 1.0))
+            rep("update_ref", update_ref=1)
+            rep("update_ref mixed bc two steps", mixed=True, update_ref=1, params=(0.5, 1.0))
+            for est in ("sigma", "energy"):
+                rep("estimator %s" % est, error_estimator=est)
+                rep("estimator %s cg" % est, error_estimator=est, method="cg")
+            rep("callback", callback=True)
+            rep("callback two steps", callback=True, params=(0.5, 1.0))
+
+
+def steps():
+    """load paths on the lone solver (Solver::run_load_steps, the carry pass of a continuing step, the polynomial extrapolation)"""
+    PATHS = ((0.5, 1.0), (0.25, 0.5, 1.0), (0.1, 0.3, 0.6, 1.0))
+    for grid in (G16, GODD, (4, 16, 80)):
+        for path in PATHS:
+            for order in (0, 1, 2):
+                report("%d steps order=%d" % (len(path), order), grid, params=path, loadstep_extrapolation_order=order)
+        report("3 steps laminate order=1", grid, params=PATHS[1], loadstep_extrapolation_order=1, **LAM)
+        report("3 steps u_loop=0", grid, params=PATHS[1], u_loop=0)
+        report("3 steps cg", grid, params=PATHS[1], method="cg")
+        report("3 steps mixed bc", grid, mixed=True, params=PATHS[1])
+        report("3 steps laminate mixed bc", grid, mixed=True, params=PATHS[1], **LAM)
+        report("3 steps update_ref", grid, params=PATHS[1], update_ref=1)
+        report("3 steps update_ref mixed bc", grid, mixed=True, params=PATHS[1], update_ref=1)
+        for est in ("sigma", "energy"):
+            report("3 steps estimator %s" % est, grid, params=PATHS[1], error_estimator=est)
+        # heat with mixed boundary conditions: on G16 and GODD the tiled sweep does not fit and <tau> comes from the flux-mean sweep
+        report("3 steps heat", grid, params=PATHS[1], **HEAT)
+        report("3 steps heat mixed bc", grid, mixed=True, params=PATHS[1], **HEAT)
+        report("equal parameters order=1", grid, params=(0.5, 0.5, 1.0), loadstep_extrapolation_order=1)
+
+
 if __name__ == "__main__":
-    {"tiles": tiles, "fft": fft, "reuss": reuss}.get((sys.argv[1:] or [""])[0], main)()
+    {"tiles": tiles, "fft": fft, "reuss": reuss, "slab": slab, "steps": steps}.get((sys.argv[1:] or [""])[0], main)()
